@@ -19,16 +19,21 @@ round-robin to the N ranks (shard_batch), each rank's gradient scaled by
 local_B / global_B before the sum.  ms_per_step / value use the median step
 (max over ranks per step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts the N
 ranks itself (a torch.distributed.run child, before any GPU call) and exits
 with its status.
 
-Prints ONE JSON line (rank 0) with the metric, a live roofline of the dominant
-kernel (per-launch HIP events on the kernel's own stream) and the CPU oracle
-baseline timed on this host.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line
+(rank 0) with the metric.  --dump-outputs DIR also writes what the last timed
+step returned (dump_outputs) as DIR/<name>.npy; the inputs and seeds are fixed,
+so two builds can be compared output for output.  --full adds the legs beside
+the headline to the same line: the H2D-inclusive loop, a live roofline of the
+dominant kernel (per-launch HIP events on the kernel's own stream, a separate
+profiled pass), the other scheduled-sampling regimes, the CPU oracle baseline
+timed on this host and the loss parity against the reference.
 """
 import argparse
 import json
@@ -657,6 +662,31 @@ def h2d_loop(model, step, host_batch, dev, warmup, steps, world, frames_per_step
                     'previous step'}
 
 
+DUMP_SAMPLE = 4 << 20    # elements kept of each flat buffer (16 MB as float32)
+
+
+def dump_outputs(out_dir, model, losses, last):
+    """What a caller of the timed step holds after its last call, as
+    out_dir/<name>.npy: `loss` (float64: every loss value the last step
+    returned, the total first), `losses` (float64: the total loss of each timed
+    step), and `params` / `grads` (float32: the model's flat parameter buffer
+    after the last update and the flat gradient that update consumed).  A flat
+    buffer of more than DUMP_SAMPLE elements is written as a fixed sample: the
+    elements at sorted indices drawn by numpy RandomState(1623), the same for
+    every run of the same model."""
+    os.makedirs(out_dir, exist_ok=True)
+    vals = last.value() if hasattr(last, 'value') else ([] if last is None else last)
+    vals = list(vals) if isinstance(vals, (list, tuple)) else [vals]
+    np.save(os.path.join(out_dir, 'loss.npy'), np.asarray([float(v) for v in vals], np.float64))
+    np.save(os.path.join(out_dir, 'losses.npy'), np.asarray(losses, np.float64))
+    for name, attr in (('params', '_flat_param'), ('grads', '_flat_grad')):
+        flat = getattr(model, attr).detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(1623).randint(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -666,6 +696,13 @@ def main():
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--batch', type=int, default=32, help='utterances per GPU')
     ap.add_argument('--frames', type=int, default=1000)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline loop also run the legs beside it: the profiled '
+                         'roofline pass, the H2D-inclusive loop, the other scheduled-sampling '
+                         'regimes, the CPU baseline and the loss parity against the reference')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (losses, updated parameters, '
+                         'gradients) as DIR/<name>.npy')
     ap.add_argument('--cpu-utts', type=int, default=0,
                     help='utterances of the timed CPU step (0: per config, ~10-30 s of CPU work)')
     ap.add_argument('--parity-utts', type=int, default=6)
@@ -787,6 +824,7 @@ def main():
             m, lv = step(m, batch)
             lv_all.append(lv)
             mk.append(time.perf_counter())
+        last = lv_all[-1] if lv_all else None
         lv_all = [float(v) for v in lv_all]
         torch.cuda.synchronize()
         if world > 1:
@@ -798,7 +836,7 @@ def main():
             t = torch.tensor([el] + list(st), dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el, st = float(t[0].item()), t[1:].cpu().numpy()
-        return el, st, lv_all
+        return el, st, lv_all, last
 
     set_ss(args.ss)
     for _ in range(args.warmup):
@@ -807,8 +845,10 @@ def main():
     from pytorch_end2end_speech_recognition_amd.utils.training import training_loop as TL
     TL.reset_step_stats()
     # the headline: unprofiled
-    elapsed, step_s, losses = timed(args.steps)
+    elapsed, step_s, losses, last_lv = timed(args.steps)
     step_stats = dict(TL.STEP_STATS)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, losses, last_lv)
     if world > 1:
         fr = torch.tensor([frames_per_step], dtype=torch.float64, device=dev)
         dist.all_reduce(fr, op=dist.ReduceOp.SUM)
@@ -821,18 +861,18 @@ def main():
     mean_us = (ctypes.c_double * NK)()
     launches = (ctypes.c_longlong * NK)()
     mean_work = (ctypes.c_double * NK)()
-    prof_steps = args.steps if args.prof_steps < 0 else args.prof_steps
+    prof_steps = (args.steps if args.prof_steps < 0 else args.prof_steps) if args.full else 0
     prof_elapsed = None
     samples = {}
     if prof_steps > 0:
-        prof_elapsed, _, _ = timed(prof_steps, profile=True)
+        prof_elapsed, _, _, _ = timed(prof_steps, profile=True)
         N.call('asr_prof_end', ctypes.cast(mean_us, ctypes.c_void_p),
                ctypes.cast(launches, ctypes.c_void_p), ctypes.cast(mean_work, ctypes.c_void_p),
                NK)
         samples = prof_samples()
     # scheduled-sampling legs: the same step at the other sampling regimes
     ss_legs = None
-    if ss_cfg and args.steps > 0:
+    if args.full and ss_cfg and args.steps > 0:
         ss_legs = {}
         for mode in ('steady', 'early', 'off'):
             if mode == args.ss:
@@ -841,12 +881,12 @@ def main():
             for _ in range(2):
                 model, lv = step(model, batch)
             float(lv)
-            el, _, _ = timed(args.steps)
+            el, _, _, _ = timed(args.steps)
             ss_legs[mode] = {'ms_per_step': round(1000.0 * el / args.steps, 3),
                              'ss_prob': round(float(model._ss_prob), 6)}
         set_ss(args.ss)
 
-    h2d_steps = args.steps if args.h2d_steps < 0 else args.h2d_steps
+    h2d_steps = (args.steps if args.h2d_steps < 0 else args.h2d_steps) if args.full else 0
     h2d = h2d_loop(model, step, host_batch, dev, args.warmup, h2d_steps, world,
                    total_frames_per_step) if h2d_steps > 0 else None
 
@@ -864,7 +904,7 @@ def main():
         roofline['encoder_train_flops_per_step_per_gpu'] = enc_flops
 
     cpu = parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu, sd0 = cpu_baseline(cfg, host_batch, args.cpu_utts or cfg.get('cpu_utts', 6))
         if not args.no_parity:
             parity = parity_report(cfg, sd0, host_batch, args.parity_utts)
@@ -889,7 +929,9 @@ def main():
                    'profiling': ('none in the headline loop; the roofline samples come from '
                                  'a separate pass of %d profiled steps (%s ms/step)'
                                  % (prof_steps, round(1000.0 * prof_elapsed / prof_steps, 3)
-                                    if prof_elapsed else None))},
+                                    if prof_elapsed else None)) if args.full else 'none'},
+        'full': bool(args.full),
+        'outputs_dir': args.dump_outputs,
         'steps_stats': {'skipped': step_stats['skipped'],
                         'recurrence_give_ups': step_stats['recurrence_give_ups'],
                         'steps': step_stats['steps'],

@@ -64,7 +64,7 @@ _H2D_PINNED = os.environ.get('ASR_H2D_PINNED', '1') != '0'   # (A/B: 0 = pageabl
 # arena was cleared again by another forward since) takes a private workspace
 # and the launch's own memset.
 # ---------------------------------------------------------------------------
-_arena = {'buf': None, 'gen': 0, 'off': 0, 'slot': 0}
+_arena = {'buf': None, 'gen': 0, 'off': 0, 'slot': 0, 'end': 0}
 
 
 def rec_arena_begin(dev, B, H, passes):
@@ -83,7 +83,8 @@ def rec_arena_begin(dev, B, H, passes):
     # only each slot's leading bytes must be zero (one strided fill)
     zb = min(int(N.query('asr_lstm_ws_zero_bytes', B, H)), slot)
     buf[:need].view(int(passes), slot)[:, :zb].zero_()
-    _arena.update(buf=buf, gen=_arena['gen'] + 1, off=0, slot=slot)
+    # end: a reused buffer may be longer than this generation's cleared slots
+    _arena.update(buf=buf, gen=_arena['gen'] + 1, off=0, slot=slot, end=need)
 
 
 def _arena_take(nbytes, dev):
@@ -91,7 +92,7 @@ def _arena_take(nbytes, dev):
     a = _arena
     if not a['slot'] or a['buf'] is None or a['buf'].device != dev or nbytes > a['slot']:
         return None
-    if a['off'] + a['slot'] > a['buf'].numel():
+    if a['off'] + a['slot'] > a['end']:
         return None
     t = a['buf'][a['off']:a['off'] + a['slot']]
     a['off'] += a['slot']

@@ -105,3 +105,31 @@ def test_roofline_rows_per_kernel_instantiation():
     assert abs(op['mean_call_us'] - 220.0) < 1e-9
     assert abs(sum(v['share_of_timed_kernel_time'] for k, v in o.items() if 'ctc_op' not in k)
                + r['share_of_timed_kernel_time'] - 1.0) < 0.01
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float64 losses, float32 flat buffers; a buffer longer
+    than DUMP_SAMPLE leaves as the same seeded sample on every call."""
+    bench = _bench()
+    from types import SimpleNamespace
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 64)
+    g = torch.Generator().manual_seed(3)
+    model = SimpleNamespace(_flat_param=torch.randn(1000, generator=g),
+                            _flat_grad=torch.randn(40, generator=g))
+    last = SimpleNamespace(value=lambda: [1.5, 0.25])
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), model, [3.0, 2.0, 1.5], last)
+    got = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in ('loss', 'losses', 'params',
+                                                                    'grads')}
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == ['grads.npy', 'loss.npy', 'losses.npy',
+                                                       'params.npy']
+    assert got['loss'].dtype == np.float64 and got['loss'].tolist() == [1.5, 0.25]
+    assert got['losses'].dtype == np.float64 and got['losses'].tolist() == [3.0, 2.0, 1.5]
+    assert got['grads'].dtype == np.float32
+    assert np.array_equal(got['grads'], model._flat_grad.numpy())
+    assert got['params'].dtype == np.float32 and got['params'].shape == (64,)
+    assert np.isin(got['params'], model._flat_param.numpy()).all()
+    assert np.array_equal(got['params'], np.load(str(tmp_path / 'b' / 'params.npy')))
+    # a synchronous step's plain float loss
+    bench.dump_outputs(str(tmp_path / 'c'), model, [0.5], 0.5)
+    assert np.load(str(tmp_path / 'c' / 'loss.npy')).tolist() == [0.5]

@@ -72,3 +72,31 @@ def test_arena_bitwise_equals_per_launch_memset(cuda_dev, monkeypatch, bf16_mode
     assert la.item() == ref[0][0] and lb.item() == ref[1][0]
     assert torch.equal(ga, ref[0][1]), int((ga != ref[0][1]).sum())
     assert torch.equal(gb, ref[1][1]), int((gb != ref[1][1]).sum())
+
+
+@pytest.mark.gpu
+def test_arena_hands_out_only_cleared_slots(cuda_dev, bf16_mode):
+    """A generation that reuses a longer buffer of an earlier, larger arena
+    clears only its own slots: nothing past them is handed out (a layer op
+    called outside a model would otherwise skip its memset on a workspace that
+    still holds an earlier launch's granules)."""
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.rec_arena_begin(cuda_dev, 32, 512, 10)
+    big = native_ops._arena['buf']
+    big.fill_(0xff)
+    native_ops.rec_arena_begin(cuda_dev, 16, 256, 2)
+    assert native_ops._arena['buf'] is big
+    nb = N.query('asr_lstm_workspace_bytes', 16, 256, native_ops.BF16, 0)
+    zb = int(N.query('asr_lstm_ws_zero_bytes', 16, 256))
+    taken = []
+    while True:
+        res = native_ops._arena_take(nb, cuda_dev)
+        if res is None:
+            break
+        taken.append(res)
+        assert len(taken) <= 2
+    assert len(taken) == 2
+    for t, gen in taken:
+        assert gen == native_ops._arena['gen']
+        assert int(t[:zb].max()) == 0

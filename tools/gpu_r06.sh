@@ -16,7 +16,7 @@ if [ "${TRACE:-0}" = 1 ]; then
   cat gpurun_out/trace_$T.txt | tail -14
 fi
 for C in $BENCH; do
-  timeout -k 10 400 python -u bench.py --config $C --no-cpu-baseline --no-parity --steps ${STEPS:-20} --warmup 5 ${BARGS} \
+  timeout -k 10 400 python -u bench.py --full --config $C --no-cpu-baseline --no-parity --steps ${STEPS:-20} --warmup 5 ${BARGS} \
     > gpurun_out/b_${C}_$T.json 2> gpurun_out/b_${C}_$T.err || { tail -20 gpurun_out/b_${C}_$T.err; exit 1; }
   python3 -c "
 import json;d=json.load(open('gpurun_out/b_${C}_$T.json'));r=d['roofline']
