@@ -460,7 +460,9 @@ int asr_add_forward(const float* a, const float* b, float* y, long long n, void*
 /* dst[r][0:ncols] = bf16(src[row(r) + 0:ncols]) (round to nearest even) for r <
  * nrows, rows through an asr_rowmap_t (perm / subsample gathers; rows outside
  * [0, t_limit) become zeros).  Builds the dense bf16 GEMM operands of the
- * encoder layer (its input X, W_ih) in bf16 mode. */
+ * encoder layer (its input X, W_ih) in bf16 mode.  Any alignment of src and
+ * dst is accepted: rows that are not 16-B aligned take a scalar kernel (the
+ * same bits, and for the dropout form below the same mask). */
 int asr_convert_rows_bf16(const float* src, asr_rowmap_t map, int nrows, int ncols,
                           uint16_t* dst, void* stream);
 /* Same with an output row pitch ld >= ncols; columns [ncols, ld) are zeros (a

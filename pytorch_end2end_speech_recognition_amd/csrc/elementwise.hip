@@ -207,6 +207,16 @@ __global__ void add_fwd(const float* __restrict__ a, const float* __restrict__ b
     y[i] = a[i] + b[i];
 }
 
+// The 16-B loads and stores of convert_rows_kernel's vector form (rows of a
+// multiple of 8 columns) are legal; a source or destination that is not --
+// a view at an odd offset into a larger tensor -- takes convert_rows_cols,
+// which computes the same values (and the same dropout mask: element offsets
+// from src) with 4-B loads and 2-B stores.
+inline bool rows_16b_aligned(const void* src, const void* dst, const asr_rowmap_t& m) {
+  return ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && m.stride_t % 4 == 0 &&
+         m.stride_b % 4 == 0;
+}
+
 inline int grid_for(long long n) {
   long long b = (n + 255) / 256;
   return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
@@ -367,13 +377,9 @@ extern "C" int asr_convert_rows_bf16_ld(const float* src, asr_rowmap_t map, int 
                                         int ncols, int ld, uint16_t* dst, void* stream) {
   ASR_REQUIRE(src && dst && nrows >= 0 && ncols >= 0 && ld >= ncols, ASR_ERR_ARG,
               "convert_rows: bad args");
-  if (ncols % 8 == 0 && ld % 8 == 0)
-    ASR_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 &&
-                    map.stride_t % 4 == 0 && map.stride_b % 4 == 0,
-                ASR_ERR_ARG, "convert_rows: vector path needs 16-B aligned rows");
   const long long n = (long long)nrows * ((ld + 7) / 8);
   if (n <= 0) return ASR_OK;
-  if (!(ncols % 8 == 0 && ld % 8 == 0))
+  if (!(ncols % 8 == 0 && ld % 8 == 0 && rows_16b_aligned(src, dst, map)))
     hipLaunchKernelGGL(convert_rows_cols<false>, dim3((ld + 1023) / 1024, std::min(nrows, 8192)),
                        dim3(256), 0, (hipStream_t)stream, src, map, nrows, ncols, ld, dst, 0.f,
                        0ull);
@@ -399,13 +405,9 @@ extern "C" int asr_convert_rows_bf16_dropout(const float* src, asr_rowmap_t map,
   ASR_REQUIRE(p >= 0.f && p < 1.f, ASR_ERR_ARG, "convert_rows_dropout: p=%f", (double)p);
   if (p == 0.f) return asr_convert_rows_bf16_ld(src, map, nrows, ncols, ncols, dst, stream);
   ASR_REQUIRE(src && dst && nrows >= 0 && ncols >= 0, ASR_ERR_ARG, "convert_rows: bad args");
-  if (ncols % 8 == 0)
-    ASR_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 &&
-                    map.stride_t % 4 == 0 && map.stride_b % 4 == 0,
-                ASR_ERR_ARG, "convert_rows: vector path needs 16-B aligned rows");
   const long long n = (long long)nrows * ((ncols + 7) / 8);
   if (n <= 0) return ASR_OK;
-  if (ncols % 8 != 0)
+  if (!(ncols % 8 == 0 && rows_16b_aligned(src, dst, map)))
     hipLaunchKernelGGL(convert_rows_cols<true>, dim3((ncols + 1023) / 1024, std::min(nrows, 8192)),
                        dim3(256), 0, (hipStream_t)stream, src, map, nrows, ncols, ncols, dst, p,
                        seed);

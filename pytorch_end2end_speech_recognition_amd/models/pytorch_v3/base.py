@@ -408,6 +408,8 @@ class FlatOptimizer(torch.optim.Optimizer):
                N.ptr(guard), N.stream_handle(p.device))
         if sh is not None:
             ops.param_shadow_written(sh, p, self.model.parameters())
+        else:
+            ops.param_shadow_skipped(p)
         return loss
 
     def clip_and_step(self, max_norm, guard=None):

@@ -62,9 +62,14 @@ _H2D_PINNED = os.environ.get('ASR_H2D_PINNED', '1') != '0'   # (A/B: 0 = pageabl
 # their memset (asr_lstm_ws_prezeroed).  A slot is handed out once per
 # generation; a backward whose reservation is from an older generation (the
 # arena was cleared again by another forward since) takes a private workspace
-# and the launch's own memset.
+# and the launch's own memset.  Only each slot's leading bytes are cleared --
+# what a tagged-granule launch of the arena's own shape zeroes -- so a launch
+# of another shape or compute dtype (a layer op called outside the model) gets
+# a slot only when that prefix covers what it would clear itself.
 # ---------------------------------------------------------------------------
-_arena = {'buf': None, 'gen': 0, 'off': 0, 'slot': 0, 'end': 0}
+_arena = {'buf': None, 'gen': 0, 'off': 0, 'slot': 0, 'end': 0, 'zero': 0, 'cd': None}
+# recurrence launches whose workspace came from the arena / was their own
+ARENA_STATS = {'granted': 0, 'private': 0}
 
 
 def rec_arena_begin(dev, B, H, passes):
@@ -81,16 +86,24 @@ def rec_arena_begin(dev, B, H, passes):
     if buf is None or buf.device != dev or buf.numel() < need:
         buf = torch.empty(need, dtype=torch.uint8, device=dev)
     # only each slot's leading bytes must be zero (one strided fill)
-    zb = min(int(N.query('asr_lstm_ws_zero_bytes', B, H)), slot)
+    zero = int(N.query('asr_lstm_ws_zero_bytes', B, H))
+    zb = min(zero, slot)
     buf[:need].view(int(passes), slot)[:, :zb].zero_()
     # end: a reused buffer may be longer than this generation's cleared slots
-    _arena.update(buf=buf, gen=_arena['gen'] + 1, off=0, slot=slot, end=need)
+    _arena.update(buf=buf, gen=_arena['gen'] + 1, off=0, slot=slot, end=need, zero=zero, cd=cd)
 
 
-def _arena_take(nbytes, dev):
-    """(zeroed slot tensor, generation) from the current arena, or None."""
+def _arena_take(nbytes, dev, zero_bytes):
+    """(zeroed slot tensor, generation) from the current arena, or None.
+    zero_bytes: asr_lstm_ws_zero_bytes of the launch's own shape, the leading
+    bytes it would clear itself.  A slot's first min(zero, slot) bytes are
+    zero, so a launch with nbytes <= slot and zero_bytes <= zero finds every
+    byte it needs zero (it needs none past its nbytes); any other launch, or
+    one in another compute dtype than the arena was sized for, is refused."""
     a = _arena
     if not a['slot'] or a['buf'] is None or a['buf'].device != dev or nbytes > a['slot']:
+        return None
+    if zero_bytes > a['zero'] or a['cd'] != compute_dtype():
         return None
     if a['off'] + a['slot'] > a['end']:
         return None
@@ -303,6 +316,16 @@ def param_shadow_written(sh, flat, params):
     sh.param_versions = {id(p): p._version for p in params}
 
 
+def param_shadow_skipped(flat):
+    """An optimizer step over `flat` ran without a shadow to write (fp32 mode,
+    ASR_PARAM_SHADOW=0): the kernel changed the parameters without bumping a
+    version, so a shadow written by an earlier step is void until a later
+    step writes it again."""
+    for sh in _shadows.values():
+        if sh.flat() is flat:
+            sh.param_versions = None
+
+
 def _shadow_rows(w, params):
     """bf16 view of the shadow's copy of `w` (a dense view of a flat parameter
     buffer, spanning `params`), or None when there is no current shadow."""
@@ -382,14 +405,16 @@ def _linear_forward(x, weight, bias, drop, lse=None, ld=None):
             SHADOW_STATS['linear_hits'] += 1
         elif not fused_drop and K % 8 == 0 and os.environ.get('ASR_LINEAR_MULTI', '1') != '0':
             # input, weight and zero pad rows staged in one launch (the same bits)
-            xo = torch.empty(M, Kp, dtype=torch.bfloat16, device=x.device)
-            wo = torch.empty(Np, Kp, dtype=torch.bfloat16, device=x.device)
-            jobs = [(x, rowmap(K), M, K, xo.data_ptr()), (weight, rowmap(K), Nout, K, wo.data_ptr())]
+            # (a declined launch -- an operand that is not 16-B aligned -- wrote
+            # nothing: xm / wm are dropped and both are converted one by one below)
+            xm = torch.empty(M, Kp, dtype=torch.bfloat16, device=x.device)
+            wm = torch.empty(Np, Kp, dtype=torch.bfloat16, device=x.device)
+            jobs = [(x, rowmap(K), M, K, xm.data_ptr()), (weight, rowmap(K), Nout, K, wm.data_ptr())]
             if Np > Nout:
                 jobs.append((weight, rowmap(0, t_limit=1, rows_per_b=Np - Nout, t_add=1),
-                             Np - Nout, Kp, wo.data_ptr() + Nout * Kp * 2))
+                             Np - Nout, Kp, wm.data_ptr() + Nout * Kp * 2))
             if M > 0 and _convert_multi(jobs, x.device):
-                return _linear_gemm(xo, wo, y, ld, M, Nout, Kp, bias, lse, x.device) + (stage,)
+                return _linear_gemm(xm, wm, y, ld, M, Nout, Kp, bias, lse, x.device) + (stage,)
         # fused_drop: K % 8 == 0, so Kp == K and the dropped copy is the operand
         xo = (convert_rows_bf16(x, rowmap(K), M, K, drop=drop) if fused_drop else
               _staged(x, M, K, Kp))
@@ -1399,11 +1424,14 @@ class BLSTMLayerFn(torch.autograd.Function):
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         cst = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 0)
-        slot = _arena_take(nb, dev)         # zeroed by rec_arena_begin
+        zb = N.query('asr_lstm_ws_zero_bytes', B, H)
+        slot = _arena_take(nb, dev, zb)     # zeroed by rec_arena_begin
         ws = slot[0] if slot is not None else _ws(nb, dev)
         pz = slot is not None
+        ARENA_STATS['granted' if pz else 'private'] += 1
         # the backward's slot, reserved now so the arena's one fill covers it
-        ctx.bws = _arena_take(N.query('asr_lstm_workspace_bytes', B, H, cd, 2), dev) if pz else None
+        ctx.bws = (_arena_take(N.query('asr_lstm_workspace_bytes', B, H, cd, 2), dev, zb)
+                   if pz else None)
         whh_r = w_hh.data_ptr() + 4 * H * H * 4
         y_f32, out_drop = out_spec
         handoff = None     # (bf16 tensor the next layer stages from, its dropout)
@@ -1534,6 +1562,7 @@ class BLSTMLayerFn(torch.autograd.Function):
                 res, ctx.bws = ctx.bws, None      # a reserved slot serves one backward
                 pz = _arena_valid(res) and nb <= res[0].numel()
                 ws = res[0] if pz else _ws(nb, dev)
+                ARENA_STATS['granted' if pz else 'private'] += 1
                 if pipe is not None:
                     N.call('asr_lstm_set_dy_flags', N.ptr(pipe[0]), pipe[1], pipe[2])
                 if split is None and wsplit and mode == '3':

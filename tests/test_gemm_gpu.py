@@ -163,6 +163,221 @@ def test_linear_staging_one_launch_bitwise(M, K, Nout, cuda_dev, monkeypatch):
         ops.set_compute_dtype('fp32')
 
 
+# ---------------------------------------------------------------------------
+# Staging of operands the one-launch conversion declines: leaves that are views
+# at an odd float offset into a larger tensor (4, 8, 12 B off a 16-B boundary).
+# ---------------------------------------------------------------------------
+_NAMES = ('y', 'dx', 'dW', 'db')
+
+
+def _leaf_at(a, off, dev):
+    """A leaf holding `a` whose storage starts `off` floats past a 16-B boundary."""
+    n = a.size
+    buf = torch.zeros(n + 4, dtype=torch.float32, device=dev)
+    buf[off:off + n] = torch.from_numpy(a).reshape(-1).to(dev)
+    t = buf[off:off + n].view(*a.shape).detach().requires_grad_(True)
+    assert t.data_ptr() % 16 == 4 * off and t.is_contiguous()
+    return t
+
+
+def _poison_allocator(dev, sizes):
+    """Leave NaN bits in the caching allocator's free blocks of the staged
+    operands' sizes, so a staged copy that is never written cannot be right
+    by accident (a fresh block may be zero)."""
+    for n in sizes:
+        blocks = [torch.full((n,), float('nan'), dtype=torch.bfloat16, device=dev)
+                  for _ in range(4)]
+        del blocks
+
+
+def _linear_run(ops, dev, x, w, b, dy, xoff, woff, drop=None):
+    M, K = x.shape
+    Nout = w.shape[0]
+    Kp, Np = (K + 7) // 8 * 8, (Nout + 7) // 8 * 8
+    xd, wd = _leaf_at(x, xoff, dev), _leaf_at(w, woff, dev)
+    bd = torch.from_numpy(b).to(dev).requires_grad_(True)
+    dyd = torch.from_numpy(dy).to(dev)
+    _poison_allocator(dev, (Np * Kp, M * Kp, M * Np))
+    y = ops.linear(xd, wd, bd, drop)
+    y.backward(dyd)
+    torch.cuda.synchronize()
+    return [t.detach().cpu() for t in (y, xd.grad, wd.grad, bd.grad)]
+
+
+def _linear_case(M, K, Nout):
+    rng = np.random.RandomState(M + K + Nout)
+    x = rng.randn(M, K).astype(np.float32)
+    w = (rng.randn(Nout, K) * 0.05).astype(np.float32)
+    b = rng.randn(Nout).astype(np.float32)
+    dy = rng.randn(M, Nout).astype(np.float32)
+    return x, w, b, dy
+
+
+_LINEAR_REFS = {}
+
+
+def _linear_ref(M, K, Nout):
+    """float64 y, dx, dW of the bf16-rounded operands, db of the f32 dY
+    (LinearFn sums the bias gradient from the f32 dY)."""
+    if (M, K, Nout) not in _LINEAR_REFS:
+        x, w, b, dy = _linear_case(M, K, Nout)
+
+        def r(a):
+            return torch.from_numpy(a).to(torch.bfloat16).double().numpy()
+        xr, wr, dyr = r(x), r(w), r(dy)
+        _LINEAR_REFS[(M, K, Nout)] = (xr @ wr.T + b, dyr @ wr, dyr.T @ xr,
+                                      dy.astype(np.float64).sum(0))
+    return _LINEAR_REFS[(M, K, Nout)]
+
+
+# the smallest shapes that take the staged path: ragged (Nout % 8 != 0, 2 M N K
+# = 3.4e7 >= _STAGE_FLOPS_RAGGED) and dense (with _STAGE_FLOPS lowered to 1e6)
+@pytest.mark.parametrize('multi', ['1', '0'])
+@pytest.mark.parametrize('M,K,Nout', [(1024, 128, 129), (256, 64, 64)])
+@pytest.mark.parametrize('which', ['weight', 'input', 'both'])
+def test_linear_staging_misaligned_operands(which, M, K, Nout, multi, cuda_dev, monkeypatch):
+    """A staged linear layer whose weight and / or input is not 16-B aligned:
+    asr_convert_rows_bf16_multi declines such a job, and the layer must then
+    convert both operands one by one (the scalar conversion for the misaligned
+    one).  The staged bf16 copies are the aligned run's, so y, dx, dW, db equal
+    it bit for bit; the aligned run vs float64 of the bf16-rounded operands
+    within 1e-3 of the reference's max magnitude (test_linear_bf16_staged_padded's
+    bound).  The allocator's free blocks hold NaN before every forward."""
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    ops = _ops()
+    ops.set_compute_dtype('bf16')
+    try:
+        monkeypatch.setattr(native_ops, '_STAGE_FLOPS', 1e6)
+        monkeypatch.setenv('ASR_LINEAR_MULTI', multi)
+        assert ops._linear_stages(M, K, Nout)
+        x, w, b, dy = _linear_case(M, K, Nout)
+        base = _linear_run(ops, cuda_dev, x, w, b, dy, 0, 0)
+        for name, got, ref in zip(_NAMES, base, _linear_ref(M, K, Nout)):
+            err = np.abs(got.double().numpy() - ref).max() / (np.abs(ref).max() + 1e-9)
+            assert err < 1e-3, (name, err)
+        for off in (1, 2, 3):
+            xoff = off if which in ('input', 'both') else 0
+            woff = off if which in ('weight', 'both') else 0
+            got = _linear_run(ops, cuda_dev, x, w, b, dy, xoff, woff)
+            for name, g, a in zip(_NAMES, got, base):
+                assert torch.equal(g, a), (name, off, int((g != a).sum()),
+                                           bool(torch.isnan(g).any()))
+    finally:
+        ops.set_compute_dtype('fp32')
+
+
+def test_linear_staging_misaligned_input_fused_dropout(cuda_dev, monkeypatch):
+    """drop=(p, seed) with K % 8 == 0 folds the dropout into the bf16 staging
+    of x (asr_convert_rows_bf16_dropout) and into the dX epilogue.  The mask is
+    keyed on element offsets from the source pointer, so a misaligned x gives
+    the aligned run's y, dx, dW, db bit for bit."""
+    ops = _ops()
+    ops.set_compute_dtype('bf16')
+    try:
+        M, K, Nout = 1024, 128, 129
+        assert ops._linear_stages(M, K, Nout) and K % 8 == 0
+        x, w, b, dy = _linear_case(M, K, Nout)
+        drop = (0.25, 20231)
+        base = _linear_run(ops, cuda_dev, x, w, b, dy, 0, 0, drop=drop)
+        plain = _linear_run(ops, cuda_dev, x, w, b, dy, 0, 0)
+        assert not torch.equal(base[0], plain[0])            # the mask is applied
+        zeros = float((base[1] == 0).float().mean())         # dx carries it too
+        assert 0.2 < zeros < 0.3, zeros
+        for off in (1, 2, 3):
+            got = _linear_run(ops, cuda_dev, x, w, b, dy, off, 0, drop=drop)
+            for name, g, a in zip(_NAMES, got, base):
+                assert torch.equal(g, a), (name, off, int((g != a).sum()))
+    finally:
+        ops.set_compute_dtype('fp32')
+
+
+def _sentinel(n, dev):
+    return torch.full((n,), 0x7fc1, dtype=torch.int16, device=dev)
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+def test_convert_multi_declines_without_writing(cuda_dev):
+    """Every condition under which asr_convert_rows_bf16_multi declines: it
+    returns False and launches nothing -- neither the offending job's
+    destination nor a qualifying job's beside it is written."""
+    ops = _ops()
+    dev = cuda_dev
+    rows, cols = 16, 64
+    src = torch.randn(rows * (cols + 1) + 4, device=dev)
+    good = src[:rows * cols]
+
+    def job(s, rmap, r, c, dst, dst_off=0):
+        return (s, rmap, r, c, dst.data_ptr() + dst_off)
+    cases = {
+        'misaligned source': lambda d: job(src[1:1 + rows * cols], ops.rowmap(cols), rows, cols, d),
+        'misaligned destination (2 B)': lambda d: job(good, ops.rowmap(cols), rows, cols, d, 2),
+        'misaligned destination (8 B)': lambda d: job(good, ops.rowmap(cols), rows, cols, d, 8),
+        'cols % 8 != 0': lambda d: job(good, ops.rowmap(12), rows, 12, d),
+        'rows == 0': lambda d: job(good, ops.rowmap(cols), 0, cols, d),
+        'stride_t % 4 != 0': lambda d: job(src, ops.rowmap(cols + 1), rows, cols, d),
+        'stride_b % 4 != 0': lambda d: job(src, ops.rowmap(cols, stride_b=cols * 4 + 2, rows_per_b=4),
+                                           rows, cols, d),
+    }
+    for name, bad in cases.items():
+        for first in (False, True):       # the offending job before / after a qualifying one
+            d0, d1 = _sentinel(rows * cols + 8, dev), _sentinel(rows * cols + 8, dev)
+            jobs = [bad(d1), job(good, ops.rowmap(cols), rows, cols, d0)]
+            assert ops._convert_multi(jobs if first else jobs[::-1], dev) is False, name
+            torch.cuda.synchronize()
+            assert bool((d0 == 0x7fc1).all()) and bool((d1 == 0x7fc1).all()), name
+    dsts = [_sentinel(rows * cols, dev) for _ in range(5)]
+    jobs = [job(good, ops.rowmap(cols), rows, cols, d) for d in dsts]
+    assert ops._convert_multi(jobs, dev) is False, 'more than 4 jobs'
+    torch.cuda.synchronize()
+    assert all(bool((d == 0x7fc1).all()) for d in dsts)
+    assert ops._convert_multi(jobs[:4], dev) is True          # the same jobs, four of them
+    torch.cuda.synchronize()
+    for d in dsts[:4]:
+        assert torch.equal(d, _bits(good.to(torch.bfloat16)))
+    assert bool((dsts[4] == 0x7fc1).all())
+
+
+@pytest.mark.parametrize('njobs', [1, 3, 4])
+def test_convert_multi_qualifying_jobs_bitwise(njobs, cuda_dev):
+    """1, 3 and 4 qualifying jobs in one launch -- 1 x 8, 257 x 64 and 33 x 1032
+    (more chunks than one block covers), and the zero-pad-rows job
+    _linear_forward builds behind a 257-row weight: every destination equals
+    src.to(bfloat16) bit for bit, pad rows zero, nothing written past its end."""
+    ops = _ops()
+    dev = cuda_dev
+    shapes = [(1, 8), (257, 64), (33, 1032)]
+    g = torch.Generator().manual_seed(njobs)
+    srcs = [(torch.randn(r, c, generator=g) * 3).to(dev) for r, c in shapes]
+    pad = 264 - 257
+    tail = 64                                  # sentinel elements kept behind each destination
+    for group in ([[0], [1], [2]] if njobs == 1 else [[0, 1, 2]]):
+        dsts, jobs = {}, []
+        for k in group:
+            r, c = shapes[k]
+            rr = r + pad if (k == 1 and njobs == 4) else r
+            dsts[k] = _sentinel(rr * c + tail, dev)
+            jobs.append((srcs[k], ops.rowmap(c), r, c, dsts[k].data_ptr()))
+        if njobs == 4:
+            r, c = shapes[1]
+            jobs.append((srcs[1], ops.rowmap(0, t_limit=1, rows_per_b=pad, t_add=1), pad, c,
+                         dsts[1].data_ptr() + r * c * 2))
+        assert len(jobs) == (njobs if njobs > 1 else 1)
+        assert ops._convert_multi(jobs, dev) is True
+        torch.cuda.synchronize()
+        for k in group:
+            r, c = shapes[k]
+            d = dsts[k]
+            assert torch.equal(d[:r * c], _bits(srcs[k].to(torch.bfloat16)).reshape(-1)), shapes[k]
+            end = r * c
+            if k == 1 and njobs == 4:
+                assert bool((d[end:end + pad * c] == 0).all())
+                end += pad * c
+            assert bool((d[end:] == 0x7fc1).all()), shapes[k]
+
+
 @pytest.mark.parametrize('M,N,K', [(529, 389, 3000), (256, 256, 64), (300, 260, 200),
                                     (1024, 512, 8000)])
 def test_kmajor_256_tiles_exact(M, N, K, cuda_dev, monkeypatch):

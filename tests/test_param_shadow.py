@@ -42,6 +42,38 @@ def test_shadow_trusted_only_after_the_step_and_until_a_write(ops, monkeypatch):
     assert ops._shadow_rows(w, params) is None
 
 
+@pytest.mark.parametrize('how', ['fp32', 'env'])
+def test_shadow_void_after_a_step_that_did_not_write_it(how, ops, monkeypatch):
+    """The fused optimizer step writes the parameters from native code and
+    bumps no version.  A step taken while param_shadow() is None (fp32 mode,
+    ASR_PARAM_SHADOW=0) reports itself through param_shadow_skipped: the
+    shadow an earlier step wrote is void until a later step writes it again."""
+    monkeypatch.delenv('ASR_PARAM_SHADOW', raising=False)
+    flat, params, w = _model()
+    other, oparams, ow = _model()
+    for f, ps in ((flat, params), (other, oparams)):
+        ops.param_shadow_written(ops.param_shadow(f), f, ps)
+    sh = ops.param_shadow(flat)
+    assert ops._shadow_rows(w, params) is not None
+    # the step without a shadow: what FlatOptimizer.step does with sh None
+    if how == 'fp32':
+        ops.set_compute_dtype('fp32')
+    else:
+        monkeypatch.setenv('ASR_PARAM_SHADOW', '0')
+    assert ops.param_shadow(flat) is None
+    ops.param_shadow_skipped(flat)
+    ops.set_compute_dtype('bf16')
+    monkeypatch.delenv('ASR_PARAM_SHADOW', raising=False)
+    assert ops._shadow_rows(w, params) is None
+    assert ops._shadow_rows(ow, oparams) is not None      # another model's shadow stands
+    assert ops.param_shadow(flat) is sh                   # the buffer is kept ...
+    assert ops._shadow_rows(w, params) is None            # ... but not trusted yet
+    ops.param_shadow_written(sh, flat, params)            # a step that wrote it
+    assert ops._shadow_rows(w, params) is not None
+    ops.param_shadow_skipped(torch.zeros(4))              # a flat buffer without a shadow: no-op
+    assert ops._shadow_rows(w, params) is not None
+
+
 def test_shadow_off_in_fp32_and_by_switch(ops, monkeypatch):
     flat, params, w = _model()
     monkeypatch.setenv('ASR_PARAM_SHADOW', '0')

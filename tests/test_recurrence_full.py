@@ -99,9 +99,13 @@ def _gpu(prec, lens, x, w_ih, w_hh, b_ih, b_hh, dy, dev):
             w.grad = torch.zeros_like(w)
         xd = x.to(dev).requires_grad_(True)
         lens_d = torch.from_numpy(lens).to(dev)
+        ops.recurrence_status(dev)               # clear what an earlier test left
         y = ops.blstm_layer(xd, lens_d, T, *ws)
         y.backward(dy.to(dev))
         torch.cuda.synchronize()
+        # a persistent recurrence that gave up a bounded wait left invalid outputs
+        st = ops.recurrence_status(dev)
+        assert int(st.max()) == 0, st.tolist()
         return [t.double().cpu() for t in (y.detach(), xd.grad, ws[0].grad, ws[1].grad,
                                            ws[2].grad, ws[3].grad)]
     finally:
