@@ -8,6 +8,8 @@ Weight gradients are accumulated by the kernels directly into ``param.grad``
 (views into the model's flat gradient buffer, see models/pytorch_v3/base.py);
 the Functions therefore return ``None`` for weights.
 """
+import collections
+import contextlib
 import ctypes
 import os
 import weakref
@@ -116,21 +118,26 @@ def _arena_valid(res):
     return res is not None and res[1] == _arena['gen']
 
 
-class _prezeroed:
+def _rec_workspace(nbytes, dev, res):
+    """(workspace, prezeroed) of one recurrence launch: the arena slot `res`
+    (_arena_take's, now or reserved by the forward) if it is of the current
+    generation and long enough, else a private buffer the launch clears."""
+    pz = _arena_valid(res) and nbytes <= res[0].numel()
+    ARENA_STATS['granted' if pz else 'private'] += 1
+    return (res[0] if pz else _ws(nbytes, dev)), pz
+
+
+@contextlib.contextmanager
+def _prezeroed(on):
     """Tell the recurrence launch inside the block that its workspace is
     already zero (asr_lstm_ws_prezeroed), and clear the setting after it."""
-
-    def __init__(self, on):
-        self.on = bool(on)
-
-    def __enter__(self):
-        if self.on:
-            N.call('asr_lstm_ws_prezeroed', 1)
-
-    def __exit__(self, *exc):
-        if self.on:
+    if on:
+        N.call('asr_lstm_ws_prezeroed', 1)
+    try:
+        yield
+    finally:
+        if on:
             N.call('asr_lstm_ws_prezeroed', 0)
-        return False
 
 
 # Gradient-ready notifications for the data-parallel bucketed all-reduce
@@ -1360,6 +1367,31 @@ def att_decoder(enc, enc_a, lens, pre_emb, h0, emb_dim, sharpen, sigmoid, w_ih, 
 # ---------------------------------------------------------------------------
 # One bidirectional LSTM layer (nn.LSTM bidirectional + pack/pad, rnn.py)
 # ---------------------------------------------------------------------------
+class _InputMap(collections.namedtuple('_InputMap', 'perm t_mul t_add T T_src Dsrc Din')):
+    """A recurrent layer's input addressing: row (b, t), t < T, of the layer
+    input is the Din values at x_src[perm[b] if perm else b, t*t_mul + t_add]
+    of x_src [B, T_src, Dsrc] (Din = 2 * Dsrc: that frame and the next one,
+    'concat' subsampling read in place)."""
+    __slots__ = ()
+
+    def rows(self, ta=0, tb=None):
+        """The row map reading X / scattering dX: rows t in [ta, tb) (default: all T)."""
+        tb = self.T if tb is None else tb
+        return rowmap(self.Dsrc, stride_b=self.T_src * self.Dsrc, rows_per_b=tb - ta,
+                      t_mul=self.t_mul, t_add=self.t_add + ta * self.t_mul,
+                      t_limit=self.T_src, perm=self.perm)
+
+    @property
+    def is_identity(self):
+        return (self.perm is None and self.t_mul == 1 and self.t_add == 0
+                and self.T == self.T_src and self.Din == self.Dsrc)
+
+    def alloc_dx(self, B, dev):
+        """dX [B, T_src, Dsrc]; zero where a non-identity map may leave frames unwritten."""
+        fill = torch.empty if self.is_identity else torch.zeros
+        return fill(B, self.T_src, self.Dsrc, dtype=torch.float32, device=dev)
+
+
 class BLSTMLayerFn(torch.autograd.Function):
     """x_src [B, T_src, Din] f32; the layer input row (b, t) is
     x_src[perm[b] if perm else b, t*t_mul + t_add].  Parameters are passed as
@@ -1394,15 +1426,12 @@ class BLSTMLayerFn(torch.autograd.Function):
         H = w_hh.shape[1]
         dev = x_src.device
         cd = compute_dtype()
-        a_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                       t_limit=T_src, perm=perm)
-        fuse_x = False
-        gx = None       # f32 gate pre-activations -> activations [B, T, 8H], or
-        Dp = Din        # packed fp16 activations [B, T, 2, H, 4] (fused bf16 path)
+        in_map = _InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Din)
+        a_map = in_map.rows()
+        Dp = Din
         if twin is not None:
             x_op = twin.view(B * T, Din)
             w_op = _wih_bf16(w_ih, graph_params, H, Din)           # [8H, Din]
-            y_bf = torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
         elif cd == BF16:
             if Din % 8 and not fused_drop:
                 # an input width that is not a multiple of 8 (TIMIT's 123) is
@@ -1418,75 +1447,38 @@ class BLSTMLayerFn(torch.autograd.Function):
                 x_op = convert_rows_bf16(x_src, a_map, B * T, Din,    # [B*T, Din]
                                          drop=drop if fused_drop else None)
                 w_op = _wih_bf16(w_ih, graph_params, H, Din)           # [8H, Din]
-            y_bf = torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
         else:
-            x_op, w_op, y_bf = x_src, w_ih, None
+            x_op, w_op = x_src, w_ih
+        y_bf = torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev) if cd == BF16 else None
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         cst = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 0)
         zb = N.query('asr_lstm_ws_zero_bytes', B, H)
-        slot = _arena_take(nb, dev, zb)     # zeroed by rec_arena_begin
-        ws = slot[0] if slot is not None else _ws(nb, dev)
-        pz = slot is not None
-        ARENA_STATS['granted' if pz else 'private'] += 1
+        ws, pz = _rec_workspace(nb, dev, _arena_take(nb, dev, zb))   # zeroed by rec_arena_begin
         # the backward's slot, reserved now so the arena's one fill covers it
         ctx.bws = (_arena_take(N.query('asr_lstm_workspace_bytes', B, H, cd, 2), dev, zb)
                    if pz else None)
         whh_r = w_hh.data_ptr() + 4 * H * H * 4
-        y_f32, out_drop = out_spec
-        handoff = None     # (bf16 tensor the next layer stages from, its dropout)
+        # gx: f32 gate pre-activations -> activations [B, T, 8H], or packed fp16
+        # activations [B, T, 2, H, 4] (fused bf16 path).  handoff: (bf16 tensor
+        # the next layer stages from, its dropout)
+        fuse_x, gx, handoff = False, None, None
         if cd == BF16 and _fuse_xproj_on():
-            # the input projection inside the persistent recurrence (no gx GEMM);
-            # ASR_ERR_UNSUPPORTED when this shape / configuration does not take it.
-            # The gate activations are kept as packed fp16 (8 B per cell instead
-            # of 16; ASR_XG_ACT_H=0 keeps the f32 layout)
-            args = (N.ptr(x_op), Dp, N.ptr(w_op), N.ptr(b_ih), N.ptr(b_hh), N.ptr(w_hh),
-                    ctypes.c_void_p(whh_r), N.ptr(lens), B, T, H)
-            if _act_h_on() and not y_f32:
-                # the next BLSTM layer stages its input from bf16 written here (its
-                # dropout applied): no f32 y, no conversion pass
-                gx = torch.empty(B, T, 2, H, 4, dtype=torch.float16, device=dev)
-                fn = 'asr_lstm_forward_xh_drop'
-                y_d = (torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
-                       if out_drop is not None else None)
-                p, seed = out_drop if out_drop is not None else (0.0, 0)
-                with _prezeroed(pz):
-                    rc = N.query(fn, *args, N.ptr(gx), None, N.ptr(cst), N.ptr(y_bf),
-                                 N.ptr(y_d) if y_d is not None else None, ctypes.c_float(p),
-                                 ctypes.c_ulonglong(seed), N.ptr(ws), nb, N.stream_handle(dev))
-                if rc == 0:
-                    handoff = (y_d if y_d is not None else y_bf, out_drop)
-            else:
-                if _act_h_on():
-                    gx = torch.empty(B, T, 2, H, 4, dtype=torch.float16, device=dev)
-                    fn = 'asr_lstm_forward_xh'
-                else:
-                    gx = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
-                    fn = 'asr_lstm_forward_x'
-                with _prezeroed(pz):
-                    rc = N.query(fn, *args, N.ptr(gx), N.ptr(y), N.ptr(cst), N.ptr(y_bf),
-                                 N.ptr(ws), nb, N.stream_handle(dev))
-            if rc not in (0, N.ASR_ERR_UNSUPPORTED):
-                raise N.NativeError('%s failed (rc=%d): %s' % (
-                    fn, rc, N.lib().asr_last_error().decode(errors='replace')))
-            fuse_x = rc == 0
+            fuse_x, gx, handoff = _lstm_forward_fused(
+                x_op, Dp, w_op, b_ih, b_hh, w_hh, lens, B, T, H, out_spec, y, cst, y_bf, ws, nb, pz)
         if not fuse_x:
             gx = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
-            if cd == BF16:
-                run_gemm([gemm_problem(operand(x_op, 0, rowmap(Dp)), operand(w_op, 0, rowmap(Dp)),
-                                       gx, rowmap(8 * H), B * T, 8 * H, Dp, bias=b_ih,
-                                       bias2=b_hh)], dev)
-            else:
-                run_gemm([gemm_problem(operand(x_src, 0, a_map), operand(w_ih, 0, rowmap(Din)), gx,
-                                       rowmap(8 * H), B * T, 8 * H, Din, bias=b_ih, bias2=b_hh)],
-                         dev)
+            # (fp32: x_op is x_src read through the input map, w_op is w_ih, Dp = Din)
+            x_map = rowmap(Dp) if cd == BF16 else a_map
+            run_gemm([gemm_problem(operand(x_op, 0, x_map), operand(w_op, 0, rowmap(Dp)), gx,
+                                   rowmap(8 * H), B * T, 8 * H, Dp, bias=b_ih, bias2=b_hh)], dev)
             with _prezeroed(pz):
                 N.call('asr_lstm_forward', N.ptr(gx), N.ptr(w_hh), ctypes.c_void_p(whh_r), F32,
                        N.ptr(lens), B, T, H, cd, N.ptr(y), N.ptr(cst), N.ptr(y_bf), N.ptr(ws),
                        nb, N.stream_handle(dev))
         ctx.save_for_backward(x_op, w_op, lens, w_hh, b_ih, b_hh, gx, cst,
                               y_bf if y_bf is not None else y)
-        ctx.meta = (T, perm, t_mul, t_add, gbufs, cd, (B, T_src, Dsrc, Din, Dp), w_ih)
+        ctx.meta = (in_map, gbufs, cd, B, Dp, w_ih)
         ctx.bh = (B, H)     # the recurrence shape a gated side stream waits on
         ctx.drop = drop
         ctx.next_rec = bool(next_rec)
@@ -1501,7 +1493,7 @@ class BLSTMLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x_op, w_op, lens, w_hh, b_ih, b_hh, act, cst, y_op = ctx.saved_tensors
-        T, perm, t_mul, t_add, gbufs, cd, (B, T_src, Dsrc, Din, Dp), w_ih = ctx.meta
+        in_map, gbufs, cd, B, Dp, w_ih = ctx.meta
         H = w_hh.shape[1]
         dev = act.device
         dy = dy.contiguous()
@@ -1514,290 +1506,368 @@ class BLSTMLayerFn(torch.autograd.Function):
             pipe = None
         if gbufs is None:
             gbufs = tuple(grad_buffer(p) for p in (w_ih, w_hh, b_ih, b_hh))
-        fused_db = os.environ.get('ASR_BIAS_FUSED', '1') != '0'
-        whh_r = w_hh.data_ptr() + 4 * H * H * 4
-        dg_bf = (torch.empty(B, T, 8 * H, dtype=torch.bfloat16, device=dev) if cd == BF16
-                 else None)
-        done = False
         # data parallel: every collective issued so far completes before this
         # persistent recurrence starts (a kernel co-resident with the
         # recurrence perturbs it)
         notify_grad_event('pre_recurrence')
-        # the recurrence's LDS pin: co-resident GEMM work-groups only in the
-        # opt-in mode 2 (84 KB); otherwise 140 KB excludes every GEMM kernel.
-        # Units per work-group: 32 where that frees the CUs for mode 3.
-        mode, xu = _overlap_plan(dev, B, H)
-        N.call('asr_lstm_set_bwd_pin_kb', 84 if mode == '2' else 0)
-        N.call('asr_lstm_set_bwd_units', xu)
-        split = None
-        band_seq = None   # (t0, t1): the same row bands, computed after the recurrence
-        dx_split = None
-        last_main = not ctx.next_rec and os.environ.get('ASR_WGRAD_LAST_MAIN', '1') != '0'
-        wsplit = last_main and _wgrad_split_ok(ctx, T, mode)
-        wprog = None      # (counter, target, event) of the bottom layer's banded dW overlap
-        if (act.dtype == torch.float16 and pipe is None and _dx_split_ok(ctx, B, T, dev, mode)
-                and not _dx_pipeline_ok(ctx, B, T, Din, dev)):
-            N.call('asr_lstm_set_bwd_units', xu)     # (arrivals follow the units setting)
-            # row bands by when their gate gradients are final: [T/4, 3T/4) at
-            # processing step 3T/4 - 1, with two chunks also [T/8, T/4) and
-            # [3T/4, 7T/8) at 7T/8 - 1; the rest after the recurrence.  Beside the
-            # recurrence in mode 3; in the other modes the same bands after it, so
-            # every mode computes dX by the same products
-            two = _dx_split_chunks() == 2 and T >= 128
-            arrivals = N.query('asr_lstm_bwd_progress_arrivals', B, H) if mode == '3' else 0
-            # dX before the recurrence: its zero fill (non-identity maps) precedes
-            # the side stream's writes
-            ident = perm is None and t_mul == 1 and t_add == 0 and T == T_src and Din == Dsrc
-            dx_split = (torch.empty if ident else torch.zeros)(B, T_src, Dsrc,
-                                                               dtype=torch.float32, device=dev)
-            if arrivals > 0:
-                split = (T // 4, _progress_counter(dev), int(arrivals), T // 8 if two else None)
-            else:
-                band_seq = (T // 4, T // 8 if two else None)
-        try:
-            if act.dtype == torch.float16:
-                # packed fp16 activations of asr_lstm_forward_xh: the tagged-granule
-                # backward reads them directly; otherwise they are unpacked to f32
-                nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2)
-                res, ctx.bws = ctx.bws, None      # a reserved slot serves one backward
-                pz = _arena_valid(res) and nb <= res[0].numel()
-                ws = res[0] if pz else _ws(nb, dev)
-                ARENA_STATS['granted' if pz else 'private'] += 1
-                if pipe is not None:
-                    N.call('asr_lstm_set_dy_flags', N.ptr(pipe[0]), pipe[1], pipe[2])
-                if split is None and wsplit and mode == '3':
-                    arrivals = N.query('asr_lstm_bwd_progress_arrivals', B, H)
-                    if arrivals > 0:
-                        wprog = (_progress_counter(dev), int(arrivals))
-                        N.call('asr_lstm_set_bwd_progress', N.ptr(wprog[0][0]), T - 1 - T // 4)
-                        wprog_pre = torch.cuda.Event()
-                        wprog_pre.record(torch.cuda.current_stream(dev))
-                if split is not None:
-                    if split[3] is not None:
-                        N.call('asr_lstm_set_bwd_progress2', N.ptr(split[1][0]), T - 1 - split[0],
-                               T - 1 - split[3])
-                    else:
-                        N.call('asr_lstm_set_bwd_progress', N.ptr(split[1][0]), T - 1 - split[0])
-                    # everything the side stream's share of dX reads that is not
-                    # written by the recurrence is enqueued by now (dx's fill included)
-                    split_pre = torch.cuda.Event()
-                    split_pre.record(torch.cuda.current_stream(dev))
-                try:
-                    with _prezeroed(pz):
-                        rc = N.query('asr_lstm_backward_dgbf_h', N.ptr(dy), N.ptr(w_hh),
-                                     ctypes.c_void_p(whh_r), F32, N.ptr(lens), B, T, H, cd,
-                                     N.ptr(act), N.ptr(cst), N.ptr(dg_bf), N.ptr(gbufs[2]),
-                                     N.ptr(gbufs[3]), N.ptr(ws), nb, N.stream_handle(dev))
-                finally:
-                    if split is not None or wprog is not None:
-                        N.call('asr_lstm_set_bwd_progress', None, 0)
-                    if pipe is not None:
-                        N.call('asr_lstm_set_dy_flags', None, 16, 0)
-                        # (after the launch: later compute-stream work sees all of dy)
-                        torch.cuda.current_stream(dev).wait_event(pipe[3])
-                        pipe = None
-                if rc not in (0, N.ASR_ERR_UNSUPPORTED):
-                    raise N.NativeError('asr_lstm_backward_dgbf_h failed (rc=%d): %s' % (
-                        rc, N.lib().asr_last_error().decode(errors='replace')))
-                done = rc == 0
-                if done and wprog is not None:
-                    wprog[0][1] += wprog[1]
-                    wprog = (wprog[0][0], wprog[0][1], wprog_pre)
-                else:
-                    wprog = None
-                if done and split is not None:
-                    first = split[1][1] + split[2]   # the arrivals this launch adds per step
-                    split[1][1] += split[2] * (2 if split[3] is not None else 1)
-                    split = split + ((first, split[1][1]), split_pre)
-                elif split is not None:            # no report: the same bands after it
-                    band_seq = (split[0], split[3])
-                    split = None
-                if not done:
-                    a32 = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
-                    N.call('asr_lstm_unpack_act_h', N.ptr(act), B, T, H, N.ptr(a32),
-                           N.stream_handle(dev))
-                    act = a32
-            nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2 if fused_db else 1)
-            ws = _ws(nb, dev)
-            # the saved activations become the gate gradients dG in place; the bias
-            # gradients (sum of dG over b, t) are accumulated by the same call
-            if done:
-                pass
-            elif fused_db:
-                # bf16 mode: only the bf16 dG feeds the GEMMs, so the f32 dG is not stored
-                fn = 'asr_lstm_backward_dgbf' if dg_bf is not None else 'asr_lstm_backward_db'
-                N.call(fn, N.ptr(dy), N.ptr(w_hh), ctypes.c_void_p(whh_r), F32,
-                       N.ptr(lens), B, T, H, cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf),
-                       N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb, N.stream_handle(dev))
-            else:   # A/B: separate column-sum pass over dG
-                N.call('asr_lstm_backward', N.ptr(dy), N.ptr(w_hh), ctypes.c_void_p(whh_r), F32,
-                       N.ptr(lens), B, T, H, cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf), N.ptr(ws), nb,
-                       N.stream_handle(dev))
-                colsum_accumulate(act.view(B * T, 8 * H), gbufs[2], gbufs[3])
-        finally:
-            N.call('asr_lstm_set_bwd_units', 0)   # direct API callers: the default again
+        plan = _blstm_bwd_plan(ctx, act, pipe, in_map, B, H, dev)
+        dg_op, act, gate = _blstm_bwd_recurrence(ctx, plan, dy, pipe, w_hh, lens, act, cst, gbufs,
+                                                 cd, B, in_map.T, H, dev)
+        # the one progress report serves the banded dX, else the banded dW
+        dx_gate, w_gate = (gate, None) if plan.bands is not None else (None, gate)
         # weight gradients of the layer above, if they went to a side stream: join
         # them here (they run beside the recurrence just enqueued) so the
         # gradient-ready bucket sees them on the compute stream
         _join_side_wgrads(dev)
         notify_grad_event('recurrence')
-        dg_op = dg_bf if dg_bf is not None else act
-        split_done = None
-        if split is not None:
-            t0, (ctr, _), _, t1, targets, pre = split
-            side = _wgrad_side_stream(dev, B, H)[0]
-            side.wait_event(pre)         # not the recurrence itself: the gate waits on its progress
-            if os.environ.get('ASR_DX_SPLIT_SYNC') == '1':   # diagnostics: after the whole recurrence
-                rec_done = torch.cuda.Event()
-                rec_done.record(torch.cuda.current_stream(dev))
-                side.wait_event(rec_done)
-            rows = lambda ta, tb: _dx_rows_problem(dg_op, w_op, dx_split, ctx, B, T, T_src, H,  # noqa: E731
-                                                   Din, Dp, Dsrc, perm, t_mul, t_add, ta, tb)
-            with torch.cuda.stream(side):
-                N.call('asr_gemm_set_nosplit', 1)     # per output element: one launch's sum
-                try:
-                    N.call('asr_lstm_progress_gate', N.ptr(ctr), targets[0], N.stream_handle(dev))
-                    run_gemm([rows(t0, T - t0)], dev)
-                    if t1 is not None:
-                        N.call('asr_lstm_progress_gate', N.ptr(ctr), targets[1],
-                               N.stream_handle(dev))
-                        run_gemm([rows(t1, t0), rows(T - t0, T - t1)], dev)
-                finally:
-                    N.call('asr_gemm_set_nosplit', 0)
-                split_done = torch.cuda.Event()
-                split_done.record(side)
-            for tt in (dg_op, w_op, dx_split, ctr) + ((perm,) if perm is not None else ()):
-                tt.record_stream(side)
-        # X as the dW_ih operand: the bf16 copy is already gathered (identity map)
-        if cd == BF16:
-            x_map = rowmap(Dp)
-        else:
-            x_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                           t_limit=T_src, perm=perm)
         # the bottom layer's weight gradients have no recurrence left to run
         # beside: they take the main stream and the full-size GEMM kernels (on
         # the co-resident small tiles the 4x320 layer-0 dW_ih ran at 29 TF/s)
-        side_ent = None if last_main else _wgrad_side_stream(dev, B, H)
-        # pipelined input gradient (_dx_pipelined): enqueued first, and the
-        # side-stream weight gradients start after it, so the CUs the next
-        # recurrence leaves free serve dX -- which that recurrence waits for --
-        # before the weight gradients, which only the optimizer needs
-        BT = B * T
-        dx = dx_done = None
-        pipelined = ctx.needs_input_grad[0] and _dx_pipeline_ok(ctx, B, T, Din, dev)
-        if pipelined:
-            dx = torch.empty(B, T_src, Dsrc, dtype=torch.float32, device=dev)
-            dx_done = _dx_pipelined(dx, dg_op, w_op, B, T, H, Din, Dp, ctx.drop, dev)
-        if side_ent is None and wsplit:
-            # time bands: the middle one first (beside the recurrence's last
-            # quarter when it reported progress), then the outer two
-            tq = T // 4
-            Dx = x_op.shape[-1]
-            if wprog is not None:
-                ctr, target, pre = wprog
-                side = _wgrad_side_stream(dev, B, H)[0]
-                side.wait_event(pre)
-                with torch.cuda.stream(side):
-                    N.call('asr_lstm_progress_gate', N.ptr(ctr), target, N.stream_handle(dev))
-                    _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, tq, T - tq)
-                    mid_done = torch.cuda.Event()
-                    mid_done.record(side)
-                for tt in (dg_op, x_op, y_op, ctr):
-                    tt.record_stream(side)
-                torch.cuda.current_stream(dev).wait_event(mid_done)
-            else:
-                _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, tq, T - tq)
-            _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, 0, tq)
-            _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, T - tq, T)
-            notify_grad_event('grads', gbufs)      # final on the compute stream
-        elif side_ent is None:
-            _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev)
-            notify_grad_event('grads', gbufs)      # final on the compute stream
-        else:
-            # weight gradients on a side stream, overlapping this layer's dX
-            # GEMM and the previous layer's backward recurrence; joined back
-            # into the main stream at the end of the backward pass
-            side, small, gated = side_ent
-            main = torch.cuda.current_stream(dev)
-            side.wait_stream(main)
-            if small:
-                N.call('asr_gemm_set_small_tiles', 1)
-            try:
-                with torch.cuda.stream(side):
-                    if dx_done is not None:
-                        side.wait_event(dx_done)
-                    elif gated and ctx.next_rec:
-                        # hold the GEMMs back until the previous layer's backward
-                        # recurrence (launched next on the main stream) is resident
-                        N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
-                    # (tools/cores_locate.py replaces _blstm_wgrad with stand-in
-                    # side-stream workloads; nothing diagnostic runs here)
-                    _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev)
-            finally:
-                if small:
-                    N.call('asr_gemm_set_small_tiles', 0)
-            for t in (dg_op, act, x_op, y_op) + ((perm,) if perm is not None else ()):
-                t.record_stream(side)
-            if not _side_pending:
-                torch.autograd.Variable._execution_engine.queue_callback(
-                    lambda: _join_side_wgrads(dev, notify=False))
-            _side_pending.append((side, gbufs, main))
-        if split_done is not None:
-            # the outer rows t in [0, T/4) and [3T/4, T) (two chunks: [0, T/8) and
-            # [7T/8, T)) on the compute stream, then the side stream's rows joined
-            t0 = split[3] if split[3] is not None else split[0]
-            N.call('asr_gemm_set_nosplit', 1)
-            try:
-                run_gemm([_dx_rows_problem(dg_op, w_op, dx_split, ctx, B, T, T_src, H, Din, Dp,
-                                           Dsrc, perm, t_mul, t_add, 0, t0),
-                          _dx_rows_problem(dg_op, w_op, dx_split, ctx, B, T, T_src, H, Din, Dp,
-                                           Dsrc, perm, t_mul, t_add, T - t0, T)], dev)
-            finally:
-                N.call('asr_gemm_set_nosplit', 0)
-            torch.cuda.current_stream(dev).wait_event(split_done)
-            dx = dx_split
-        elif band_seq is not None:
-            # the split's row bands in its order, on the compute stream
-            t0, t1 = band_seq
-            rows = lambda ta, tb: _dx_rows_problem(dg_op, w_op, dx_split, ctx, B, T, T_src, H,  # noqa: E731
-                                                   Din, Dp, Dsrc, perm, t_mul, t_add, ta, tb)
-            N.call('asr_gemm_set_nosplit', 1)
-            try:
-                run_gemm([rows(T // 4, T - T // 4)], dev)
-                if t1 is not None:
-                    run_gemm([rows(t1, t0), rows(T - t0, T - t1)], dev)
-                te = t1 if t1 is not None else t0
-                run_gemm([rows(0, te), rows(T - te, T)], dev)
-            finally:
-                N.call('asr_gemm_set_nosplit', 0)
-            dx = dx_split
-        elif ctx.needs_input_grad[0] and not pipelined:
-            # dX [BT, Din] = dG [BT, 8H] W_ih [8H, Din], scattered back through the input map
-            if perm is None and t_mul == 1 and t_add == 0 and T == T_src and Din == Dsrc:
-                dx = torch.empty(B, T_src, Dsrc, dtype=torch.float32, device=dev)
-            else:
-                dx = torch.zeros(B, T_src, Dsrc, dtype=torch.float32, device=dev)
-            c_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                           t_limit=T_src, perm=perm)
-            # dropout's backward (the forward mask over x_src's flat offsets) is
-            # applied by the GEMM's epilogue as it writes dX
-            p = gemm_problem(operand(dg_op, 0, rowmap(8 * H)), operand(w_op, 1, rowmap(Dp)), dx,
-                             c_map, BT, Din, 8 * H, drop=ctx.drop)
-            run_gemm([p], dev)
+        side_ent = None if plan.last_main else _wgrad_side_stream(dev, B, H)
+        dx, pipe_done, bands_done = _blstm_bwd_dx_ahead(ctx, plan, dx_gate, dg_op, w_op, in_map,
+                                                        B, H, Dp, dev)
+        _blstm_bwd_wgrads(ctx, plan, w_gate, side_ent, pipe_done, dg_op, act, x_op, y_op, in_map,
+                          Dp, cd, gbufs, B, H, dev)
+        dx = _blstm_bwd_dx_rest(ctx, plan, dx, bands_done, dg_op, w_op, in_map, B, H, Dp, dev)
         return (dx,) + (None,) * (14 + ctx.n_graph)
 
 
-def _dx_rows_problem(dg_op, w_op, dx, ctx, B, T, T_src, H, Din, Dp, Dsrc, perm, t_mul, t_add,
-                     ta, tb):
+def _dx_bands(T, two):
+    """The split input gradient's row bands as ordered groups of (ta, tb) ranges
+    of t, one run_gemm launch per group: by when their gate gradients are
+    final, [T/4, 3T/4) at processing step 3T/4 - 1, with two chunks also
+    [T/8, T/4) and [3T/4, 7T/8) at 7T/8 - 1; the rest, after the recurrence,
+    last.  Every mode runs the groups in this order: dX by the same products."""
+    t0 = te = T // 4
+    groups = [[(t0, T - t0)]]
+    if two:
+        te = T // 8
+        groups.append([(te, t0), (T - t0, T - te)])
+    return groups + [[(0, te), (T - te, T)]]
+
+
+class _ProgressReport:
+    """The progress report of one packed-activation backward launch: at each of
+    `steps` (one or two processing steps) the recurrence adds `arrivals` to the
+    device counter, and a side stream gates (asr_lstm_progress_gate) on the
+    counter reaching targets[k] before it reads what is final after steps[k].
+    The counter only grows; the host's running total of it (_progress_counter)
+    advances in commit() alone."""
+
+    def __init__(self, dev, arrivals, steps):
+        self.entry = _progress_counter(dev)
+        self.counter, self.arrivals, self.steps = self.entry[0], int(arrivals), tuple(steps)
+        self.targets = self.pre = None
+
+    @classmethod
+    def request(cls, dev, B, H, steps):
+        """For the next backward of [B, *, H]; None where it would not report."""
+        arrivals = N.query('asr_lstm_bwd_progress_arrivals', B, H)
+        return cls(dev, arrivals, steps) if arrivals > 0 else None
+
+    def arm(self, dev):
+        """pre: all a gated consumer reads but the recurrence's writes is enqueued by now."""
+        N.call('asr_lstm_set_bwd_progress' + ('2' if len(self.steps) == 2 else ''),
+               N.ptr(self.counter), *self.steps)
+        self.pre = torch.cuda.Event()
+        self.pre.record(torch.cuda.current_stream(dev))
+
+    @staticmethod
+    def disarm():
+        N.call('asr_lstm_set_bwd_progress', None, 0)
+
+    def commit(self, done):
+        """The gate targets of a launch that ran (done): each step's arrivals on
+        top of the running total, which they advance.  Else None."""
+        if done:
+            self.targets = tuple(self.entry[1] + self.arrivals * k
+                                 for k in range(1, len(self.steps) + 1))
+            self.entry[1] = self.targets[-1]
+        return self.targets
+
+
+_BwdPlan = collections.namedtuple('_BwdPlan', 'mode last_main wgrad_banded bands dx report')
+
+
+def _blstm_bwd_plan(ctx, act, pipe, in_map, B, H, dev):
+    """What a BLSTM layer's backward runs, and its recurrence's launch settings
+    (made here: the progress arrivals follow the units setting).  bands
+    (_dx_bands) come with dx and, where the recurrence reports progress, the
+    report gating them; None: dX pipelined or whole, decided after it."""
+    T = in_map.T
+    # the recurrence's LDS pin: co-resident GEMM work-groups only in the
+    # opt-in mode 2 (84 KB); otherwise 140 KB excludes every GEMM kernel.
+    # Units per work-group: 32 where that frees the CUs for mode 3.
+    mode, xu = _overlap_plan(dev, B, H)
+    N.call('asr_lstm_set_bwd_pin_kb', 84 if mode == '2' else 0)
+    N.call('asr_lstm_set_bwd_units', xu)
+    last_main = not ctx.next_rec and _wgrad_last_main_on()
+    wgrad_banded = last_main and _wgrad_split_ok(ctx, T, mode)
+    bands = dx = report = None
+    if (act.dtype == torch.float16 and pipe is None and _dx_split_ok(ctx, B, T, dev, mode)
+            and not _dx_pipeline_ok(ctx, B, T, in_map.Din, dev)):
+        # beside the recurrence in mode 3; in the other modes the same bands after it
+        bands = _dx_bands(T, _dx_split_chunks() == 2 and T >= 128)
+        if mode == '3':
+            report = _ProgressReport.request(dev, B, H, [T - 1 - g[0][0] for g in bands[:-1]])
+        # dX before the recurrence: its zero fill (non-identity maps) precedes
+        # the side stream's writes
+        dx = in_map.alloc_dx(B, dev)
+    return _BwdPlan(mode, last_main, wgrad_banded, bands, dx, report)
+
+
+def _blstm_bwd_recurrence(ctx, plan, dy, pipe, w_hh, lens, act, cst, gbufs, cd, B, T, H, dev):
+    """(dg_op, act, gate): the saved activations become the gate gradients dG
+    in place (act: f32, unpacked if the packed-activation launch did not run);
+    dg_op is dG as the GEMMs read it (bf16 mode: the bf16 copy); gate is the
+    committed progress report or None."""
+    fused_db = _bias_fused_on()
+    whh_r = ctypes.c_void_p(w_hh.data_ptr() + 4 * H * H * 4)
+    dg_bf = torch.empty(B, T, 8 * H, dtype=torch.bfloat16, device=dev) if cd == BF16 else None
+    done, gate = False, None
+    try:
+        if act.dtype == torch.float16:
+            # packed fp16 activations of asr_lstm_forward_xh: the tagged-granule
+            # backward reads them directly; otherwise they are unpacked to f32
+            done, gate = _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf,
+                                           gbufs, cd, B, T, H, dev)
+            if not done:
+                a32 = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
+                N.call('asr_lstm_unpack_act_h', N.ptr(act), B, T, H, N.ptr(a32),
+                       N.stream_handle(dev))
+                act = a32
+        nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2 if fused_db else 1)
+        ws = _ws(nb, dev)
+        # the bias gradients (sum of dG over b, t) are accumulated by the same call
+        if not done and fused_db:
+            # bf16 mode: only the bf16 dG feeds the GEMMs, so the f32 dG is not stored
+            fn = 'asr_lstm_backward_dgbf' if dg_bf is not None else 'asr_lstm_backward_db'
+            N.call(fn, N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H, cd, N.ptr(act),
+                   N.ptr(cst), N.ptr(dg_bf), N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb,
+                   N.stream_handle(dev))
+        elif not done:   # A/B: separate column-sum pass over dG
+            N.call('asr_lstm_backward', N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H,
+                   cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf), N.ptr(ws), nb, N.stream_handle(dev))
+            colsum_accumulate(act.view(B * T, 8 * H), gbufs[2], gbufs[3])
+    finally:
+        N.call('asr_lstm_set_bwd_units', 0)   # direct API callers: the default again
+    return (dg_bf if dg_bf is not None else act), act, gate
+
+
+def _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf, gbufs, cd, B, T, H,
+                      dev):
+    """The packed-activation tagged-granule backward, armed with the plan's
+    progress report (with none, banded weight gradients in mode 3 ask for one
+    at their middle band's step) and the dy flags of a pipelined layer above.
+    (ran, committed report or None); not ran: ASR_ERR_UNSUPPORTED, no report --
+    its consumers run the same bands after the recurrence."""
+    nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2)
+    res, ctx.bws = ctx.bws, None      # a reserved slot serves one backward
+    ws, pz = _rec_workspace(nb, dev, res)
+    if pipe is not None:
+        N.call('asr_lstm_set_dy_flags', N.ptr(pipe[0]), pipe[1], pipe[2])
+    report = plan.report
+    if report is None and plan.wgrad_banded and plan.mode == '3':
+        report = _ProgressReport.request(dev, B, H, [T - 1 - T // 4])
+    if report is not None:
+        report.arm(dev)
+    try:
+        with _prezeroed(pz):
+            rc = N.query('asr_lstm_backward_dgbf_h', N.ptr(dy), N.ptr(w_hh), whh_r, F32,
+                         N.ptr(lens), B, T, H, cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf),
+                         N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb, N.stream_handle(dev))
+    finally:
+        if report is not None:
+            report.disarm()
+        if pipe is not None:
+            N.call('asr_lstm_set_dy_flags', None, 16, 0)
+            # (after the launch: later compute-stream work sees all of dy)
+            torch.cuda.current_stream(dev).wait_event(pipe[3])
+    if rc not in (0, N.ASR_ERR_UNSUPPORTED):
+        raise N.NativeError('asr_lstm_backward_dgbf_h failed (rc=%d): %s' % (
+            rc, N.lib().asr_last_error().decode(errors='replace')))
+    committed = report is not None and report.commit(rc == 0) is not None
+    return rc == 0, report if committed else None
+
+
+def _blstm_bwd_wgrads(ctx, plan, gate, side_ent, dx_done, dg_op, act, x_op, y_op, in_map, Dp, cd,
+                      gbufs, B, H, dev):
+    """The weight gradients where the plan and side_ent (_wgrad_side_stream's
+    entry or None) place them: the compute stream, whole or in time bands, or
+    a side stream (behind the pipelined dX's event dx_done, if any)."""
+    T = in_map.T
+    # X as the dW_ih operand: the bf16 copy is already gathered (identity map)
+    x_map = rowmap(Dp) if cd == BF16 else in_map.rows()
+    if side_ent is None:
+        if plan.wgrad_banded:
+            _wgrad_main_banded(gate, dg_op, x_op, y_op, T, gbufs, B, H, dev)
+        else:
+            _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev)
+        notify_grad_event('grads', gbufs)      # final on the compute stream
+        return
+    # weight gradients on a side stream, overlapping this layer's dX
+    # GEMM and the previous layer's backward recurrence; joined back
+    # into the main stream at the end of the backward pass
+    side, small, gated = side_ent
+    main = torch.cuda.current_stream(dev)
+    side.wait_stream(main)
+    if small:
+        N.call('asr_gemm_set_small_tiles', 1)
+    try:
+        with torch.cuda.stream(side):
+            if dx_done is not None:
+                # the pipelined input gradient first, so the CUs the next
+                # recurrence leaves free serve dX -- which that recurrence waits
+                # for -- before the weight gradients, which only the optimizer needs
+                side.wait_event(dx_done)
+            elif gated and ctx.next_rec:
+                # hold the GEMMs back until the previous layer's backward
+                # recurrence (launched next on the main stream) is resident
+                N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
+            # (tools/cores_locate.py replaces _blstm_wgrad with stand-in
+            # side-stream workloads; nothing diagnostic runs here)
+            _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev)
+    finally:
+        if small:
+            N.call('asr_gemm_set_small_tiles', 0)
+    for t in (dg_op, act, x_op, y_op) + ((in_map.perm,) if in_map.perm is not None else ()):
+        t.record_stream(side)
+    if not _side_pending:
+        torch.autograd.Variable._execution_engine.queue_callback(
+            lambda: _join_side_wgrads(dev, notify=False))
+    _side_pending.append((side, gbufs, main))
+
+
+def _wgrad_main_banded(gate, dg_op, x_op, y_op, T, gbufs, B, H, dev):
+    """Time bands: the middle one first (with gate, the recurrence's progress
+    report: beside its last quarter, on the side stream), then the outer two."""
+    tq = T // 4
+    Dx = x_op.shape[-1]
+    if gate is not None:
+        side = _wgrad_side_stream(dev, B, H)[0]
+        side.wait_event(gate.pre)
+        with torch.cuda.stream(side):
+            N.call('asr_lstm_progress_gate', N.ptr(gate.counter), gate.targets[0],
+                   N.stream_handle(dev))
+            _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, tq, T - tq)
+            mid_done = torch.cuda.Event()
+            mid_done.record(side)
+        for tt in (dg_op, x_op, y_op, gate.counter):
+            tt.record_stream(side)
+        torch.cuda.current_stream(dev).wait_event(mid_done)
+    else:
+        _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, tq, T - tq)
+    _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, 0, tq)
+    _blstm_wgrad_rows(dg_op, x_op, Dx, y_op, T, gbufs, dev, T - tq, T)
+
+
+def _blstm_bwd_dx_ahead(ctx, plan, gate, dg_op, w_op, in_map, B, H, Dp, dev):
+    """The input gradient enqueued before the weight gradients: (dx, the
+    pipelined form's event, the gated bands' event), None where not that form."""
+    if plan.bands is not None and gate is not None:
+        # all band groups but the last on the weight-gradient side stream
+        side = _wgrad_side_stream(dev, B, H)[0]
+        side.wait_event(gate.pre)     # not the recurrence itself: the gate waits on its progress
+        if _dx_split_sync_on():       # diagnostics: after the whole recurrence
+            rec_done = torch.cuda.Event()
+            rec_done.record(torch.cuda.current_stream(dev))
+            side.wait_event(rec_done)
+        with torch.cuda.stream(side):
+            _dx_run_bands(plan.bands[:-1], dg_op, w_op, plan.dx, in_map, H, Dp, ctx.drop, dev, gate)
+            done = torch.cuda.Event()
+            done.record(side)
+        perm = in_map.perm
+        for tt in (dg_op, w_op, plan.dx, gate.counter) + ((perm,) if perm is not None else ()):
+            tt.record_stream(side)
+        return plan.dx, None, done
+    # pipelined input gradient (_dx_pipelined): enqueued first, and the
+    # side-stream weight gradients start after it
+    if (plan.bands is None and ctx.needs_input_grad[0]
+            and _dx_pipeline_ok(ctx, B, in_map.T, in_map.Din, dev)):
+        dx = in_map.alloc_dx(B, dev)     # (a handed-over input: the identity map)
+        return dx, _dx_pipelined(dx, dg_op, w_op, B, in_map.T, H, in_map.Din, Dp, ctx.drop,
+                                 dev), None
+    return plan.dx, None, None
+
+
+def _dx_run_bands(groups, dg_op, w_op, dx, in_map, H, Dp, drop, dev, gate=None):
+    """One launch per band group, in order, on the current stream; gate: each
+    first waits for the recurrence's progress to reach its target."""
+    N.call('asr_gemm_set_nosplit', 1)     # per output element: one launch's sum
+    try:
+        for k, group in enumerate(groups):
+            if gate is not None:
+                N.call('asr_lstm_progress_gate', N.ptr(gate.counter), gate.targets[k],
+                       N.stream_handle(dev))
+            run_gemm([_dx_rows_problem(dg_op, w_op, dx, in_map, H, Dp, drop, ta, tb)
+                      for ta, tb in group], dev)
+    finally:
+        N.call('asr_gemm_set_nosplit', 0)
+
+
+def _blstm_bwd_dx_rest(ctx, plan, dx, bands_done, dg_op, w_op, in_map, B, H, Dp, dev):
+    """The input gradient enqueued after the weight gradients; returns dX."""
+    if plan.bands is not None and bands_done is not None:
+        # the outer rows on the compute stream, then the side stream's rows joined
+        _dx_run_bands(plan.bands[-1:], dg_op, w_op, dx, in_map, H, Dp, ctx.drop, dev)
+        torch.cuda.current_stream(dev).wait_event(bands_done)
+    elif plan.bands is not None:
+        # the split's row bands in its order, on the compute stream
+        _dx_run_bands(plan.bands, dg_op, w_op, dx, in_map, H, Dp, ctx.drop, dev)
+    elif dx is None and ctx.needs_input_grad[0]:
+        # dX [BT, Din] = dG [BT, 8H] W_ih [8H, Din], scattered back through the
+        # input map; dropout's backward (the forward mask over x_src's flat
+        # offsets) is applied by the GEMM's epilogue as it writes dX
+        dx = in_map.alloc_dx(B, dev)
+        run_gemm([gemm_problem(operand(dg_op, 0, rowmap(8 * H)), operand(w_op, 1, rowmap(Dp)), dx,
+                               in_map.rows(), B * in_map.T, in_map.Din, 8 * H, drop=ctx.drop)], dev)
+    return dx
+
+
+def _dx_rows_problem(dg_op, w_op, dx, in_map, H, Dp, drop, ta, tb):
     """dX rows (b, t) for t in [ta, tb) of every utterance: dG [B, T, 8H] W_ih
     [8H, Din], written through the layer's input map (the dropout mask by dX's
     element offsets, as the whole-product form)."""
     n = tb - ta
-    a_map = rowmap(8 * H, stride_b=T * 8 * H, rows_per_b=n, t_add=ta)
-    c_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=n, t_mul=t_mul, t_add=t_add + ta * t_mul,
-                   t_limit=T_src, perm=perm)
-    return gemm_problem(operand(dg_op, 0, a_map), operand(w_op, 1, rowmap(Dp)), dx, c_map,
-                        B * n, Din, 8 * H, drop=ctx.drop)
+    a_map = rowmap(8 * H, stride_b=in_map.T * 8 * H, rows_per_b=n, t_add=ta)
+    return gemm_problem(operand(dg_op, 0, a_map), operand(w_op, 1, rowmap(Dp)), dx,
+                        in_map.rows(ta, tb), dg_op.shape[0] * n, in_map.Din, 8 * H, drop=drop)
+
+
+def _lstm_forward_fused(x_op, Dp, w_op, b_ih, b_hh, w_hh, lens, B, T, H, out_spec, y, cst, y_bf,
+                        ws, nb, pz):
+    """The input projection inside the persistent forward recurrence (no gx
+    GEMM): (ran, gx, handoff); not ran (ASR_ERR_UNSUPPORTED): this shape /
+    configuration does not take it.  gx: the gate activations as packed fp16
+    (8 B per cell instead of 16; ASR_XG_ACT_H=0 keeps the f32 layout).  With
+    out_spec's y_f32 off, the next BLSTM layer stages its input from bf16
+    written here, its dropout applied (handoff): no f32 y, no conversion pass."""
+    dev = x_op.device
+    y_f32, out_drop = out_spec
+    packed = _act_h_on()
+    gx = (torch.empty(B, T, 2, H, 4, dtype=torch.float16, device=dev) if packed
+          else torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev))
+    args = (N.ptr(x_op), Dp, N.ptr(w_op), N.ptr(b_ih), N.ptr(b_hh), N.ptr(w_hh),
+            ctypes.c_void_p(w_hh.data_ptr() + 4 * H * H * 4), N.ptr(lens), B, T, H, N.ptr(gx))
+    handoff = None
+    with _prezeroed(pz):
+        if packed and not y_f32:
+            fn = 'asr_lstm_forward_xh_drop'
+            y_d = (torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
+                   if out_drop is not None else None)
+            p, seed = out_drop if out_drop is not None else (0.0, 0)
+            rc = N.query(fn, *args, None, N.ptr(cst), N.ptr(y_bf), N.ptr(y_d), ctypes.c_float(p),
+                         ctypes.c_ulonglong(seed), N.ptr(ws), nb, N.stream_handle(dev))
+            if rc == 0:
+                handoff = (y_d if y_d is not None else y_bf, out_drop)
+        else:
+            fn = 'asr_lstm_forward_xh' if packed else 'asr_lstm_forward_x'
+            rc = N.query(fn, *args, N.ptr(y), N.ptr(cst), N.ptr(y_bf), N.ptr(ws), nb,
+                         N.stream_handle(dev))
+    if rc not in (0, N.ASR_ERR_UNSUPPORTED):
+        raise N.NativeError('%s failed (rc=%d): %s' % (
+            fn, rc, N.lib().asr_last_error().decode(errors='replace')))
+    return rc == 0, gx, handoff
 
 
 class BGRULayerFn(torch.autograd.Function):
@@ -1818,25 +1888,24 @@ class BGRULayerFn(torch.autograd.Function):
         assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
         H = w_hh.shape[1]
         dev = x_src.device
-        a_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                       t_limit=T_src, perm=perm)
+        in_map = _InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Din)
         gx = torch.empty(B, T, 6 * H, dtype=torch.float32, device=dev)
-        run_gemm([gemm_problem(operand(x_src, 0, a_map), operand(w_ih, 0, rowmap(Din)), gx,
+        run_gemm([gemm_problem(operand(x_src, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
                                rowmap(6 * H), B * T, 6 * H, Din, bias=b_ih)], dev)
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         ghn = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
         N.call('asr_gru_forward', N.ptr(gx), N.ptr(w_hh), N.ptr(b_hh), N.ptr(lens), B, T, H,
                N.ptr(y), N.ptr(ghn), N.stream_handle(dev))
         ctx.save_for_backward(x_src, w_ih, w_hh, b_ih, b_hh, lens, gx, ghn, y)
-        ctx.meta = (T, perm, t_mul, t_add, gbufs, Din)
+        ctx.meta = (in_map, gbufs)
         ctx.n_graph = len(graph_params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x_src, w_ih, w_hh, b_ih, b_hh, lens, act, ghn, y = ctx.saved_tensors
-        T, perm, t_mul, t_add, gbufs, Din = ctx.meta
-        B, T_src, Dsrc = x_src.shape
+        in_map, gbufs = ctx.meta
+        B, T, Din = x_src.shape[0], in_map.T, in_map.Din
         H = w_hh.shape[1]
         dev = act.device
         dy = dy.contiguous()
@@ -1850,11 +1919,9 @@ class BGRULayerFn(torch.autograd.Function):
         N.call('asr_gru_backward', N.ptr(dy), N.ptr(w_hh), N.ptr(lens), B, T, H, N.ptr(act),
                N.ptr(ghn), N.ptr(y), N.ptr(dgh), N.ptr(ws), nb, N.stream_handle(dev))
         BT = B * T
-        x_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                       t_limit=T_src, perm=perm)
         # dW_ih [6H, Din] += dgx^T x (both directions in one problem)
-        run_gemm([gemm_problem(operand(act, 1, rowmap(6 * H)), operand(x_src, 1, x_map), g_ih,
-                               rowmap(Din), 6 * H, Din, BT, beta=1.0)], dev)
+        run_gemm([gemm_problem(operand(act, 1, rowmap(6 * H)), operand(x_src, 1, in_map.rows()),
+                               g_ih, rowmap(Din), 6 * H, Din, BT, beta=1.0)], dev)
         # dW_hh[dir] += dgh_dir^T h_prev_dir ; h_prev = y[b, t-1, :H] (fwd), y[b, t+1, H:] (rev)
         hp_f = rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=-1, t_limit=T)
         hp_r = rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=1, t_limit=T)
@@ -1871,14 +1938,9 @@ class BGRULayerFn(torch.autograd.Function):
         notify_grad_event('grads', gbufs)
         dx = None
         if ctx.needs_input_grad[0]:
-            if perm is None and t_mul == 1 and t_add == 0 and T == T_src and Din == Dsrc:
-                dx = torch.empty(B, T_src, Dsrc, dtype=torch.float32, device=dev)
-            else:
-                dx = torch.zeros(B, T_src, Dsrc, dtype=torch.float32, device=dev)
-            c_map = rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
-                           t_limit=T_src, perm=perm)
+            dx = in_map.alloc_dx(B, dev)
             run_gemm([gemm_problem(operand(act, 0, rowmap(6 * H)), operand(w_ih, 1, rowmap(Din)),
-                                   dx, c_map, BT, Din, 6 * H)], dev)
+                                   dx, in_map.rows(), BT, Din, 6 * H)], dev)
         return (dx,) + (None,) * (11 + ctx.n_graph)
 
 
@@ -1900,6 +1962,21 @@ def _fuse_xproj_on():
     forward recurrence (asr_lstm_forward_x) first (ASR_FUSE_XPROJ=0 keeps the
     separate GEMM)."""
     return os.environ.get('ASR_FUSE_XPROJ', '1') != '0'
+
+
+def _bias_fused_on():
+    """The backward recurrence sums the bias gradients too (ASR_BIAS_FUSED=0: a separate pass)."""
+    return os.environ.get('ASR_BIAS_FUSED', '1') != '0'
+
+
+def _wgrad_last_main_on():
+    """The bottom layer's weight gradients on the compute stream (ASR_WGRAD_LAST_MAIN=0: A/B)."""
+    return os.environ.get('ASR_WGRAD_LAST_MAIN', '1') != '0'
+
+
+def _dx_split_sync_on():
+    """Diagnostics (ASR_DX_SPLIT_SYNC=1): the gated dX bands also wait for the whole recurrence."""
+    return os.environ.get('ASR_DX_SPLIT_SYNC') == '1'
 
 
 def convert_rows_bf16(src, rmap, nrows, ncols, drop=None):
@@ -1925,47 +2002,40 @@ def _blstm_wgrad(dg, dg_f32, x_op, x_map, y_op, T, gbufs, dev):
     """dW_ih, dW_hh of one BLSTM layer from its gate gradients (dg: bf16 copy
     in bf16 mode, else the f32 tensor).  db_ih / db_hh were accumulated by
     asr_lstm_backward_db."""
-    B = dg.shape[0]
     H = y_op.shape[2] // 2
-    BT = B * T
-    g_ih, g_hh, g_bih, g_bhh = gbufs
-    Din = g_ih.shape[-1]          # != x_op's width for 'concat' input rows
-    # dW_ih [8H, Din] += dG^T x   (both directions in one problem)
-    run_gemm([gemm_problem(operand(dg, 1, rowmap(8 * H)), operand(x_op, 1, x_map), g_ih,
-                           rowmap(Din), 8 * H, Din, BT, beta=1.0)], dev)
-    # dW_hh[dir] += dG_dir^T h_prev_dir ; h_prev = y[b, t-1, :H] (fwd), y[b, t+1, H:] (rev)
-    hp_f = rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=-1, t_limit=T)
-    hp_r = rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=1, t_limit=T)
-    run_gemm([
-        gemm_problem(operand(dg, 1, rowmap(8 * H)), operand(y_op, 1, hp_f), g_hh, rowmap(H),
-                     4 * H, H, BT, beta=1.0),
-        gemm_problem(operand(dg, 1, rowmap(8 * H), offset=4 * H),
-                     operand(y_op, 1, hp_r, offset=H), g_hh, rowmap(H), 4 * H, H, BT, beta=1.0,
-                     c_offset=4 * H * H),
-    ], dev)
+    hp = lambda add: rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=add,  # noqa: E731
+                            t_limit=T)
+    _wgrad_gemms(dg, x_op, y_op, gbufs, dev, dg.shape[0] * T, rowmap(8 * H), x_map, hp(-1), hp(1))
 
 
 def _blstm_wgrad_rows(dg, x_op, Dx, y_op, T, gbufs, dev, ta, tb):
     """_blstm_wgrad over the rows (b, t), t in [ta, tb), of every utterance
     (bf16 mode: dg and x_op dense [B*T, width] rows): the weight gradients
     accumulated (beta = 1) from that band of time steps only."""
-    B = dg.shape[0]
     H = y_op.shape[2] // 2
     n = tb - ta
     if n <= 0:
         return
-    g_ih, g_hh, g_bih, g_bhh = gbufs
-    Din = g_ih.shape[-1]
     band = lambda ld, add=0: rowmap(ld, stride_b=T * ld, rows_per_b=n, t_add=ta + add,  # noqa: E731
                                     t_limit=T)
-    run_gemm([gemm_problem(operand(dg, 1, band(8 * H)), operand(x_op, 1, band(Dx)), g_ih,
-                           rowmap(Din), 8 * H, Din, B * n, beta=1.0)], dev)
+    _wgrad_gemms(dg, x_op, y_op, gbufs, dev, dg.shape[0] * n, band(8 * H), band(Dx),
+                 band(2 * H, -1), band(2 * H, 1))
+
+
+def _wgrad_gemms(dg, x_op, y_op, gbufs, dev, rows, dg_map, x_map, hp_f, hp_r):
+    """The two weight-gradient launches over `rows` rows addressed by the maps."""
+    H = y_op.shape[2] // 2
+    g_ih, g_hh = gbufs[:2]
+    Din = g_ih.shape[-1]          # != x_op's width for 'concat' input rows
+    # dW_ih [8H, Din] += dG^T x   (both directions in one problem)
+    run_gemm([gemm_problem(operand(dg, 1, dg_map), operand(x_op, 1, x_map), g_ih, rowmap(Din),
+                           8 * H, Din, rows, beta=1.0)], dev)
+    # dW_hh[dir] += dG_dir^T h_prev_dir ; h_prev = y[b, t-1, :H] (fwd), y[b, t+1, H:] (rev)
     run_gemm([
-        gemm_problem(operand(dg, 1, band(8 * H)), operand(y_op, 1, band(2 * H, -1)), g_hh,
-                     rowmap(H), 4 * H, H, B * n, beta=1.0),
-        gemm_problem(operand(dg, 1, band(8 * H), offset=4 * H),
-                     operand(y_op, 1, band(2 * H, 1), offset=H), g_hh, rowmap(H), 4 * H, H,
-                     B * n, beta=1.0, c_offset=4 * H * H),
+        gemm_problem(operand(dg, 1, dg_map), operand(y_op, 1, hp_f), g_hh, rowmap(H), 4 * H, H,
+                     rows, beta=1.0),
+        gemm_problem(operand(dg, 1, dg_map, offset=4 * H), operand(y_op, 1, hp_r, offset=H), g_hh,
+                     rowmap(H), 4 * H, H, rows, beta=1.0, c_offset=4 * H * H),
     ], dev)
 
 
@@ -2009,16 +2079,6 @@ def discard_side_wgrads():
     for side, _gbufs, main in _side_pending:
         main.wait_stream(side)
     del _side_pending[:]
-
-
-_warned = set()
-
-
-def _warn_once(msg):
-    if msg not in _warned:
-        _warned.add(msg)
-        import warnings
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
 
 def _num_cus(dev):

@@ -294,7 +294,6 @@ def test_split_row_problems_equal_whole_product(B, T, T_src, H, Dsrc, t_mul, t_a
     A / C row maps, K unsplit) against the whole dX = dG W_ih product on the
     same bf16 operands: bitwise, with and without the batch permutation and
     the pyramidal input map.  GEMMs only (no recurrence, no progress gate)."""
-    from types import SimpleNamespace
     from pytorch_end2end_speech_recognition_amd import native_ops as ops
     from pytorch_end2end_speech_recognition_amd import _native as N
     ops.set_compute_dtype('bf16')
@@ -302,7 +301,7 @@ def test_split_row_problems_equal_whole_product(B, T, T_src, H, Dsrc, t_mul, t_a
     dg = torch.randn(B, T, 8 * H, generator=g).to(torch.bfloat16).to(cuda_dev)
     w = (torch.randn(8 * H, Dsrc, generator=g) * 0.05).to(torch.bfloat16).to(cuda_dev)
     perm = (torch.randperm(B, generator=g).to(torch.int32).to(cuda_dev) if permute else None)
-    ctx = SimpleNamespace(drop=None)
+    in_map = ops._InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Dsrc)
     whole = torch.zeros(B, T_src, Dsrc, device=cuda_dev)
     c_map = ops.rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
                        t_limit=T_src, perm=perm)
@@ -314,8 +313,8 @@ def test_split_row_problems_equal_whole_product(B, T, T_src, H, Dsrc, t_mul, t_a
         parts = torch.zeros_like(whole)
         t0 = T // 4
         for ta, tb in ((t0, T - t0), (0, t0), (T - t0, T)):
-            ops.run_gemm([ops._dx_rows_problem(dg, w, parts, ctx, B, T, T_src, H, Dsrc, Dsrc, Dsrc,
-                                               perm, t_mul, t_add, ta, tb)], cuda_dev)
+            ops.run_gemm([ops._dx_rows_problem(dg, w, parts, in_map, H, Dsrc, None, ta, tb)],
+                         cuda_dev)
     finally:
         N.call('asr_gemm_set_nosplit', 0)
     torch.cuda.synchronize()
