@@ -656,6 +656,18 @@ __global__ void __launch_bounds__(64 * NSW + R * XUF) lstm_fwd_xg(
 // LDS hazards (producers write pre(s+1) into xpart[(s+1)&1] between Bp(s-1)
 // and B(s); cells read pre(s+1) between Bp(s) and B(s+1)): the buffer a
 // producer overwrites at iteration s was last read before B(s-1).
+//
+// Input rows (xs, three slots, step st in slot st % 3).  At iteration s a
+// producer wave runs produce(s+1) (reads slot (s+1) % 3), waits until sweeper
+// wave 0's poll for step s has succeeded (s_go == s, or s_dead), waits for its
+// own DMA of step s+2 (issued one iteration ago) and issues the DMA of step
+// s+3 into slot s % 3, all before B(s).  That slot was last read by
+// produce(s) at iteration s-1, before B(s-1), which this wave has passed.
+// Step s+2's rows are complete in every wave before B(s), so produce(s+2)
+// after Bp(s) reads whole rows.  The DMA leaves at poll success, the start of
+// the CU's quiet window (sweeper MFMAs, partials, barrier), and not after
+// B(s), where its 16 KB per CU (Din = 1024) queued in front of the cells'
+// partial-sum reads and the sweepers' next poll.
 // ---------------------------------------------------------------------------
 constexpr int XGX_DMAX = 1024;   // largest input width of the fused projection
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -693,11 +705,12 @@ __global__ void __launch_bounds__(64 * NSW + R * XU + 64 * NPW) lstm_fwd_xgx(
   // Din % 64 == 0, so a fragment read of 8 rows hits distinct banks)
   __shared__ __attribute__((aligned(16))) uint16_t xs[3][R * XGX_DMAX];
   __shared__ int s_dead;
+  __shared__ int s_go;    // last step whose poll sweeper wave 0 has seen succeed
   __shared__ int s_pl[4];
   int* abortw = hdr;
   const int WPG = H / XU;
   const int G = gridDim.x / WPG;
-  if (threadIdx.x == 0) s_dead = 0;
+  if (threadIdx.x == 0) s_dead = s_go = 0;
   xg_place(WPG, allow_local, hdr, s_pl);
   if (!s_pl[3]) return;
   const int grp = s_pl[0], mem = s_pl[1];
@@ -759,6 +772,7 @@ __global__ void __launch_bounds__(64 * NSW + R * XU + 64 * NPW) lstm_fwd_xgx(
               ok &= (int)((((v[i][0] ^ ebit) | (v[i][2] ^ ebit)) & 1u) == 0u);
           }
           if (__all(ok)) {
+            if (wave == 0 && lane == 0) *(volatile int*)&s_go = s;   // releases the row DMA
             XG_TR(s, 1, __builtin_amdgcn_s_memrealtime());
             XG_TR(s, 5, spins);
             XG_TR(s, 6, t_iss);
@@ -824,31 +838,43 @@ __global__ void __launch_bounds__(64 * NSW + R * XU + 64 * NPW) lstm_fwd_xgx(
     const __amdgpu_buffer_rsrc_t xr = xg_rsrc((void*)x, (unsigned)((long long)B * T * Din * 2));
     const int slot_elems = R * Din;
     constexpr int NI = (R * XGX_DMAX * 2 + NPW * 1024 - 1) / (NPW * 1024);  // DMAs per wave
-    // buffer -> LDS DMA of step st's R input rows into ring slot st % 3
-    auto stage_x = [&](int st) {
-      const int t = dir ? T - 1 - st : st;
-      uint16_t* slot = &xs[st % 3][0];
+    // Lane constants of this wave's DMAs: piece i fills 1 KB (512 elements from
+    // blk * 512) of a slot; its row, source chunk and validity do not depend on
+    // the step, so a step's source offset is vbase[i] + t * Din * 2.  A lane
+    // past the slot or past row B keeps an offset the add cannot bring back in
+    // range (the buffer is < 0x7fff0000 bytes): it reads zeros.
+    unsigned vbase[NI];
+    const int npc = __builtin_amdgcn_readfirstlane(
+        min(NI, max(0, (slot_elems + 511) / 512 - pw * NI)));   // pieces of this wave
 #pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int blk = pw * NI + i;
-        const int e = blk * 512 + lane * 8;        // element of the slot this lane fills
-        unsigned voff = 0x7ffffff0u;               // out of range: zeros
-        if (e < slot_elems) {
-          const int r = e / Din, c = (e - r * Din) >> 3;
-          const int cs = swz ? (c ^ (r & 7)) : c;  // source chunk of LDS chunk c
-          if (b0 + r < B) voff = (unsigned)((((long long)(b0 + r) * T + t) * Din + 8 * cs) * 2);
-        }
-        if (blk * 512 < slot_elems) {              // wave-uniform
-          const unsigned lds_addr = (unsigned)(uintptr_t)(lds_void_t*)(slot + blk * 512);
-          unsigned keep;
-          asm volatile(
-              "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-              "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-              : "=&s"(keep)
-              : "v"(voff), "s"(xr), "s"(lds_addr)
-              : "memory");
-        }
+    for (int i = 0; i < NI; ++i) {
+      const int e = (pw * NI + i) * 512 + lane * 8;
+      vbase[i] = 0x7ffffff0u;
+      if (e < slot_elems) {
+        const int r = e / Din, c = (e - r * Din) >> 3;
+        const int cs = swz ? (c ^ (r & 7)) : c;      // source chunk of LDS chunk c
+        if (b0 + r < B) vbase[i] = (unsigned)((((long long)(b0 + r) * T) * Din + 8 * cs) * 2);
       }
+    }
+    const unsigned xs0 = (unsigned)(uintptr_t)(lds_void_t*)(&xs[0][0]) + (unsigned)(pw * NI * 1024);
+    const unsigned row_bytes = (unsigned)Din * 2u;
+    // piece i of step st's rows -> ring slot st % 3 (buffer -> LDS DMA)
+    auto stage_piece = [&](int st, int i) {
+      const int t = dir ? T - 1 - st : st;
+      const unsigned voff = vbase[i] + (unsigned)t * row_bytes;
+      const unsigned lds_addr = xs0 + (unsigned)((st % 3) * (R * XGX_DMAX * 2) + i * 1024);
+      unsigned keep;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+          "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+          : "=&s"(keep)
+          : "v"(voff), "s"(xr), "s"(lds_addr)
+          : "memory");
+    };
+    auto stage_x = [&](int st) {
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+        if (i < npc) stage_piece(st, i);   // wave-uniform
     };
     auto produce = [&](int st) {
       const uint16_t* slot = &xs[st % 3][0];
@@ -883,16 +909,20 @@ __global__ void __launch_bounds__(64 * NSW + R * XU + 64 * NPW) lstm_fwd_xgx(
     __syncthreads();  // B_pre
     produce(0);
     __syncthreads();  // B_init
-    // Step s+1's gate inputs before B(s); after B(s) wait for this wave's DMA
-    // of step s+2 (issued one step ago) and issue step s+3's: the barrier Bp(s)
-    // then publishes every wave's rows of step s+2 for produce(s+2).
+    // Step s+1's gate inputs first; then, once sweeper wave 0's poll for step
+    // s has succeeded (or a sweeper gave up), wait for this wave's DMA of step
+    // s+2 (issued one step ago) and issue step s+3's; B(s) then publishes every
+    // wave's rows of step s+2 for produce(s+2).  (Hazards: above the kernel.)
     for (int s = 0; s < T; ++s) {
       if (s + 1 < T) produce(s + 1);
       if (pw == 0 && lane == 0) XG_TR_AT(s, 8, __builtin_amdgcn_s_memrealtime());
+      const bool more = s + 3 < T && npc > 0;
+      if (more)
+        while (*(volatile int*)&s_go < s && !*(volatile int*)&s_dead) __builtin_amdgcn_s_sleep(1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step s+2's rows, issued a step ago
+      if (more) stage_x(s + 3);
       __syncthreads();  // B(s)
       if (s_dead) return;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (s + 3 < T) stage_x(s + 3);
       __syncthreads();  // Bp(s)
     }
     return;

@@ -56,8 +56,10 @@ def report(name, tr, names):
         print('  wg%d ' % w + '  '.join(parts))
 
 
-def main():
-    B, T, H, Din = 32, 1000, 512, 1024
+def layer(Din):
+    """One forward + backward layer pass at input width Din, stamps reported."""
+    B, T, H = 32, 1000, 512
+    print('=== Din = %d' % Din)
     ops.set_compute_dtype('bf16')
     dev = torch.device('cuda:0')
     rng = np.random.RandomState(0)
@@ -83,6 +85,12 @@ def main():
     hop('backward', bwd, 4)
     report('forward (us): sweep = start->sweep ok, comb = sweep->barrier, cell = barrier->publish',
            fwd, [(0, 1, 'sweep'), (1, 4, 'mfma'), (4, 2, 'bar'), (2, 3, 'cell')])
+    # the successful poll's issue -> return, and B(s) -> past Bp(s) (the next step's start)
+    print('forward: poll issue -> return / B(s) -> Bp(s) (us)')
+    for w in range(4):
+        d = fwd[w, 8:]
+        print('  wg%d  poll %.2f  B->Bp %.2f' % (w, np.median(d[:, 1] - d[:, 6]) / 100.0,
+                                                np.median(d[1:, 0] - d[:-1, 2]) / 100.0))
     report('forward detail (us): prod = step start -> projection done; mm = sweep ok -> MFMA '
            'results; rd = barrier -> partial sums read; act = -> h; pub = -> published',
            fwd, [(0, 8, 'prod'), (1, 11, 'mm'), (11, 4, 'lds'), (2, 9, 'rd'), (9, 10, 'act'),
@@ -94,6 +102,12 @@ def main():
            'mp = -> published', bwd,
            [(0, 8, 'pre'), (8, 9, 'b1w'), (9, 10, 'cell'), (10, 3, 'b2w'), (3, 11, 'b2m'),
             (11, 4, 'mp')])
+
+
+def main():
+    # the production layer widths of ctc5x512 in one run: layers 1-4, then layer 0
+    for Din in ([int(a) for a in sys.argv[1:]] or [1024, 128]):
+        layer(Din)
 
 
 if __name__ == '__main__':
