@@ -422,8 +422,10 @@ int asr_optim_step(int kind, float* params, const float* grads, float* m, float*
  *   Replaces nn.Dropout on the encoder / decoder activations.
  * asr_embedding_*: nn.Embedding(padding_idx) lookup / gradient (linear.py:50-77;
  *   trans=1: weight stored [E][V], the one-hot @ W^T of Embedding_LS,
- *   linear.py:80-116).  idx int64 [n].  Backward is deterministic and skips
- *   padding_idx (pass -1 for none).
+ *   linear.py:80-116).  idx int64 [n]; an index outside [0, V) reads row
+ *   clamp(idx, 0, V-1), and both backward forms send its gradient to that
+ *   same row.  Backward is deterministic and skips padding_idx (pass -1 for
+ *   none).
  * asr_tanh_*: F.tanh of the encoder projection / attention bottleneck.
  */
 int asr_dropout(const float* x, float* y, long long n, float p, unsigned long long seed,
@@ -491,6 +493,8 @@ int asr_convert_rows_bf16_dropout(const float* src, asr_rowmap_t map, int nrows,
  *   np.argmax), collapse repeats, drop `blank`.  hyps int32 [B][T] (first
  *   hyp_lens[b] valid), hyp_lens int32 [B].  Bit-exact with the reference.
  * asr_row_argmax: out[r] = argmax_v x[r*V + v] (int64; first max on ties).
+ * In both, a NaN never wins and the result is always in [0, V): a row / frame
+ * of all NaN (or all -inf) gives 0.
  */
 int asr_ctc_best_path(const float* logits, long long stride_t, long long stride_b, int T, int B,
                       int V, const int32_t* lens, int blank, int32_t* hyps, int32_t* hyp_lens,
@@ -503,7 +507,9 @@ int asr_row_argmax(const float* x, int rows, int V, long long* out, void* stream
  *   loss = ce_scale * sum_{r: tgt[r]>=0} (lse_r - x[r,tgt[r]])
  *        + ls_scale * sum_{r in LS rows} -(1/V) sum_v (x[r,v] - lse_r)
  * LS rows: r = b*T + t with t < lens[b] if lens != NULL, else tgt[r] >= 0.
- * targets int64 (nullable), -1 = ignore.  workspace keeps the row lse for
+ * targets int64 (nullable), -1 = ignore (any negative value is); a target
+ * >= V is NOT an error: it is clamped to V - 1, in forward and backward alike
+ * (tests/test_aux_kernels_gpu.py pins this).  workspace keeps the row lse for
  * backward (asr_xent_workspace_bytes(R)).  Backward writes
  * dlogits = scale * (*grad_scale) * dloss/dlogits.
  */

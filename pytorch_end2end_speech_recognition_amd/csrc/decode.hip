@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(64) best_path_kernel(const float* __restrict__
     for (int f = 0; f < nf; ++f) {
       const float* x = logits + (long long)(t0 + f) * st + (long long)b * sb;
       float bv = -__builtin_huge_valf();
-      int bi = 0x7fffffff;
+      int bi = 0;   // (-inf, 0): a NaN never wins, so an all-NaN / all -inf frame gives 0
       for (int v = lane; v < V; v += 64) argmax_pair(bv, bi, x[v], v);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
@@ -65,7 +65,7 @@ __global__ void row_argmax_kernel(const float* __restrict__ x, int rows, int V,
   if (r >= rows) return;
   const float* p = x + (long long)r * V;
   float bv = -__builtin_huge_valf();
-  int bi = 0x7fffffff;
+  int bi = 0;   // as best_path_kernel: the initial index is in range, an all-NaN row gives 0
   for (int v = lane; v < V; v += 64) argmax_pair(bv, bi, p[v], v);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {

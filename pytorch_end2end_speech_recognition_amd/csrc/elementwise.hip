@@ -29,8 +29,9 @@ __global__ void embedding_fwd(const long long* __restrict__ idx, const float* __
   }
 }
 
-// gw[v, e] += sum_{r: idx[r]==v} dout[r, e]  (skip v == padding_idx); fixed
-// order over r -> deterministic.  One thread per (v, e).
+// gw[v, e] += sum_{r: clamp(idx[r], 0, V-1)==v} dout[r, e]  (skip v ==
+// padding_idx; the clamp is the forward's, so the gradient goes to the row the
+// forward read); fixed order over r -> deterministic.  One thread per (v, e).
 __global__ void embedding_bwd(const long long* __restrict__ idx, const float* __restrict__ dout,
                               int n, int V, int E, int trans, int padding_idx,
                               float* __restrict__ gw) {
@@ -40,8 +41,11 @@ __global__ void embedding_bwd(const long long* __restrict__ idx, const float* __
     const int v = (int)(i / E), e = (int)(i % E);
     if (v == padding_idx) continue;
     float s = 0.f;
-    for (int r = 0; r < n; ++r)
-      if (idx[r] == v) s += dout[(long long)r * E + e];
+    for (int r = 0; r < n; ++r) {
+      long long t = idx[r];
+      t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+      if (t == v) s += dout[(long long)r * E + e];
+    }
     if (trans) gw[(long long)e * V + v] += s;
     else gw[i] += s;
   }
