@@ -500,6 +500,36 @@ int asr_ctc_best_path(const float* logits, long long stride_t, long long stride_
                       int V, const int32_t* lens, int blank, int32_t* hyps, int32_t* hyp_lens,
                       void* stream);
 int asr_row_argmax(const float* x, int rows, int V, long long* out, void* stream);
+/* asr_ctc_beam_search: CTC prefix beam search (beam_search_decoder.py:22-124
+ *   with alpha = beta = 0): per utterance the most probable prefix among the
+ *   beam_width kept per frame, prefixes ranked by logaddexp(p_blank,
+ *   p_nonblank), candidates that denote the same prefix summed before ranking.
+ *   logits / strides / lens as asr_ctc_best_path (lens[b] is clipped to T;
+ *   frames at t >= lens[b] are never read).  normalize != 0: logits are raw
+ *   and the log-softmax is fused; normalize == 0: logits are log-probabilities.
+ *   hyps int32 [B][T] (first hyp_lens[b] valid), hyp_lens int32 [B], scores
+ *   float32 [B] = log-probability of the returned prefix (lens[b] == 0: empty
+ *   hypothesis, score 0).  float32 arithmetic throughout.  On exactly equal
+ *   scores: entries already in the beam before extensions, by their previous
+ *   rank; extensions by parent rank, then by (logit descending, class
+ *   ascending).  A NaN logit never enters the per-frame class ranking.
+ *   Refused with ASR_ERR_ARG (nothing launched): beam_width outside [1, 64],
+ *   V < 2, blank outside [0, V), a workspace that is not 16-B aligned; with
+ *   ASR_ERR_WORKSPACE: one smaller than asr_ctc_beam_ws_bytes(T, B, V,
+ *   beam_width) (which is 0 for refused shapes).  The workspace needs no
+ *   initialisation.
+ */
+size_t asr_ctc_beam_ws_bytes(int T, int B, int V, int beam_width);
+int asr_ctc_beam_search(const float* logits, long long stride_t, long long stride_b, int T, int B,
+                        int V, const int32_t* lens, int blank, int beam_width, int normalize,
+                        void* ws, size_t ws_bytes, int32_t* hyps, int32_t* hyp_lens, float* scores,
+                        void* stream);
+/* The search's first pass alone (per frame: log-sum-exp and the beam_width + 1
+ * best non-blank classes, into the workspace); for timing it
+ * (tools/ctc_beam_bench.py).  Same checks as asr_ctc_beam_search. */
+int asr_ctc_beam_rows(const float* logits, long long stride_t, long long stride_b, int T, int B,
+                      int V, const int32_t* lens, int blank, int beam_width, int normalize,
+                      void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------- losses
  * Fused softmax cross-entropy + uniform label smoothing over rows of V logits

@@ -131,6 +131,11 @@ SIGNATURES = {
     'asr_ctc_best_path': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                   c_vp]),
     'asr_row_argmax': (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
+    'asr_ctc_beam_ws_bytes': (c_size, [c_int, c_int, c_int, c_int]),
+    'asr_ctc_beam_search': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                    c_int, c_vp, c_size, c_vp, c_vp, c_vp, c_vp]),
+    'asr_ctc_beam_rows': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                  c_vp, c_size, c_vp]),
     'asr_xent_workspace_bytes': (c_size, [c_int]),
     'asr_xent_forward': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_float, c_float, c_vp,
                                  c_vp, c_size, c_vp]),

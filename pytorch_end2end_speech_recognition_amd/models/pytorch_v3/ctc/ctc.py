@@ -21,6 +21,7 @@ from ..base import ModelBase, check_recurrences, eval_retry
 from ..linear import LinearND
 from ..encoders.load_encoder import load
 from ..criterion import cross_entropy_label_smoothing
+from .decoders.beam_search_decoder import BeamSearchDecoder
 from .decoders.greedy_decoder import GreedyDecoder
 
 
@@ -105,6 +106,7 @@ class CTC(ModelBase):
             self.init_forget_gate_bias_with_one()
 
         self._decode_greedy_np = GreedyDecoder(blank_index=0)
+        self._decode_beam_np = BeamSearchDecoder(blank_index=0)
         self.flatten_parameters_()
         self.encoder.__dict__['_owner'] = self
 
@@ -191,20 +193,38 @@ class CTC(ModelBase):
         with torch.no_grad():
             self._flat_param.add_(torch.randn_like(self._flat_param) * std + mean)
 
+    def _task_logits(self, xs_d, x_lens, task):
+        """ctc.py:423-433 / :478-488: the logits, device lengths and host
+        lengths of the head `task` selects.  A model with a sub head: 0 is the
+        main head, 1 the sub head, anything else raises; a single-task model
+        ignores `task`."""
+        if not hasattr(self, 'main_loss_weight'):
+            logits, lens_d, _ = self._encode(xs_d, x_lens)
+            return logits, lens_d, self.encoder.last_lens_np
+        if task not in (0, 1):
+            raise NotImplementedError('task index %r (0: main head, 1: sub head)' % (task,))
+        logits, lens_d, logits_sub, lens_sub_d, _ = self._encode(xs_d, x_lens, is_multi_task=True)
+        if task == 0:
+            return logits, lens_d, self.encoder.last_lens_np
+        return logits_sub, lens_sub_d, self.encoder.last_lens_sub_np
+
     @eval_retry
     @torch.no_grad()
     def decode(self, xs, x_lens, beam_width, max_decode_len=None, min_decode_len=0,
                length_penalty=0, coverage_penalty=0, task_index=0):
-        """ctc.py:398-452.  beam_width == 1: device best path (HIP kernel);
-        returns (best_hyps [B] object array of int arrays, None, perm_idx)."""
+        """ctc.py:398-452.  beam_width == 1: device best path; beam_width > 1:
+        device prefix beam search on the raw logits (log-softmax fused, no
+        [B, T, V] log-probability tensor).  Returns (best_hyps [B] object array
+        of int arrays, None, perm_idx)."""
         self.eval()
-        if beam_width != 1:
-            raise NotImplementedError('CTC prefix beam search is host-side inference, out of '
-                                      'the training hot path (SURVEY §2 #12)')
         xs_d = self.np2var(xs, dtype='float')
-        logits, out_lens_d, perm_d = self._encode(xs_d, x_lens)
+        logits, out_lens_d, _ = self._task_logits(xs_d, x_lens, task_index)
         check_recurrences(self)
-        best_hyps = self._decode_greedy_np(logits, out_lens_d)
+        if beam_width == 1:
+            best_hyps = self._decode_greedy_np(logits, out_lens_d)
+        else:
+            best_hyps = self._decode_beam_np(logits, out_lens_d, beam_width=beam_width,
+                                             normalize=True)
         best_hyps = np.array([h - 1 for h in best_hyps] + [None], dtype=object)[:-1]
         return best_hyps, None, self.encoder.last_perm_np.copy()
 
@@ -216,16 +236,18 @@ class CTC(ModelBase):
         if blank_scale is not None:
             raise NotImplementedError
         xs_d = self.np2var(xs, dtype='float')
-        logits, out_lens_d, perm_d = self._encode(xs_d, x_lens)
+        logits, _, lens_np = self._task_logits(xs_d, x_lens, task_idx)
         check_recurrences(self)
         probs = ops.softmax(logits * (1.0 / temperature))
-        return self.var2np(probs), self.encoder.last_lens_np.copy(), \
+        return self.var2np(probs), np.asarray(lens_np).astype(np.int32).copy(), \
             self.encoder.last_perm_np.copy()
 
     def decode_from_probs(self, probs, x_lens, beam_width=1, max_decode_len=None):
-        """ctc.py:504-529 (host numpy, as the reference)."""
-        if beam_width != 1:
-            raise NotImplementedError
+        """ctc.py:504-529.  beam_width == 1 on the host, as the reference;
+        beam_width > 1 on the device, fed log(probs + 1e-10) as it stands."""
         log_probs = np.log(probs + 1e-10)
-        best = self._decode_greedy_np(log_probs, x_lens)
+        if beam_width == 1:
+            best = self._decode_greedy_np(log_probs, x_lens)
+        else:
+            best = self._decode_beam_np(log_probs, x_lens, beam_width=beam_width)
         return np.array([h - 1 for h in best] + [None], dtype=object)[:-1]

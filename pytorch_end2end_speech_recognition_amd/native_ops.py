@@ -2652,6 +2652,30 @@ def ctc_best_path(logits, lens, blank=0):
     return hyps, hl
 
 
+_beam_ws = {}    # device -> workspace of the largest ctc_beam_search call so far
+
+
+def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True):
+    """CTC prefix beam search on device (asr_ctc_beam_search): logits [B, T, V]
+    raw (normalize=True: the log-softmax is fused) or log-probabilities.
+    Returns (hyps int32 [B, T], hyp_lens int32 [B], scores float32 [B])."""
+    N.require_device(logits, lens)
+    logits = logits.contiguous().float()
+    B, T, V = logits.shape
+    dev = logits.device
+    hyps = torch.empty(B, T, dtype=torch.int32, device=dev)
+    hl = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, dtype=torch.float32, device=dev)
+    nb = N.query('asr_ctc_beam_ws_bytes', T, B, V, int(beam_width))
+    ws = _beam_ws.get(dev)
+    if ws is None or ws.numel() < nb:
+        ws = _beam_ws[dev] = _ws(nb, dev)
+    N.call('asr_ctc_beam_search', N.ptr(logits), V, T * V, T, B, V,
+           N.ptr(lens.int().contiguous()), int(blank), int(beam_width), int(bool(normalize)),
+           N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl), N.ptr(scores), N.stream_handle(dev))
+    return hyps, hl, scores
+
+
 def row_argmax(x):
     N.require_device(x)
     x = x.contiguous()
