@@ -1996,6 +1996,8 @@ __host__ __device__ inline PbGeom pb_geom(const Dims& d, bool f32 = false) {
   g.wdl = o; o += d.A * g.UPW;
   g.cmb = o;
   g.cmbn = max(max(8 * d.A, PD_THREADS), 4 * ((g.FCH + 3) / 4) * 4 * d.C);
+  // phase F's dF tiles: MT row tiles of 16 x 16 (MT = 4 above 32 frames)
+  g.cmbn = max(g.cmbn, (g.FCH <= 16 ? 1 : g.FCH <= 32 ? 2 : 4) * 256);
   o += g.cmbn;
   g.red = o; o += 64;
   g.total = (o + 3) & ~3;
