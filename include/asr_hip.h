@@ -688,6 +688,58 @@ int asr_att_step_backward(const asr_attdec_dims_t* dims, const float* enc, const
                           float* dctx_tot, float* dwd, float* dv_part, float* dwc_part,
                           float* dcw_part, void* workspace, size_t ws_bytes, void* stream);
 
+/* Attention beam search on the device (AttentionSeq2seq._decode_infer_beam,
+ * attention_seq2seq.py:1038-1237; csrc/att_beam.hip states the semantics) for
+ * bahdanau order, a one-layer LSTMCell decoder without residual, location or
+ * content attention.  f32 arithmetic whatever the compute mode.  dims as above
+ * (T = the padded frame count, S ignored); every utterance decodes over its
+ * own lens[b] frames (clipped to [0, T]; 0 frames: empty hypothesis).
+ * opts: W beam width, V classes, Y embedding width, Dz bottleneck width,
+ *   max_len / min_len (min_decode_len counts <sos>), eos, length_penalty
+ *   (added in double), the decoder weights: w_ih [4D][ld_ih] (columns [0, Y)
+ *   embedding, [Y, Y + E) context), w_hh [4D][D], b_ih / b_hh [4D], w_dec
+ *   [A][D], w_conv [A][C], conv_w [C][K], v [A], w_d [Dz][D], w_c [Dz][E],
+ *   w_fc [V][Dz] (b_d, b_c, b_fc nullable), emb_w [V][Y] ([Y][V] if emb_trans).
+ * enc [B][T][E], enc_a [B][T][A] (= W_enc enc + b), h0 [B][D] (nullable).
+ * Outputs: tokens int64 [B][max_len] (hyp_lens[b] valid, -1 after; the final
+ *   <eos> included when the hypothesis completed), hyp_lens int32 [B], scores
+ *   double [B], aw float [B][max_len][T] (row s = the weights of step s along
+ *   the hypothesis' parent rows; zero past hyp_lens[b] rows and lens[b] frames).
+ * Plain launches on `stream` in a fixed order, 4 per step; no allocation, no
+ * host synchronisation.  The workspace (asr_att_beam_ws_bytes; 256-B aligned,
+ * no initialisation) holds the per-step attention record [max_len][B*W][T]
+ * and the logits [B*W][V]; utterances read enc in place, so lens_host (nullable)
+ * does not change its size.
+ * ASR_ERR_UNSUPPORTED (nothing launched, asr_last_error says why): W outside
+ *   [2, 32], C > 16, or a kernel's LDS need above 64 KiB (attention: D + 2A +
+ *   C K + A C + 2T + K + 63 floats); asr_att_beam_ws_bytes is 0 then. */
+typedef struct {
+  int W, V, Y, Dz, max_len, min_len, eos, emb_trans;
+  double length_penalty;
+  long long ld_ih;
+  const float* w_ih;
+  const float* w_hh;
+  const float* b_ih;
+  const float* b_hh;
+  const float* w_dec;
+  const float* w_conv;
+  const float* conv_w;
+  const float* v;
+  const float* w_d;
+  const float* b_d;
+  const float* w_c;
+  const float* b_c;
+  const float* w_fc;
+  const float* b_fc;
+  const float* emb_w;
+} asr_att_beam_opts_t;
+size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
+                             int max_len, const int32_t* lens_host);
+int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
+                        const float* enc, const float* enc_a, const int32_t* lens,
+                        const float* h0, void* workspace, size_t ws_bytes, long long* tokens,
+                        int32_t* hyp_lens, double* scores, float* aw, void* stream);
+
 /* Test / diagnostics: the attention-step kernel instantiations the last
  * asr_attdec_forward_ex / _backward_ex launched: out4 = {forward conv-channel
  * template (10 or 3; 0 = generic), forward 32-frame chunks per utterance,

@@ -223,6 +223,8 @@ SIGNATURES = {
     'asr_att_step_workspace_bytes': (c_size, [c_vp]),
     'asr_att_step_forward': (c_int, [c_vp] + [c_vp] * 12 + [c_size, c_vp]),
     'asr_att_step_backward': (c_int, [c_vp] + [c_vp] * 21 + [c_size, c_vp]),
+    'asr_att_beam_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    'asr_att_beam_decode': (c_int, [c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
@@ -281,6 +283,15 @@ class AttDecOpts(ctypes.Structure):
                 ('drop_emb', c_float), ('seed_emb', ctypes.c_ulonglong), ('w_ih_emb', c_vp),
                 ('ld_ih', c_ll), ('b_ih', c_vp), ('b_hh', c_vp), ('pre_ss', c_vp),
                 ('emb_ss', c_vp), ('tok_ss', c_vp), ('d_pre', c_vp), ('dg_ss', c_vp)]
+
+
+class AttBeamOpts(ctypes.Structure):
+    """asr_att_beam_opts_t"""
+    _fields_ = [(n, c_int) for n in ('W', 'V', 'Y', 'Dz', 'max_len', 'min_len', 'eos',
+                                     'emb_trans')] + [
+        ('length_penalty', ctypes.c_double), ('ld_ih', c_ll)] + [
+        (n, c_vp) for n in ('w_ih', 'w_hh', 'b_ih', 'b_hh', 'w_dec', 'w_conv', 'conv_w', 'v',
+                            'w_d', 'b_d', 'w_c', 'b_c', 'w_fc', 'b_fc', 'emb_w')]
 
 
 class Gemm(ctypes.Structure):

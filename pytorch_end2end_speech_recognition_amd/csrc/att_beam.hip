@@ -1,0 +1,600 @@
+// Attention beam search on gfx950 (AttentionSeq2seq._decode_infer_beam,
+// attention_seq2seq.py:1038-1237 of the reference) for the decoders the fused
+// pass covers: bahdanau order, one LSTMCell layer, no residual, location or
+// content attention.  f32 arithmetic in both compute modes: a beam of at most
+// W rows needs no MFMA throughput, and a bf16 near-tie flip changes whole
+// hypotheses.
+//
+// Semantics (those of the host path, which the recorded fixtures pin):
+//   * each utterance decodes over its own frames: T = lens[b], enc[b, :L].
+//     The attention mask is multiplicative, so a frame past the length would
+//     get energy 0 and a non-zero weight; here the convolution window, the
+//     softmax and the context all stop at L, as if the utterance were alone.
+//   * step 0 runs one row from <sos> and the initial state (no cell step, the
+//     first attention uses h0); later steps run the live hypotheses (<= W).
+//   * per row: f32 log-softmax (lg - max) - log(sum(exp(lg - max))), then the
+//     min(W, V) best classes in descending order, the lower class index first
+//     among equal values.
+//   * candidates in (parent ascending, rank ascending) order; <eos> is dropped
+//     while len(hyp) < min_decode_len (len counts <sos>: t + 1 at step t);
+//     score = (parent score + log-prob) + length_penalty, in double.
+//   * sort by score, descending and stable (ties keep generation order), keep
+//     the first W: those ending in <eos> join `complete`, the others form the
+//     next beam.
+//   * an utterance stops once `complete` holds W entries (the first W in
+//     insertion order are kept), or its beam is empty, or at max_decode_len.
+//     If nothing completed, the final beam is `complete`.  The answer is the
+//     top score of a stable descending sort of `complete`.
+//   * the hypothesis includes its final <eos> if it completed; its attention
+//     weights follow its parent rows step by step ([len][L]).
+//
+// Kernels, launched in a fixed order on the caller's stream, max_decode_len
+// times (no host read, no spin-wait, no hand-off between work-groups; every
+// work-group reads its utterance's done word first and leaves uniformly):
+//   beam_cell    (row)  t >= 1: embedding of the row's token, LSTMCell on
+//                       [e; ctx; h] of the parent row -> h, c
+//   beam_attend  (row)  W_dec h, conv(aw of the parent row), energies,
+//                       sharpening, softmax / sigmoid over L, context; aw goes
+//                       to the per-step record [step][row][T]
+//   beam_expand  (row)  z = tanh(W_d h + b_d + W_c ctx + b_c), the V logits,
+//                       log-softmax, the min(W, V) best in order
+//   beam_select  (utt)  one wave: the <= W x W candidates, W rounds of
+//                       (score descending, generation index ascending), then
+//                       completion and the next beam (token, parent, score)
+//   beam_backtrack (utt) at the end: best entry, its tokens and aw rows
+// The state is double buffered by step parity and read through the parent
+// index, so no gather pass exists.
+#include <limits.h>
+
+#include "common.h"
+
+namespace asr {
+namespace {
+
+constexpr int kMinBeam = 2, kMaxBeam = 32;
+constexpr int CELL_THREADS = 256, ATT_THREADS = 512, EXP_THREADS = 256, BT_THREADS = 256;
+constexpr int kMaxC = 16;
+constexpr size_t kLdsLimit = 64 * 1024;
+
+struct BeamP {
+  int B, T, E, A, C, K, D, W, V, Y, Dz, max_len, min_len, eos, sigmoid, emb_trans;
+  float sharpen;
+  double penalty;
+  long long ld_ih;
+  const float *enc, *enc_a, *h0;
+  const int32_t* lens;
+  const float *w_ih, *w_hh, *b_ih, *b_hh, *w_dec, *w_conv, *conv_w, *v;
+  const float *w_d, *b_d, *w_c, *b_c, *w_fc, *b_fc, *emb_w;
+  // workspace
+  float *h, *c, *ctx;      // [2][R][D], [2][R][D], [2][R][E]   (R = B * W)
+  float *lg;               // [R][V]
+  float *awrec;            // [max_len][R][T]
+  float *topv;             // [R][W]
+  int *topc;               // [R][W]
+  double *sc;              // [B][W] scores of the live rows
+  int *tok_tab, *par_tab;  // [max_len][B][W]: row j of step t + 1 = (token, parent row) picked at t
+  int *n_live, *done, *ncomp, *last_t;   // [B]
+  double *comp_score;      // [B][W]
+  int *comp_t, *comp_par;  // [B][W]: completed at step t from parent row
+  int *rows;               // [B][max_len]: the best hypothesis' row per step
+};
+
+__device__ __forceinline__ int utt_len(const BeamP& p, int b) {
+  return max(0, min(p.lens[b], p.T));
+}
+
+__device__ __forceinline__ float block_red(float v, float* red, bool is_max) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  v = is_max ? wave_max(v) : wave_sum(v);
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  float r = red[0];
+  for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, red[i]) : r + red[i];
+  __syncthreads();
+  return r;
+}
+
+__global__ void __launch_bounds__(256) beam_init(BeamP p) {
+  const int b = blockIdx.x;
+  const long long r = (long long)b * p.W;
+  for (int j = threadIdx.x; j < p.D; j += blockDim.x) {
+    p.h[r * p.D + j] = p.h0 ? p.h0[(long long)b * p.D + j] : 0.f;
+    p.c[r * p.D + j] = 0.f;
+  }
+  if (threadIdx.x == 0) {
+    p.n_live[b] = 1;
+    p.done[b] = (utt_len(p, b) <= 0 || p.max_len <= 0) ? 1 : 0;
+    p.ncomp[b] = 0;
+    p.last_t[b] = -1;
+    p.sc[r] = 0.0;
+  }
+}
+
+// ------------------------------------------------------------------- cell
+__global__ void __launch_bounds__(CELL_THREADS) beam_cell(int t, BeamP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = CELL_THREADS / 64;
+  const long long R = (long long)p.B * p.W;
+  const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
+  const int par = p.par_tab[tab], tok = p.tok_tab[tab];
+  const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
+  const int cur = t & 1, prev = cur ^ 1;
+  const int YE = p.Y + p.E;
+  float* x = sm;   // [Y + E + D] = [e; ctx; h] of the parent row
+  for (int y = tid; y < p.Y; y += CELL_THREADS)
+    x[y] = p.emb_trans ? p.emb_w[(long long)y * p.V + tok] : p.emb_w[(long long)tok * p.Y + y];
+  for (int e = tid; e < p.E; e += CELL_THREADS) x[p.Y + e] = p.ctx[(prev * R + pr) * p.E + e];
+  for (int j = tid; j < p.D; j += CELL_THREADS) x[YE + j] = p.h[(prev * R + pr) * p.D + j];
+  __syncthreads();
+  for (int u = w; u < p.D; u += nw) {   // one wave per hidden unit, lanes over K
+    float s[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const long long row = (long long)g * p.D + u;
+      const float* wi = p.w_ih + row * p.ld_ih;
+      const float* wh = p.w_hh + row * p.D;
+      float a = 0.f;
+      for (int k = lane; k < YE; k += 64) a += wi[k] * x[k];
+      for (int k = lane; k < p.D; k += 64) a += wh[k] * x[YE + k];
+      s[g] = wave_sum(a) + p.b_ih[row] + p.b_hh[row];
+    }
+    if (lane == 0) {
+      const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
+      const float gg = tanhf_(s[2]), og = sigmoidf_(s[3]);
+      const float cn = fg * p.c[(prev * R + pr) * p.D + u] + ig * gg;
+      p.c[(cur * R + r) * p.D + u] = cn;
+      p.h[(cur * R + r) * p.D + u] = og * tanhf_(cn);
+    }
+  }
+}
+
+// -------------------------------------------------------------- attention
+__host__ __device__ inline size_t attend_lds_floats(int D, int A, int C, int K, int T) {
+  return (size_t)D + 2 * (size_t)A + (size_t)C * K + (size_t)A * C + ((size_t)T + K - 1) + T + 64;
+}
+
+__global__ void __launch_bounds__(ATT_THREADS) beam_attend(int t, BeamP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = ATT_THREADS / 64;
+  const int L = utt_len(p, b), half = p.K / 2;
+  const long long R = (long long)p.B * p.W;
+  const long long r = (long long)b * p.W + i;
+  const int cur = t & 1;
+  float* hS = sm;                          // [D]
+  float* wd = hS + p.D;                    // [A]  W_dec h
+  float* vS = wd + p.A;                    // [A]
+  float* cw = vS + p.A;                    // [C*K]
+  float* wc = cw + (size_t)p.C * p.K;      // [A*C]
+  float* awp = wc + (size_t)p.A * p.C;     // [L + K - 1] aw_{t-1}[tt - half + k], 0 outside [0, L)
+  float* e = awp + (p.T + p.K - 1);        // [L] energies, then aw_t
+  float* red = e + p.T;                    // [64]
+  for (int j = tid; j < p.D; j += ATT_THREADS) hS[j] = p.h[(cur * R + r) * p.D + j];
+  for (int j = tid; j < p.A; j += ATT_THREADS) vS[j] = p.v[j];
+  for (int j = tid; j < p.C * p.K; j += ATT_THREADS) cw[j] = p.conv_w[j];
+  for (int j = tid; j < p.A * p.C; j += ATT_THREADS) wc[j] = p.w_conv[j];
+  if (t > 0) {
+    const int par = p.par_tab[((long long)(t - 1) * p.B + b) * p.W + i];
+    const float* ap = p.awrec + ((long long)(t - 1) * R + (long long)b * p.W + par) * p.T;
+    for (int j = tid; j < L + p.K - 1; j += ATT_THREADS) {
+      const int tt = j - half;
+      awp[j] = (tt >= 0 && tt < L) ? ap[tt] : 0.f;
+    }
+  }
+  __syncthreads();
+  for (int a = w; a < p.A; a += nw) {
+    const float* wr = p.w_dec + (long long)a * p.D;
+    float s = 0.f;
+    for (int k = lane; k < p.D; k += 64) s += wr[k] * hS[k];
+    s = wave_sum(s);
+    if (lane == 0) wd[a] = s;
+  }
+  __syncthreads();
+  for (int tt = w; tt < L; tt += nw) {     // one wave per frame
+    float f[kMaxC];
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) {
+      f[c] = 0.f;
+      if (c < p.C && t > 0) {              // wave-uniform
+        float s = 0.f;
+        for (int k = lane; k < p.K; k += 64) s += cw[c * p.K + k] * awp[tt + k];
+        f[c] = wave_sum(s);
+      }
+    }
+    const float* er = p.enc_a + ((long long)b * p.T + tt) * p.A;
+    float s = 0.f;
+    for (int a = lane; a < p.A; a += 64) {
+      float q = er[a] + wd[a];
+#pragma unroll
+      for (int c = 0; c < kMaxC; ++c)
+        if (c < p.C) q += f[c] * wc[a * p.C + c];
+      s += vS[a] * tanhf(q);
+    }
+    s = wave_sum(s);
+    if (lane == 0) e[tt] = s * p.sharpen;
+  }
+  __syncthreads();
+  if (p.sigmoid) {
+    for (int j = tid; j < L; j += ATT_THREADS) e[j] = sigmoidf_(e[j]);
+  } else {
+    float mx = neg_inf();
+    for (int j = tid; j < L; j += ATT_THREADS) mx = fmaxf(mx, e[j]);
+    mx = block_red(mx, red, true);
+    float s = 0.f;
+    for (int j = tid; j < L; j += ATT_THREADS) {
+      const float q = __expf(e[j] - mx);
+      e[j] = q;
+      s += q;
+    }
+    s = block_red(s, red, false);
+    const float inv = 1.f / s;
+    for (int j = tid; j < L; j += ATT_THREADS) e[j] *= inv;
+  }
+  __syncthreads();
+  float* rec = p.awrec + ((long long)t * R + r) * p.T;
+  for (int j = tid; j < p.T; j += ATT_THREADS) rec[j] = j < L ? e[j] : 0.f;
+  for (int col = tid; col < p.E; col += ATT_THREADS) {
+    const float* er = p.enc + (long long)b * p.T * p.E + col;
+    float s = 0.f;
+    int tt = 0;
+    for (; tt + 8 <= L; tt += 8) {
+      float u[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) u[j] = er[(long long)(tt + j) * p.E];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += e[tt + j] * u[j];
+    }
+    for (; tt < L; ++tt) s += e[tt] * er[(long long)tt * p.E];
+    p.ctx[(cur * R + r) * p.E + col] = s;
+  }
+}
+
+// ----------------------------------------------------------------- expand
+__device__ __forceinline__ void arg_pair(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+__global__ void __launch_bounds__(EXP_THREADS) beam_expand(int t, BeamP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = EXP_THREADS / 64;
+  const long long R = (long long)p.B * p.W;
+  const long long r = (long long)b * p.W + i;
+  const int cur = t & 1;
+  float* hS = sm;             // [D]
+  float* cS = hS + p.D;       // [E]
+  float* z = cS + p.E;        // [Dz]
+  float* red = z + p.Dz;      // [4]
+  int* redi = (int*)(red + 4);   // [4]
+  for (int j = tid; j < p.D; j += EXP_THREADS) hS[j] = p.h[(cur * R + r) * p.D + j];
+  for (int j = tid; j < p.E; j += EXP_THREADS) cS[j] = p.ctx[(cur * R + r) * p.E + j];
+  __syncthreads();
+  for (int k = w; k < p.Dz; k += nw) {
+    const float* wdr = p.w_d + (long long)k * p.D;
+    const float* wcr = p.w_c + (long long)k * p.E;
+    float sa = 0.f, sc = 0.f;
+    for (int j = lane; j < p.D; j += 64) sa += wdr[j] * hS[j];
+    for (int j = lane; j < p.E; j += 64) sc += wcr[j] * cS[j];
+    sa = wave_sum(sa);
+    sc = wave_sum(sc);
+    if (lane == 0) z[k] = tanhf((sa + (p.b_d ? p.b_d[k] : 0.f)) + (sc + (p.b_c ? p.b_c[k] : 0.f)));
+  }
+  __syncthreads();
+  float* lg = p.lg + r * p.V;
+  float mx = neg_inf();
+  for (int v = w; v < p.V; v += nw) {      // one wave per class
+    const float* wr = p.w_fc + (long long)v * p.Dz;
+    float s = 0.f;
+    for (int k = lane; k < p.Dz; k += 64) s += wr[k] * z[k];
+    s = wave_sum(s) + (p.b_fc ? p.b_fc[v] : 0.f);
+    if (lane == 0) lg[v] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = block_red(mx, red, true);           // its barriers also publish lg to the work-group
+  float se = 0.f;
+  for (int v = tid; v < p.V; v += EXP_THREADS) se += expf(lg[v] - mx);
+  se = block_red(se, red, false);
+  const float lse = logf(se);
+  // round k takes the best of what lies strictly after round k - 1's pick in
+  // the order (log-prob descending, class ascending)
+  const int ktop = min(p.W, p.V);
+  float pv = __builtin_huge_valf();
+  int pi = -1;
+  for (int k = 0; k < ktop; ++k) {
+    float bv = neg_inf();
+    int bi = INT_MAX;
+    for (int v = tid; v < p.V; v += EXP_THREADS) {
+      const float lp = (lg[v] - mx) - lse;
+      if (lp < pv || (lp == pv && v > pi)) arg_pair(bv, bi, lp, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      arg_pair(bv, bi, ov, oi);
+    }
+    __syncthreads();
+    if (lane == 0) { red[w] = bv; redi[w] = bi; }
+    __syncthreads();
+    bv = red[0];
+    bi = redi[0];
+    for (int q = 1; q < nw; ++q) arg_pair(bv, bi, red[q], redi[q]);
+    if (tid == 0) {
+      p.topv[r * p.W + k] = bv;
+      p.topc[r * p.W + k] = bi == INT_MAX ? -1 : bi;
+    }
+    pv = bv;
+    pi = bi;
+  }
+}
+
+// ----------------------------------------------------------------- select
+__global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
+  __shared__ double s_score[kMaxBeam * kMaxBeam];
+  __shared__ int s_tok[kMaxBeam * kMaxBeam];
+  __shared__ double s_selv[kMaxBeam];
+  __shared__ int s_seli[kMaxBeam];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (p.done[b]) return;
+  const int n = p.n_live[b];
+  const int ktop = min(p.W, p.V);
+  const int nc = n * ktop;                 // <= W * W
+  const long long r0 = (long long)b * p.W;
+  for (int e = lane; e < nc; e += 64) {
+    const int i = e / ktop, k = e - i * ktop;
+    const int tok = p.topc[(r0 + i) * p.W + k];
+    const bool drop = tok < 0 || (tok == p.eos && t + 1 < p.min_len);
+    s_tok[e] = drop ? -1 : tok;
+    s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k]) + p.penalty;
+  }
+  __syncthreads();
+  // W rounds of (score descending, generation index ascending)
+  double ps = __builtin_huge_val();
+  int pi = -1, nsel = 0;
+  for (int rd = 0; rd < p.W; ++rd) {
+    double bs = -__builtin_huge_val();
+    int bi = INT_MAX;
+    for (int e = lane; e < nc; e += 64) {
+      if (s_tok[e] < 0) continue;
+      const double s = s_score[e];
+      const bool after = s < ps || (s == ps && e > pi);
+      if (after && (bi == INT_MAX || s > bs)) { bs = s; bi = e; }   // e ascending: first wins
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double os = __shfl_xor(bs, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (oi != INT_MAX && (bi == INT_MAX || os > bs || (os == bs && oi < bi))) { bs = os; bi = oi; }
+    }
+    if (bi == INT_MAX) break;              // wave-uniform
+    if (lane == 0) { s_selv[rd] = bs; s_seli[rd] = bi; }
+    ps = bs;
+    pi = bi;
+    ++nsel;
+  }
+  __syncthreads();
+  if (lane == 0) {
+    // p.sc was last read before the barrier above: the new beam's scores go
+    // straight over it (unused if the utterance completes at this step)
+    int ncomp = p.ncomp[b], nb = 0;
+    for (int rd = 0; rd < nsel; ++rd) {
+      const int e = s_seli[rd], i = e / ktop, tok = s_tok[e];
+      if (tok == p.eos) {
+        if (ncomp < p.W) {
+          p.comp_score[r0 + ncomp] = s_selv[rd];
+          p.comp_t[r0 + ncomp] = t;
+          p.comp_par[r0 + ncomp] = i;
+        }
+        ++ncomp;
+      } else {
+        const long long tab = ((long long)t * p.B + b) * p.W + nb;
+        p.tok_tab[tab] = tok;
+        p.par_tab[tab] = i;
+        p.sc[r0 + nb] = s_selv[rd];
+        ++nb;
+      }
+    }
+    if (ncomp >= p.W) {                    // complete = complete[:W]; break
+      p.ncomp[b] = p.W;
+      p.done[b] = 1;
+    } else {
+      p.ncomp[b] = ncomp;
+      p.n_live[b] = nb;
+      p.last_t[b] = t;
+      if (nb == 0) p.done[b] = 1;
+    }
+  }
+}
+
+// -------------------------------------------------------------- backtrack
+__global__ void __launch_bounds__(BT_THREADS) beam_backtrack(BeamP p, long long* __restrict__ tokens,
+                                                             int32_t* __restrict__ hyp_lens,
+                                                             double* __restrict__ scores,
+                                                             float* __restrict__ aw) {
+  __shared__ int s_len;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long r0 = (long long)b * p.W;
+  const long long R = (long long)p.B * p.W;
+  int* rows = p.rows + (long long)b * p.max_len;
+  long long* out = tokens + (long long)b * p.max_len;
+  if (tid == 0) {
+    int len = 0, tf = -1, par = 0, tok = -1;
+    double best = 0.0;
+    const int ncomp = p.ncomp[b];
+    if (ncomp > 0) {                       // stable descending sort: the first maximum
+      int q = 0;
+      for (int j = 1; j < ncomp; ++j)
+        if (p.comp_score[r0 + j] > p.comp_score[r0 + q]) q = j;
+      best = p.comp_score[r0 + q];
+      tf = p.comp_t[r0 + q];
+      par = p.comp_par[r0 + q];
+      tok = p.eos;
+    } else if (p.last_t[b] >= 0 && p.n_live[b] > 0) {   // nothing completed: the final beam
+      int q = 0;
+      for (int j = 1; j < p.n_live[b]; ++j)
+        if (p.sc[r0 + j] > p.sc[r0 + q]) q = j;
+      best = p.sc[r0 + q];
+      tf = p.last_t[b];
+      const long long tab = ((long long)tf * p.B + b) * p.W + q;
+      par = p.par_tab[tab];
+      tok = p.tok_tab[tab];
+    }
+    if (tf >= 0) {
+      len = tf + 1;
+      out[tf] = tok;
+      rows[tf] = par;
+      for (int s = tf; s > 0; --s) {
+        const long long tab = ((long long)(s - 1) * p.B + b) * p.W + rows[s];
+        out[s - 1] = p.tok_tab[tab];
+        rows[s - 1] = p.par_tab[tab];
+      }
+    }
+    for (int s = len; s < p.max_len; ++s) out[s] = -1;
+    hyp_lens[b] = len;
+    scores[b] = best;
+    s_len = len;
+  }
+  __syncthreads();
+  const int len = s_len, L = utt_len(p, b);
+  for (int s = 0; s < p.max_len; ++s) {
+    float* dst = aw + ((long long)b * p.max_len + s) * p.T;
+    const float* src = s < len ? p.awrec + ((long long)s * R + r0 + rows[s]) * p.T : nullptr;
+    for (int j = tid; j < p.T; j += BT_THREADS) dst[j] = (src && j < L) ? src[j] : 0.f;
+  }
+}
+
+inline size_t al256(size_t n) { return (n + 255) & ~size_t(255); }
+
+struct BeamWs {
+  size_t h, c, ctx, lg, awrec, topv, topc, sc, tok_tab, par_tab, n_live, done, ncomp, last_t,
+      comp_score, comp_t, comp_par, rows, total;
+};
+
+BeamWs beam_ws(int B, int T, int E, int D, int W, int V, int max_len) {
+  BeamWs w;
+  const size_t R = (size_t)B * W, ml = (size_t)(max_len > 0 ? max_len : 1);
+  size_t o = 0;
+  w.h = o; o += al256(2 * R * D * 4);
+  w.c = o; o += al256(2 * R * D * 4);
+  w.ctx = o; o += al256(2 * R * E * 4);
+  w.lg = o; o += al256(R * V * 4);
+  w.awrec = o; o += al256(ml * R * T * 4);
+  w.topv = o; o += al256(R * W * 4);
+  w.topc = o; o += al256(R * W * 4);
+  w.sc = o; o += al256(R * 8);
+  w.tok_tab = o; o += al256(ml * R * 4);
+  w.par_tab = o; o += al256(ml * R * 4);
+  w.n_live = o; o += al256((size_t)B * 4);
+  w.done = o; o += al256((size_t)B * 4);
+  w.ncomp = o; o += al256((size_t)B * 4);
+  w.last_t = o; o += al256((size_t)B * 4);
+  w.comp_score = o; o += al256(R * 8);
+  w.comp_t = o; o += al256(R * 4);
+  w.comp_par = o; o += al256(R * 4);
+  w.rows = o; o += al256((size_t)B * ml * 4);
+  w.total = o;
+  return w;
+}
+
+// ASR_OK, or the refusal with its reason in the error text
+int beam_check(const asr_attdec_dims_t& d, int W, int V, int Y, int Dz, int max_len) {
+  ASR_REQUIRE(d.B > 0 && d.T > 0 && d.E > 0 && d.A > 0 && d.C > 0 && d.K > 0 && d.D > 0 && V >= 2 &&
+                  Y > 0 && Dz > 0 && max_len >= 0,
+              ASR_ERR_ARG, "att_beam: bad dims");
+  ASR_REQUIRE(d.K % 2 == 1, ASR_ERR_ARG, "att_beam: conv width must be odd");
+  ASR_REQUIRE(W >= kMinBeam && W <= kMaxBeam, ASR_ERR_UNSUPPORTED,
+              "att_beam: beam_width = %d outside [%d, %d]", W, kMinBeam, kMaxBeam);
+  ASR_REQUIRE(d.C <= kMaxC, ASR_ERR_UNSUPPORTED, "att_beam: conv channels <= %d supported (C=%d)",
+              kMaxC, d.C);
+  const size_t la = attend_lds_floats(d.D, d.A, d.C, d.K, d.T) * 4;
+  const size_t lc = ((size_t)Y + d.E + d.D) * 4;
+  const size_t le = ((size_t)d.D + d.E + Dz + 8) * 4;
+  ASR_REQUIRE(la <= kLdsLimit && lc <= kLdsLimit && le <= kLdsLimit, ASR_ERR_UNSUPPORTED,
+              "att_beam: LDS need (attend %zu, cell %zu, expand %zu B) > %zu B", la, lc, le,
+              kLdsLimit);
+  return ASR_OK;
+}
+
+}  // namespace
+}  // namespace asr
+
+using namespace asr;
+
+extern "C" size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
+                                        int max_len, const int32_t* lens_host) {
+  if (!dims || beam_check(*dims, W, V, Y, Dz, max_len) != ASR_OK) return 0;
+  (void)lens_host;   // every utterance reads enc in place: no per-length copies to size
+  return beam_ws(dims->B, dims->T, dims->E, dims->D, W, V, max_len).total;
+}
+
+extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                   const float* enc, const float* enc_a, const int32_t* lens,
+                                   const float* h0, void* workspace, size_t ws_bytes,
+                                   long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
+                                   void* stream) {
+  ASR_REQUIRE(dims && o, ASR_ERR_ARG, "att_beam_decode: dims / opts is null");
+  const int rc = beam_check(*dims, o->W, o->V, o->Y, o->Dz, o->max_len);
+  if (rc) return rc;
+  ASR_REQUIRE(enc && enc_a && lens && workspace && tokens && hyp_lens && scores && aw &&
+                  o->w_ih && o->w_hh && o->b_ih && o->b_hh && o->w_dec && o->w_conv && o->conv_w &&
+                  o->v && o->w_d && o->w_c && o->w_fc && o->emb_w,
+              ASR_ERR_ARG, "att_beam_decode: null pointer");
+  ASR_REQUIRE(o->eos >= 0 && o->eos < o->V, ASR_ERR_ARG, "att_beam_decode: eos = %d outside [0, %d)",
+              o->eos, o->V);
+  ASR_REQUIRE(o->ld_ih >= (long long)o->Y + dims->E, ASR_ERR_ARG,
+              "att_beam_decode: ld_ih = %lld < Y + E", o->ld_ih);
+  ASR_REQUIRE(o->max_len > 0, ASR_ERR_ARG, "att_beam_decode: max_len = %d", o->max_len);
+  const BeamWs w = beam_ws(dims->B, dims->T, dims->E, dims->D, o->W, o->V, o->max_len);
+  ASR_REQUIRE(ws_bytes >= w.total, ASR_ERR_WORKSPACE, "att_beam_decode: workspace %zu < %zu bytes",
+              ws_bytes, w.total);
+  ASR_REQUIRE(((uintptr_t)workspace & 255) == 0, ASR_ERR_ARG,
+              "att_beam_decode: workspace not 256-B aligned");
+  char* base = (char*)workspace;
+  BeamP p;
+  p.B = dims->B; p.T = dims->T; p.E = dims->E; p.A = dims->A; p.C = dims->C; p.K = dims->K;
+  p.D = dims->D; p.W = o->W; p.V = o->V; p.Y = o->Y; p.Dz = o->Dz; p.max_len = o->max_len;
+  p.min_len = o->min_len; p.eos = o->eos; p.sigmoid = dims->sigmoid_smoothing;
+  p.emb_trans = o->emb_trans; p.sharpen = dims->sharpening; p.penalty = o->length_penalty;
+  p.ld_ih = o->ld_ih;
+  p.enc = enc; p.enc_a = enc_a; p.h0 = h0; p.lens = lens;
+  p.w_ih = o->w_ih; p.w_hh = o->w_hh; p.b_ih = o->b_ih; p.b_hh = o->b_hh; p.w_dec = o->w_dec;
+  p.w_conv = o->w_conv; p.conv_w = o->conv_w; p.v = o->v; p.w_d = o->w_d; p.b_d = o->b_d;
+  p.w_c = o->w_c; p.b_c = o->b_c; p.w_fc = o->w_fc; p.b_fc = o->b_fc; p.emb_w = o->emb_w;
+  p.h = (float*)(base + w.h); p.c = (float*)(base + w.c); p.ctx = (float*)(base + w.ctx);
+  p.lg = (float*)(base + w.lg); p.awrec = (float*)(base + w.awrec);
+  p.topv = (float*)(base + w.topv); p.topc = (int*)(base + w.topc); p.sc = (double*)(base + w.sc);
+  p.tok_tab = (int*)(base + w.tok_tab); p.par_tab = (int*)(base + w.par_tab);
+  p.n_live = (int*)(base + w.n_live); p.done = (int*)(base + w.done);
+  p.ncomp = (int*)(base + w.ncomp); p.last_t = (int*)(base + w.last_t);
+  p.comp_score = (double*)(base + w.comp_score); p.comp_t = (int*)(base + w.comp_t);
+  p.comp_par = (int*)(base + w.comp_par); p.rows = (int*)(base + w.rows);
+
+  hipStream_t s = (hipStream_t)stream;
+  const size_t lds_cell = ((size_t)p.Y + p.E + p.D) * 4;
+  const size_t lds_att = attend_lds_floats(p.D, p.A, p.C, p.K, p.T) * 4;
+  const size_t lds_exp = ((size_t)p.D + p.E + p.Dz + 8) * 4;
+  const dim3 rows(p.W, p.B);
+  hipLaunchKernelGGL(beam_init, dim3(p.B), dim3(256), 0, s, p);
+  ASR_LAUNCH_CHECK();
+  for (int t = 0; t < p.max_len; ++t) {
+    if (t > 0) {
+      hipLaunchKernelGGL(beam_cell, rows, dim3(CELL_THREADS), lds_cell, s, t, p);
+      ASR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(beam_attend, rows, dim3(ATT_THREADS), lds_att, s, t, p);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_expand, rows, dim3(EXP_THREADS), lds_exp, s, t, p);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_select, dim3(p.B), dim3(64), 0, s, t, p);
+    ASR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(beam_backtrack, dim3(p.B), dim3(BT_THREADS), 0, s, p, tokens, hyp_lens,
+                     scores, aw);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}

@@ -17,6 +17,7 @@ encoder states, the W_d / W_c bottleneck, the output layer and the loss -- is
 hoisted into full-batch GEMMs before / after the loop; per step only the
 LSTMCell and the fused location-attention kernel run.
 """
+import os
 import random
 
 import numpy as np
@@ -487,15 +488,19 @@ class AttentionSeq2seq(ModelBase):
     @eval_retry
     @torch.no_grad()
     def decode_ctc(self, xs, x_lens, beam_width=1, task_index=0):
-        """:1239-1289 (greedy; HIP best path)."""
+        """:1239-1289 (beam_width 1: HIP best path; > 1: the device prefix beam
+        search, native_ops.ctc_beam_search, on fc_ctc_0's raw logits)."""
         self.eval()
-        if beam_width != 1:
-            raise NotImplementedError
         xs_d = self.np2var(xs, dtype='float')
         enc_out, enc_lens_d, _ = self._encode(xs_d, x_lens)
         logits = self.fc_ctc_0(enc_out)
         check_recurrences(self)
-        hyps = self._decode_ctc_greedy_np(logits, enc_lens_d)
+        if beam_width != 1:
+            h, hl, _ = ops.ctc_beam_search(logits, enc_lens_d, int(beam_width), blank=0)
+            h, hl = h.cpu().numpy(), hl.cpu().numpy()
+            hyps = [h[b, :hl[b]].astype(np.int64) for b in range(len(hl))]
+        else:
+            hyps = self._decode_ctc_greedy_np(logits, enc_lens_d)
         best = np.array([h - 1 for h in hyps] + [None], dtype=object)[:-1]
         return best, self.encoder.last_perm_np.copy()
 
@@ -574,7 +579,75 @@ class AttentionSeq2seq(ModelBase):
         return best_hyps
 
     def _decode_infer_beam(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
-                           length_penalty, coverage_penalty, task=0, dir='fwd'):
+                           length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
+                           _scores=None):
+        """:1038-1237.  Decoders the fused pass covers (_fused_ok) search on the
+        device (native_ops.att_decode_beam, csrc/att_beam.hip: no host read
+        inside the step loop); the others, a shape the kernels refuse, and
+        ASR_ATT_BEAM=host run _decode_infer_beam_host.  Same results either
+        way; native_ops.last_att_beam_path() says which ran.  _gaps: a list
+        that receives the host path's decision margins (filled by that path
+        only); _scores: a list that receives each best hypothesis' score."""
+        if coverage_penalty > 0:
+            raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
+        if (self._fused_ok(task, dir) and max_decode_len >= 1
+                and os.environ.get('ASR_ATT_BEAM', 'device') != 'host'):
+            out = self._decode_infer_beam_device(enc_out, x_lens, beam_width, max_decode_len,
+                                                 min_decode_len, length_penalty, task, dir,
+                                                 _scores)
+            if out is not None:
+                ops._set_att_beam_path('device')
+                return out
+        ops._set_att_beam_path('host')
+        return self._decode_infer_beam_host(enc_out, x_lens, beam_width, max_decode_len,
+                                            min_decode_len, length_penalty, coverage_penalty,
+                                            task, dir, _gaps, _scores)
+
+    def _decode_infer_beam_device(self, enc_out, x_lens, beam_width, max_decode_len,
+                                  min_decode_len, length_penalty, task=0, dir='fwd',
+                                  _scores=None):
+        """The whole search as one op; None when the kernels refuse the shape.
+        One device-to-host copy of the compact results at the end."""
+        att = getattr(self, 'attend_%d_%s' % (task, dir))
+        cell = getattr(self, 'decoder_%d_%s' % (task, dir)).lstm_l0
+        W_d, W_c = getattr(self, 'W_d_%d_%s' % (task, dir)), getattr(self, 'W_c_%d_%s' % (task, dir))
+        fc = getattr(self, 'fc_%d_%s' % (task, dir))
+        embed = getattr(self, 'embed_%d' % task)
+        emb_ls = isinstance(embed, Embedding_LS)
+        emb_w = embed.embed.fc.weight if emb_ls else embed.embed.weight
+        lens = np.asarray(x_lens).reshape(-1).astype(np.int64)
+        bf16 = ops.compute_dtype() == ops.BF16
+        ops.set_compute_dtype('fp32')      # the search is f32 in both compute modes
+        try:
+            h0 = self._init_h0(enc_out, task, dir)
+            enc_a = att.W_enc_head0(enc_out)
+        finally:
+            ops.set_compute_dtype('bf16' if bf16 else 'fp32')
+        gen = dict(w_d=W_d.fc.weight, b_d=W_d.fc.bias, w_c=W_c.fc.weight, b_c=W_c.fc.bias,
+                   w_fc=fc.fc.weight, b_fc=fc.fc.bias, emb_w=emb_w,
+                   emb_trans=int(emb_ls), b_ih=cell.bias_ih, b_hh=cell.bias_hh)
+        out = ops.att_decode_beam(enc_out, enc_a, lens.astype(np.int32), h0, self._emb_dims[task],
+                                  self.sharpening_factor, self.sigmoid_smoothing,
+                                  cell.weight_ih, cell.weight_hh, att.W_dec_head0.fc.weight,
+                                  *att.conv_weights(), att.V_head0.fc.weight, gen, beam_width,
+                                  max_decode_len, min_decode_len, length_penalty,
+                                  getattr(self, 'eos_%d' % task))
+        if out is None:
+            return None
+        toks, hl, sc, aw = (t.cpu().numpy() for t in out)
+        if _scores is not None:
+            _scores.extend(float(v) for v in sc)
+        best = [toks[b, :hl[b]].astype(np.int64) for b in range(len(lens))]
+        aws = [aw[b, :hl[b], :int(lens[b])].copy() for b in range(len(lens))]
+        if dir == 'bwd':                                  # :1231-1234
+            best = self._reverse_bwd(best, [len(h) for h in best])
+        if len(set(len(h) for h in best)) <= 1:
+            return np.array(best), aws
+        return np.array(best + [None], dtype=object)[:-1], aws
+
+    def _decode_infer_beam_host(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
+                                length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
+                                _scores=None):
         """:1038-1237 (any decoding order / decoder depth).  Utterance by utterance like the
         reference, each over its own frames (enc_out[b, :x_len]); the live
         hypotheses of an utterance advance as ONE batch per step on the HIP ops
@@ -613,6 +686,7 @@ class AttentionSeq2seq(ModelBase):
                          aw=init['aw'][b:b + 1, :L])
             beam = [dict(hyp=[sos], score=0.0, row=0, hist=[])]
             complete, step_aw = [], []
+            gap = float('inf')
             for t in range(max_decode_len):
                 n = len(beam)
                 if n == 0:
@@ -653,6 +727,18 @@ class AttentionSeq2seq(ModelBase):
                                         score=beam[i]['score'] + float(lp[i, tok]) + length_penalty,
                                         row=i, hist=beam[i]['hist'] + [(t, i)]))
                 new.sort(key=lambda c: c['score'], reverse=True)     # stable, as sorted()
+                if _gaps is not None:
+                    # the smallest positive margin at a decision boundary: the
+                    # last kept candidate against the first dropped one, and per
+                    # row the last class of the top-k against the next class
+                    ds = []
+                    if len(new) > beam_width:
+                        ds.append(new[beam_width - 1]['score'] - new[beam_width]['score'])
+                    if k_top < lp.shape[1]:
+                        nxt = np.argsort(-lp, axis=1, kind='stable')[:, k_top]
+                        ds += [float(lp[i, order[i, k_top - 1]]) - float(lp[i, nxt[i]])
+                               for i in range(n)]
+                    gap = min([gap] + [d for d in ds if d > 0])
                 not_complete = []
                 for cand in new[:beam_width]:
                     (complete if cand['hyp'][-1] == eos else not_complete).append(cand)
@@ -662,8 +748,12 @@ class AttentionSeq2seq(ModelBase):
                 beam = not_complete[:beam_width]
             if len(complete) == 0:
                 complete = beam
+            if _gaps is not None:
+                _gaps.append(gap)
             complete.sort(key=lambda c: c['score'], reverse=True)
             top = complete[0]
+            if _scores is not None:
+                _scores.append(float(top['score']))
             best.append(np.array(top['hyp'][1:], dtype=np.int64))
             aw_rows = [step_aw[t][i] for t, i in top['hist']]
             aws.append(torch.stack(aw_rows).cpu().numpy() if aw_rows

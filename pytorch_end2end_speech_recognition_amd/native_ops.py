@@ -1068,6 +1068,76 @@ def att_decode_greedy(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_h
     return keep['tok_ss'][:, 1:], outs[5][:, :S - 1]
 
 
+_att_beam = {'path': None, 'ws': {}}
+
+
+def last_att_beam_path():
+    """'device' or 'host': what the last AttentionSeq2seq beam decode ran on
+    (None before the first one); tests read it."""
+    return _att_beam['path']
+
+
+def _set_att_beam_path(path):
+    _att_beam['path'] = path
+
+
+@torch.no_grad()
+def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh, w_dec, w_conv,
+                    conv_w, v, gen, beam_width, max_len, min_len, length_penalty, eos):
+    """Attention beam search on the device (asr_att_beam_decode, csrc/att_beam.hip;
+    attention_seq2seq.py:1038-1237, bahdanau order): every utterance over its
+    own lens[b] frames, f32 in both compute modes, no host read inside the
+    step loop.  gen as att_decode_greedy.  Returns (tokens int64 [B, max_len],
+    lengths int32 [B], scores float64 [B], aw float32 [B, max_len, T]) on the
+    device, or None when the kernels do not cover the shape
+    (ASR_ERR_UNSUPPORTED; the reason is asr_last_error's)."""
+    N.require_device(enc, enc_a, w_ih)
+    enc, enc_a = enc.contiguous().float(), enc_a.contiguous().float()
+    B, T, E = enc.shape
+    A = enc_a.shape[-1]
+    D = w_hh.shape[1]
+    C, K = conv_w.shape[0], conv_w.shape[-1]
+    dev = enc.device
+    V, Dz = gen['w_fc'].shape
+    dims = N.AttDecDims(B, T, E, A, C, K, D, 1, float(sharpen), int(bool(sigmoid)))
+    if torch.is_tensor(lens):
+        lens_d = lens.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_d = h2d(np.asarray(lens, np.int32).reshape(-1), dev)
+    W, max_len = int(beam_width), int(max_len)
+    nb = N.query('asr_att_beam_ws_bytes', ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz),
+                 max_len, None)
+    if nb == 0:
+        return None
+    ws = _att_beam['ws'].get(dev)
+    if ws is None or ws.numel() < nb:
+        ws = _att_beam['ws'][dev] = _ws(nb, dev)
+    keep = [t.contiguous() for t in (w_ih, w_hh, gen['b_ih'], gen['b_hh'], w_dec, w_conv, conv_w,
+                                     v, gen['w_d'], gen['w_c'], gen['w_fc'], gen['emb_w'])]
+    kb = [None if gen[k] is None else gen[k].contiguous() for k in ('b_d', 'b_c', 'b_fc')]
+    pv = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    opts = N.AttBeamOpts(W, int(V), int(emb_dim), int(Dz), max_len, int(min_len), int(eos),
+                         int(gen['emb_trans']), float(length_penalty), keep[0].shape[1],
+                         pv(keep[0]), pv(keep[1]), pv(keep[2]), pv(keep[3]), pv(keep[4]),
+                         pv(keep[5]), pv(keep[6]), pv(keep[7]), pv(keep[8]), pv(kb[0]),
+                         pv(keep[9]), pv(kb[1]), pv(keep[10]), pv(kb[2]), pv(keep[11]))
+    tokens = torch.empty(B, max_len, dtype=torch.int64, device=dev)
+    hl = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, dtype=torch.float64, device=dev)
+    aw = torch.empty(B, max_len, T, dtype=torch.float32, device=dev)
+    h0c = h0.contiguous().float() if h0 is not None else None
+    rc = getattr(N.lib(), 'asr_att_beam_decode')(
+        ctypes.byref(dims), ctypes.byref(opts), N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d),
+        N.ptr(h0c), N.ptr(ws), ws.numel(), N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw),
+        N.stream_handle(dev))
+    if rc == N.ASR_ERR_UNSUPPORTED:
+        return None
+    if rc != N.ASR_OK:
+        raise N.NativeError('asr_att_beam_decode failed (rc=%d): %s'
+                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
+    return tokens, hl, scores, aw
+
+
 _last_sampled = {'tok': None}
 
 

@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""Time attention beam search on the device (native_ops.att_decode_beam) beside
+the host path (ASR_ATT_BEAM=host: the per-step ops with the beam bookkeeping in
+numpy) on the same model and encoder output, on an MI355X.  Not part of
+bench.py.
+
+Shapes: B 32, 250 padded frames (lengths 150 .. 250), max_decode_len 100,
+encoder width 640, decoder 320, attention 128, bottleneck 256, embedding 64,
+10 x 201 location convolution; (W 4, V 29), (W 10, V 29), (W 10, V 10001).
+Random weights with the <eos> logit pushed down, so every search runs its 100
+steps on both paths.  One process; per shape and path: warm-up calls, then
+wall time around each call with a device synchronisation on both sides (the
+host path synchronises by itself at every step), median (min .. max).
+
+Writes profiles/att_beam_bench.txt (or --out).
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _time_ms(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times)), float(np.min(times)), float(np.max(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'att_beam_bench.txt'))
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--host_repeats', type=int, default=3)
+    ap.add_argument('--max_decode_len', type=int, default=100)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('att_beam_bench: needs an MI355X; a CPU run gives no time')
+    from pytorch_end2end_speech_recognition_amd import native_ops as ops
+    from pytorch_end2end_speech_recognition_amd.models.pytorch_v3.attention.attention_seq2seq \
+        import AttentionSeq2seq
+    ops.set_compute_dtype('fp32')
+    B, T, S = 32, 250, args.max_decode_len
+    rng = np.random.RandomState(0)
+    lens = np.sort(rng.randint(150, T + 1, B))[::-1].copy()
+    lens[0] = T
+    enc_np = rng.uniform(-1, 1, (B, T, 640)).astype(np.float32)
+    for b in range(B):
+        enc_np[b, lens[b]:] = 0
+    enc = torch.from_numpy(enc_np).cuda()
+    lines = ['# attention beam search, device path beside host path, MI355X; B %d, T %d (lengths '
+             '%d .. %d), max_decode_len %d; wall ms per call, median (min .. max) of %d device / '
+             '%d host calls after %d warm-up' % (B, T, lens.min(), lens.max(), S, args.repeats,
+                                                 args.host_repeats, args.warmup)]
+    for W, V in ((4, 29), (10, 29), (10, 10001)):
+        torch.manual_seed(V + W)
+        model = AttentionSeq2seq(
+            input_size=40, encoder_type='lstm', encoder_bidirectional=True, encoder_num_units=320,
+            encoder_num_proj=0, encoder_num_layers=1, attention_type='location',
+            attention_dim=128, decoder_type='lstm', decoder_num_units=320, decoder_num_layers=1,
+            embedding_dim=64, dropout_input=0, dropout_encoder=0, dropout_decoder=0,
+            dropout_embedding=0, num_classes=V - 1, subsample_list=[False],
+            init_dec_state='first', bottleneck_dim=256)
+        with torch.no_grad():
+            model.fc_0_fwd.fc.bias[V - 1] -= 30.0
+        model.set_cuda()
+        model.eval()
+
+        def run(mode):
+            os.environ['ASR_ATT_BEAM'] = mode
+            with torch.no_grad():
+                out = model._decode_infer_beam(enc, lens, W, S, 0, 0, 0)
+            assert ops.last_att_beam_path() == mode
+            return out
+
+        dev_t = _time_ms(lambda: run('device'), args.warmup, args.repeats)
+        host_t = _time_ms(lambda: run('host'), args.warmup, args.host_repeats)
+        hd, _ = run('device')
+        hh, _ = run('host')
+        same = sum(int(np.array_equal(a, b)) for a, b in zip(hd, hh))
+        lines.append('W %2d V %5d: device %.1f ms (%.1f .. %.1f), host %.1f ms (%.1f .. %.1f), '
+                     'host / device %.1fx; %d of %d hypotheses equal, mean length %.1f'
+                     % ((W, V) + dev_t + host_t +
+                        (host_t[0] / dev_t[0], same, B, float(np.mean([len(h) for h in hd])))))
+        del model
+    os.environ.pop('ASR_ATT_BEAM', None)
+    text = '\n'.join(lines) + '\n'
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        f.write(text)
+
+
+if __name__ == '__main__':
+    main()
