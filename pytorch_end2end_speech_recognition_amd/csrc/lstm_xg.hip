@@ -1073,8 +1073,13 @@ __global__ void __launch_bounds__(64 * NSW + R * XU + 64 * NPW) lstm_fwd_xgx(
 //     B2, then the f32 / bf16 dg stores and the next step's prefetch.
 //   XB / 4 MFMA waves: B1, B2, partial dh_{t-1}[rows][all units] = dg x (this
 //     block's 4 XB rows of W_hh) -> write-through granules.
-// A fragments (VGPRs): A[m][k] = W_hh[gaterow(k)][m] for output unit m (M block
-// mb = mw + (XB / 4) i) and local gate row k in [0, 4 XB): gate k / XB, unit u0 + k % XB.
+// A fragments (VGPRs): A[m][k] = W_hh[gaterow(k)][unit(m)] for local gate row k
+// in [0, 4 XB): gate k / XB, unit u0 + k % XB.  bf16: a wave owns adjacent M
+// block pairs pp = mw + (XB / 4) i (32 output units) with the rows permuted so
+// that a lane's C registers of the pair are 8 consecutive units: it publishes
+// two tagged granules as ONE 16-B store, the very 16 B one sweeper lane of the
+// consumer loads (8-B stores per block: twice the store instructions, and the
+// consumer's load complete only when two stores of different blocks had landed).
 //
 // F32 (reference-precision configs; XB = 16, f32 activations, f32 dG): the
 // partials of dh travel as f32 pairs (pg[par][grp][producer][row][H/2] u64 =
@@ -1535,22 +1540,35 @@ __global__ void __launch_bounds__(256 + R * XB + 64 * (F32 ? 4 : XB / 4)) lstm_b
     }
     return;
   }
-  bf16x8 wa[MB][NKS];
+  // Block pairs: wave mw owns the adjacent M blocks 2 pp, 2 pp + 1 of pair
+  // pp = mw + NMW i (32 output units), i < MP.  The pair's A rows are permuted:
+  // row m of half hf is unit 32 pp + 8 (m / 4) + 4 hf + m % 4, so that the C
+  // registers of lane group kq are units 32 pp + 8 kq .. + 3 (half 0) and
+  // + 4 .. + 7 (half 1) of row ln -- eight consecutive units, two granules, one
+  // 16-B store, which is exactly one consumer lane's 16-B sweep load.  Every
+  // C element is the same products summed in the same k order whatever row of
+  // the fragment its unit sits in.
+  constexpr int MP = (MB + 1) / 2;
+  const int NP = H / 32;                 // pairs (H % 32 == 0: xg_rows)
+  bf16x8 wa[MP][2][NKS];
   {
     const float* W = dir ? whh_r : whh_f;
 #pragma unroll
-    for (int i = 0; i < MB; ++i) {
-      const int mb = min(mw + NMW * i, HB - 1);
-      const int m = 16 * mb + ln;
+    for (int i = 0; i < MP; ++i) {
+      const int pp = min(mw + NMW * i, NP - 1);
 #pragma unroll
-      for (int kst = 0; kst < NKS; ++kst) {
-        u16x8 r;
+      for (int hf = 0; hf < 2; ++hf) {
+        const int m = 32 * pp + 8 * (ln >> 2) + 4 * hf + (ln & 3);
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-          const int k = 32 * kst + 8 * kq + jj;
-          r[jj] = f2bf(W[(long long)((k / XB) * H + u0 + (k % XB)) * H + m]);
+        for (int kst = 0; kst < NKS; ++kst) {
+          u16x8 r;
+#pragma unroll
+          for (int jj = 0; jj < 8; ++jj) {
+            const int k = 32 * kst + 8 * kq + jj;
+            r[jj] = f2bf(W[(long long)((k / XB) * H + u0 + (k % XB)) * H + m]);
+          }
+          wa[i][hf][kst] = as_bf16x8(r);
         }
-        wa[i][kst] = as_bf16x8(r);
       }
     }
   }
@@ -1566,44 +1584,52 @@ __global__ void __launch_bounds__(256 + R * XB + 64 * (F32 ? 4 : XB / 4)) lstm_b
       bfk[kst] = *reinterpret_cast<const bf16x8*>(&dgt[ln][32 * kst + 8 * kq]);
     const unsigned tb = tag_bit(q);
     const long long obase = (((long long)(q & 1) * G + grp) * WPG + mem) * R;
-    // block by block, one block of lag: the MFMA pair of block i is issued
-    // before block i - 1 is converted and stored, so the pair's latency hides
-    // behind the previous block's conversion (a block's MFMAs, convert and store
-    // back to back serialised the phase).  All MFMAs first and then the stores
-    // (every granule leaves in one burst) measured 0.7 ms / step slower at 5x512.
-    // Blocks past HB (wave-uniform) compute on a clamped fragment and store
-    // nothing.
-    f32x4 acc[MB];
+    // pair by pair, one pair of lag: the MFMAs of pair i are issued before
+    // pair i - 1 is converted and stored, so their latency hides behind the
+    // previous pair's conversion (a block's MFMAs, convert and store back to
+    // back serialised the phase).  All MFMAs first and then the stores (every
+    // granule leaves in one burst) measured 0.7 ms / step slower at 5x512.
+    // The pair's two accumulation chains are independent and alternate k-step
+    // by k-step.  Pairs past NP (wave-uniform) compute on a clamped fragment
+    // and store nothing.
+    f32x4 acc[MP][2];
     auto mm = [&](int i) {
-      acc[i] = mfma_bf16(wa[i][0], bfk[0], f32x4{0.f, 0.f, 0.f, 0.f});
+      acc[i][0] = mfma_bf16(wa[i][0][0], bfk[0], f32x4{0.f, 0.f, 0.f, 0.f});
+      acc[i][1] = mfma_bf16(wa[i][1][0], bfk[0], f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-      for (int kst = 1; kst < NKS; ++kst) acc[i] = mfma_bf16(wa[i][kst], bfk[kst], acc[i]);
+      for (int kst = 1; kst < NKS; ++kst) {
+        acc[i][0] = mfma_bf16(wa[i][0][kst], bfk[kst], acc[i][0]);
+        acc[i][1] = mfma_bf16(wa[i][1][kst], bfk[kst], acc[i][1]);
+      }
     };
-    // granule of (row ln, block mb): units 16 mb + 4 kq .. + 3
-    const unsigned off0 = (unsigned)(((obase + ln) * (long long)hq + 4 * mw + kq) * 8);
+    // two granules of (row ln, pair pp): units 32 pp + 8 kq .. + 7
+    const unsigned off0 = (unsigned)(((obase + ln) * (long long)hq + 8 * mw + 2 * kq) * 8);
     auto publish = [&](auto aux) {
       auto st = [&](int i) {
-        const int mb = mw + NMW * i;
-        if (ln < R && mb < HB) {  // C[m][n]: n = ln (row), m = 16 mb + 4 kq + r
-          // one granule: units 16 mb + 4 kq .. + 3, tag bit in the first value
-          const unsigned off = off0 + 32u * NMW * i;
+        const int pp = mw + NMW * i;
+        if (ln < R && pp < NP) {  // C[m][n]: n = ln (row); half hf, m = 4 kq + r: unit 32 pp + 8 kq + 4 hf + r
+          // both granules carry the tag bit in their first value: the whole
+          // 16 B a sweeper lane loads leaves in this one store
+          const unsigned off = off0 + 64u * NMW * i;
           // (packed v_cvt_pk_bf16_f32 conversions here, three VALU instead of
           // about twelve, measured 35 us / launch SLOWER in a same-box A/B)
-          const unsigned p01 = bf_with_lsb(acc[i][0], tb) | ((unsigned)f2bf(acc[i][1]) << 16);
-          const unsigned p23 = f2bf(acc[i][2]) | ((unsigned)f2bf(acc[i][3]) << 16);
-          const u32x2 v0 = {p01, p23};
-          __builtin_amdgcn_raw_buffer_store_b64(v0, rs, off, 0, decltype(aux)::value);
+          const unsigned a01 = bf_with_lsb(acc[i][0][0], tb) | ((unsigned)f2bf(acc[i][0][1]) << 16);
+          const unsigned a23 = f2bf(acc[i][0][2]) | ((unsigned)f2bf(acc[i][0][3]) << 16);
+          const unsigned b01 = bf_with_lsb(acc[i][1][0], tb) | ((unsigned)f2bf(acc[i][1][1]) << 16);
+          const unsigned b23 = f2bf(acc[i][1][2]) | ((unsigned)f2bf(acc[i][1][3]) << 16);
+          const u32x4 v0 = {a01, a23, b01, b23};
+          __builtin_amdgcn_raw_buffer_store_b128(v0, rs, off, 0, decltype(aux)::value);
         }
       };
       mm(0);
 #pragma unroll
-      for (int i = 1; i < MB; ++i) {
+      for (int i = 1; i < MP; ++i) {
         mm(i);
         __builtin_amdgcn_sched_barrier(0);
         st(i - 1);
         __builtin_amdgcn_sched_barrier(0);
       }
-      st(MB - 1);
+      st(MP - 1);
     };
     if (local)  // plain: into this XCD's L2
       publish(std::integral_constant<int, 0>());
