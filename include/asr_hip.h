@@ -272,15 +272,46 @@ int asr_colsum_accumulate_bf16(const uint16_t* g, long long ld, int M, int N, fl
  *   the persistent kernels as they go, for the bf16 weight-gradient GEMMs.
  * bf16 mode runs each pass as ONE persistent launch when the grid is
  *   co-resident (see lstm_persist.hip), else one launch per time step.
- */
+ * opts: the tagged-granule recurrence's settings for that call alone (NULL =
+ * all zero = the defaults).  Every call reads ws_prezeroed, the bf16 backward
+ * calls the pin and the units, asr_lstm_backward_dgbf_h alone the dy flags and
+ * the progress report; a value out of range is ASR_ERR_ARG before any launch.
+ *   ws_prezeroed: the workspace's leading asr_lstm_ws_zero_bytes(B, H) bytes
+ *     are already zero (native_ops.rec_arena_begin: one fill per training
+ *     step), so a tagged-granule launch skips its own memset.
+ *   bwd_pin_kb: the backward's dynamic-LDS pin, 0 (ASR_XG_PIN_BWD_KB, else
+ *     140) or KB in (80, 160].  At the default no kernel with more than 9 KB
+ *     of LDS -- every GEMM and convolution kernel -- can be co-resident with it.
+ *   bwd_units: hidden units per backward work-group, 0 (ASR_XG_BWD_XU, else
+ *     16), 16, or 32 -- half the work-groups, which leaves CUs to the layer
+ *     above's weight-gradient GEMMs (native_ops' ASR_OVERLAP_WGRAD mode 3).  32
+ *     only where H % 32 == 0, H <= 512 and 8 rows per group fit; else 16.
+ *   dy_flags, dy_c0 > 0, dy_epoch != 0 (flags NULL: off): dy is written
+ *     concurrently by the layer above's dX GEMMs (rnn.py:343-390's stacked
+ *     layers), in chunks of processing steps q in [c0 k, c0 (k + 1)) -- rows
+ *     t = q and t = T - 1 - q -- complete once flags[k] == epoch (up to the
+ *     middle step (T + 1) / 2 - 1); the recurrence waits for each chunk's flag.
+ *   progress, progress_q1 >= 0, progress_q2 (NULL: off): the launch adds 1 to
+ *     *progress per cell wave once the gate gradients of processing steps
+ *     <= q1 are stored and released at agent scope, and again at q2 > q1
+ *     (q2 < 0: one step).  Step q covers t = T-1-q (forward direction) and
+ *     t = q (reverse): rows t in [T-1-q, q] of dG are final once q >= T/2. */
+typedef struct {
+  int ws_prezeroed, bwd_pin_kb, bwd_units;
+  const int* dy_flags;
+  int dy_c0, dy_epoch;
+  unsigned long long* progress;
+  int progress_q1, progress_q2;
+} asr_lstm_opts_t;
 size_t asr_lstm_workspace_bytes(int B, int H, int compute_dtype, int backward);
 int asr_lstm_forward(float* gx_act, const void* whh_f, const void* whh_r, int w_dtype,
                      const int32_t* lens, int B, int T, int H, int compute_dtype, float* y,
-                     float* cst, uint16_t* ybf, void* workspace, size_t ws_bytes, void* stream);
+                     float* cst, uint16_t* ybf, void* workspace, size_t ws_bytes, void* stream,
+                     const asr_lstm_opts_t* opts);
 int asr_lstm_backward(const float* dy, const void* whh_f, const void* whh_r, int w_dtype,
                       const int32_t* lens, int B, int T, int H, int compute_dtype, float* act_dg,
                       const float* cst, uint16_t* dgbf, void* workspace, size_t ws_bytes,
-                      void* stream);
+                      void* stream, const asr_lstm_opts_t* opts);
 /* asr_lstm_backward plus the bias gradients of nn.LSTM's bias_ih / bias_hh
  * (both [2 dirs x 4H], accumulated +=, identical values: both biases feed the
  * same gate pre-activation, rnn.py:166-172).  The tagged-granule recurrence
@@ -289,7 +320,8 @@ int asr_lstm_backward(const float* dy, const void* whh_f, const void* whh_r, int
 int asr_lstm_backward_db(const float* dy, const void* whh_f, const void* whh_r, int w_dtype,
                          const int32_t* lens, int B, int T, int H, int compute_dtype,
                          float* act_dg, const float* cst, uint16_t* dgbf, float* db_ih,
-                         float* db_hh, void* workspace, size_t ws_bytes, void* stream);
+                         float* db_hh, void* workspace, size_t ws_bytes, void* stream,
+                         const asr_lstm_opts_t* opts);
 /* asr_lstm_backward_db for a caller that feeds only the bf16 gate gradients
  * (dgbf, required) to its weight / input gradient GEMMs: the tagged-granule
  * recurrence skips the f32 dG stores and act_dg's contents are unspecified on
@@ -297,7 +329,8 @@ int asr_lstm_backward_db(const float* dy, const void* whh_f, const void* whh_r, 
 int asr_lstm_backward_dgbf(const float* dy, const void* whh_f, const void* whh_r, int w_dtype,
                            const int32_t* lens, int B, int T, int H, int compute_dtype,
                            float* act_dg, const float* cst, uint16_t* dgbf, float* db_ih,
-                           float* db_hh, void* workspace, size_t ws_bytes, void* stream);
+                           float* db_hh, void* workspace, size_t ws_bytes, void* stream,
+                           const asr_lstm_opts_t* opts);
 
 /* Forward layer pass with the input projection fused into the persistent
  * recurrence (bf16 mode; replaces asr_gemm(gx = x W_ih^T + b_ih + b_hh) +
@@ -310,7 +343,8 @@ int asr_lstm_backward_dgbf(const float* dy, const void* whh_f, const void* whh_r
 int asr_lstm_forward_x(const uint16_t* x, int Din, const uint16_t* wih, const float* b_ih,
                        const float* b_hh, const float* whh_f, const float* whh_r,
                        const int32_t* lens, int B, int T, int H, float* act, float* y, float* cst,
-                       uint16_t* ybf, void* workspace, size_t ws_bytes, void* stream);
+                       uint16_t* ybf, void* workspace, size_t ws_bytes, void* stream,
+                       const asr_lstm_opts_t* opts);
 int asr_lstm_forward_x_ok(int B, int H, int Din);
 /* asr_lstm_forward_x with the gate activations stored packed as fp16:
  * act_h [B][T][2][H][4] (i, f, g, o of one (utterance, frame, direction,
@@ -322,7 +356,7 @@ int asr_lstm_forward_xh(const uint16_t* x, int Din, const uint16_t* wih, const f
                         const float* b_hh, const float* whh_f, const float* whh_r,
                         const int32_t* lens, int B, int T, int H, uint16_t* act_h, float* y,
                         float* cst, uint16_t* ybf, void* workspace, size_t ws_bytes,
-                        void* stream);
+                        void* stream, const asr_lstm_opts_t* opts);
 /* asr_lstm_forward_xh for a layer whose output feeds only the next BLSTM
  * layer's staged bf16 input (the stacked nn.LSTM layers of
  * models/pytorch_v3/encoders/rnn.py:343-390 with dropout between them,
@@ -335,14 +369,14 @@ int asr_lstm_forward_xh_drop(const uint16_t* x, int Din, const uint16_t* wih, co
                              const int32_t* lens, int B, int T, int H, uint16_t* act_h,
                              float* y, float* cst, uint16_t* ybf, uint16_t* ydrop, float drop_p,
                              unsigned long long drop_seed, void* workspace, size_t ws_bytes,
-                             void* stream);
+                             void* stream, const asr_lstm_opts_t* opts);
 /* asr_lstm_backward_dgbf reading act_h of asr_lstm_forward_xh (tagged-granule
  * recurrence only; ASR_ERR_UNSUPPORTED otherwise).  Same workspace. */
 int asr_lstm_backward_dgbf_h(const float* dy, const void* whh_f, const void* whh_r, int w_dtype,
                              const int32_t* lens, int B, int T, int H, int compute_dtype,
                              const uint16_t* act_h, const float* cst, uint16_t* dgbf,
                              float* db_ih, float* db_hh, void* workspace, size_t ws_bytes,
-                             void* stream);
+                             void* stream, const asr_lstm_opts_t* opts);
 int asr_lstm_unpack_act_h(const uint16_t* act_h, int B, int T, int H, float* act, void* stream);
 /* Diagnostics only (tools/buckets_diag.py, ASR_DIAG_SPIN): nwg work-groups of
  * 256 threads that fill 64 KB of LDS with a pattern and check it `iters`
@@ -1012,53 +1046,18 @@ int asr_lstm_last_path(int* out2);
  * per-step phase timestamps of work-groups 0..63 (64 x 128 steps x 12 u64) to
  * `host` (may be NULL); returns the element count, 0 when tracing is off. */
 long long asr_xg_trace_read(unsigned long long* host);
-/* The persistent backward recurrence's dynamic-LDS pin (KB, in (80, 160]; 0 =
- * ASR_XG_PIN_BWD_KB or the 140 KB default) for the launches that follow.  At
- * the default no kernel with more than 9 KB of LDS -- every GEMM and
- * convolution kernel -- can be co-resident with it. */
-int asr_lstm_set_bwd_pin_kb(int kb);
-/* Hidden units per work-group of the tagged-granule backward recurrence for the
- * launches that follow: 0 (ASR_XG_BWD_XU, else 16), 16, or 32 -- half the
- * work-groups, so a layer of 2 x 8 rows x 512 units takes 128 of 256 CUs and
- * the weight-gradient GEMMs of the layer above run beside it (native_ops'
- * ASR_OVERLAP_WGRAD mode 3).  32 applies only where H % 32 == 0, H <= 512 and
- * 8 rows per group fit; elsewhere 16 is used. */
-int asr_lstm_set_bwd_units(int xu);
-/* Work-groups that backward recurrence launches for [B, *, H] with xu units per
- * work-group (0: the current setting); 0 if the shape cannot take that path. */
+/* Work-groups the tagged-granule backward recurrence launches for [B, *, H]
+ * with xu units per work-group (0: ASR_XG_BWD_XU, else 16; 16; 32 where the
+ * shape supports it); 0 if the shape cannot take that path. */
 int asr_lstm_backward_grid(int B, int H, int xu);
-/* Pipelined input gradients (the layer above's dX GEMMs overlapping this
- * layer's backward recurrence, rnn.py:343-390's stacked layers): dy of the
- * asr_lstm_backward_dgbf_h launches that follow is written concurrently, in
- * chunks of processing steps q in [c0 k, c0 (k + 1)) -- rows t = q and
- * t = T - 1 - q -- complete once flags[k] == epoch (chunks up to the middle
- * step (T + 1) / 2 - 1).  The recurrence
- * waits for each chunk's flag before reading its dy rows.  flags NULL: off. */
-int asr_lstm_set_dy_flags(const int* flags, int c0, int epoch);
-
-/* Split input gradient (round 6): the next asr_lstm_backward_dgbf_h launch
- * adds 1 to *counter per cell wave once the gate gradients of processing steps
- * <= q are stored and released at agent scope (NULL: off; applies to launches
- * from the calling host thread until reset).  asr_lstm_bwd_progress_arrivals:
- * what one launch of [B, *, H] adds.  asr_lstm_progress_gate enqueues a wait
- * on another stream until *counter >= target (bounded; a timeout sets the
- * recurrence status word, so the step is skipped).  Processing step q covers
- * t = T-1-q (forward direction) and t = q (reverse): rows t in [T-1-q, q] of
- * dG are final once q >= T/2. */
-int asr_lstm_set_bwd_progress(unsigned long long* counter, int q);
-/* Two reporting steps q1 < q2 (round 6, the two-chunk split): one launch's
- * arrivals are added at each. */
-int asr_lstm_set_bwd_progress2(unsigned long long* counter, int q1, int q2);
-long long asr_lstm_bwd_progress_arrivals(int B, int H);
+/* Arrivals a launch with opts->bwd_units = xu adds to opts->progress at each
+ * reporting step, 0 if the shape cannot take that path.  asr_lstm_progress_gate
+ * enqueues a wait on `stream` until *counter >= target, the running total (bounded; a
+ * timeout sets the recurrence status word, so the step is skipped). */
+long long asr_lstm_bwd_progress_arrivals(int B, int H, int xu);
 int asr_lstm_progress_gate(const unsigned long long* counter, long long target, void* stream);
-/* Per-step workspace arena (round 6): the workspace handed to the next
- * tagged-granule launch from this host thread is already zero (on = 1), so
- * the launch skips its own memset.  Consumed by that launch; reset it after
- * the call.  Replaces asr_lstm_workspace_bytes' "zeroed before every launch"
- * with one fill per training step (native_ops.rec_arena_begin). */
-int asr_lstm_ws_prezeroed(int on);
-/* Leading bytes of such a workspace a tagged-granule launch of [B, *, H]
- * zeroes (the arena clears only these). */
+/* Leading bytes of a recurrence workspace a tagged-granule launch of [B, *, H]
+ * zeroes (what opts->ws_prezeroed promises; the arena clears only these). */
 size_t asr_lstm_ws_zero_bytes(int B, int H);
 /* Stream-ordered: flags[k] = epoch after the work enqueued before it. */
 int asr_lstm_dy_signal(int* flags, int k, int epoch, void* stream);

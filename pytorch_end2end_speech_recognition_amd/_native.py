@@ -80,24 +80,25 @@ SIGNATURES = {
     'asr_conv3x3_c1_forward': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                        c_vp, c_vp]),
     'asr_lstm_workspace_bytes': (c_size, [c_int, c_int, c_int, c_int]),
+    # the eight BLSTM layer entry points end in (..., stream, opts: LstmOpts* or NULL)
     'asr_lstm_forward': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
-                                 c_vp, c_vp, c_vp, c_size, c_vp]),
+                                 c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_backward': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
-                                  c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                  c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_backward_db': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
-                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_backward_dgbf': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
-                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_forward_x': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
-                                   c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                   c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_forward_x_ok': (c_int, [c_int, c_int, c_int]),
     'asr_lstm_forward_xh': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
-                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_forward_xh_drop': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
                                          c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_float,
-                                         ctypes.c_ulonglong, c_vp, c_size, c_vp]),
+                                         ctypes.c_ulonglong, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_backward_dgbf_h': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
-                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_diag_lds_spin': (c_int, [c_int, c_int, c_vp, c_vp]),
     'asr_diag_hold_cus': (c_int, [c_int, c_int, c_int, c_vp]),
     'asr_lstm_unpack_act_h': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
@@ -232,17 +233,11 @@ SIGNATURES = {
     'asr_gemm_last_family': (c_int, []),
     'asr_attdec_set_conv_feat': (c_int, [c_vp]),
     'asr_attdec_conv_feat_bytes': (c_size, [c_vp]),
-    'asr_lstm_set_bwd_progress': (c_int, [c_vp, c_int]),
-    'asr_lstm_set_bwd_progress2': (c_int, [c_vp, c_int, c_int]),
-    'asr_lstm_ws_prezeroed': (c_int, [c_int]),
     'asr_lstm_ws_zero_bytes': (c_size, [c_int, c_int]),
-    'asr_lstm_bwd_progress_arrivals': (c_ll, [c_int, c_int]),
+    'asr_lstm_bwd_progress_arrivals': (c_ll, [c_int, c_int, c_int]),
     'asr_lstm_progress_gate': (c_int, [c_vp, c_ll, c_vp]),
     'asr_xg_trace_read': (c_ll, [c_vp]),
     'asr_lstm_debug_dh': (c_int, [c_vp, c_vp, c_vp, c_vp]),
-    'asr_lstm_set_bwd_pin_kb': (c_int, [c_int]),
-    'asr_lstm_set_bwd_units': (c_int, [c_int]),
-    'asr_lstm_set_dy_flags': (c_int, [c_vp, c_int, c_int]),
     'asr_lstm_dy_signal': (c_int, [c_vp, c_int, c_int, c_vp]),
     'asr_lstm_backward_grid': (c_int, [c_int, c_int, c_int]),
 }
@@ -283,6 +278,13 @@ class AttDecOpts(ctypes.Structure):
                 ('drop_emb', c_float), ('seed_emb', ctypes.c_ulonglong), ('w_ih_emb', c_vp),
                 ('ld_ih', c_ll), ('b_ih', c_vp), ('b_hh', c_vp), ('pre_ss', c_vp),
                 ('emb_ss', c_vp), ('tok_ss', c_vp), ('d_pre', c_vp), ('dg_ss', c_vp)]
+
+
+class LstmOpts(ctypes.Structure):
+    """asr_lstm_opts_t (one recurrence call's launch settings; all zero: the defaults)"""
+    _fields_ = [('ws_prezeroed', c_int), ('bwd_pin_kb', c_int), ('bwd_units', c_int),
+                ('dy_flags', c_vp), ('dy_c0', c_int), ('dy_epoch', c_int), ('progress', c_vp),
+                ('progress_q1', c_int), ('progress_q2', c_int)]
 
 
 class AttBeamOpts(ctypes.Structure):

@@ -42,20 +42,21 @@ size_t lstm_xg_fwd_bytes(int B, int H);
 size_t lstm_xg_bwd_bytes(int B, int H);
 int lstm_fwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                        const float* whh_r, float* gx_act, float* y, float* cst, void* ws,
-                       uint16_t* ybf, hipStream_t s, bool dry);
+                       uint16_t* ybf, hipStream_t s, bool dry, bool prezeroed);
 int lstm_bwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                        const float* whh_r, const float* dy, float* act_dg, const float* cst,
                        void* ws, uint16_t* dgbf, float* dbpart, hipStream_t s, bool dry,
-                       bool dg_f32, const uint16_t* acth = nullptr);
+                       bool dg_f32, const asr_lstm_opts_t& o, const uint16_t* acth = nullptr);
 // the same hand-off at reference precision (f32 granules, f32 MFMA)
 size_t lstm_xg32_fwd_bytes(int B, int H);
 size_t lstm_xg32_bwd_bytes(int B, int H);
 int lstm_fwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                          const float* whh_r, float* gx_act, float* y, float* cst, void* ws,
-                         hipStream_t s, bool dry);
+                         hipStream_t s, bool dry, bool prezeroed);
 int lstm_bwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                          const float* whh_r, const float* dy, float* act_dg, const float* cst,
-                         void* ws, float* dbpart, hipStream_t s, bool dry);
+                         void* ws, float* dbpart, hipStream_t s, bool dry,
+                         const asr_lstm_opts_t& o);
 
 namespace {
 
@@ -568,7 +569,7 @@ extern "C" size_t asr_lstm_workspace_bytes(int B, int H, int compute_dtype, int 
 extern "C" int asr_lstm_forward(float* gx_act, const void* whh_f, const void* whh_r, int w_dtype,
                                 const int32_t* lens, int B, int T, int H, int compute_dtype,
                                 float* y, float* cst, uint16_t* ybf, void* workspace,
-                                size_t ws_bytes, void* stream) {
+                                size_t ws_bytes, void* stream, const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(gx_act && whh_f && whh_r && lens && y && cst && workspace, ASR_ERR_ARG,
               "lstm_forward: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0, ASR_ERR_ARG, "lstm_forward: bad shape");
@@ -576,6 +577,7 @@ extern "C" int asr_lstm_forward(float* gx_act, const void* whh_f, const void* wh
               "lstm_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const bool bf = compute_dtype == ASR_DT_BF16;
+  const bool pz = opts && opts->ws_prezeroed;
   int* ctr = (int*)workspace;
   void* hbuf = (char*)workspace + fwd_ctr_bytes(B);
   const int vec = (H % 8 == 0) ? 1 : 0;
@@ -583,22 +585,22 @@ extern "C" int asr_lstm_forward(float* gx_act, const void* whh_f, const void* wh
   ASR_REQUIRE(bf || w_dtype == ASR_DT_F32, ASR_ERR_ARG, "lstm_forward: f32 compute needs f32 W");
   if (bf && w_dtype == ASR_DT_F32 &&
       lstm_fwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, gx_act, y, cst,
-                         workspace, ybf, s, true) == 1) {
+                         workspace, ybf, s, true, pz) == 1) {
     // one persistent launch, tagged-granule hand-off (lstm_xg.hip)
     const int slot = prof_begin_launch(ASR_PROF_LSTM_FWD_SEQ, s, 0.0, ASR_PTAG_LSTM_FWD_XG);
     const int rc = lstm_fwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r,
-                                      gx_act, y, cst, workspace, ybf, s, false);
+                                      gx_act, y, cst, workspace, ybf, s, false, pz);
     ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_forward: tagged-granule launch failed");
     prof_end_launch(ASR_PROF_LSTM_FWD_SEQ, slot, s);
     g_lstm_last_path[0] = 1;
     return ASR_OK;
   }
   if (!bf && lstm_fwd_xg32_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, gx_act,
-                                  y, cst, workspace, s, true) == 1) {
+                                  y, cst, workspace, s, true, pz) == 1) {
     // reference precision: the same persistent hand-off with f32 granules
     const int slot = prof_begin_launch(ASR_PROF_LSTM_FWD_SEQ, s, 0.0, ASR_PTAG_LSTM_FWD_XG);
     const int rc = lstm_fwd_xg32_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r,
-                                        gx_act, y, cst, workspace, s, false);
+                                        gx_act, y, cst, workspace, s, false, pz);
     ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_forward: f32 tagged-granule launch failed");
     prof_end_launch(ASR_PROF_LSTM_FWD_SEQ, slot, s);
     g_lstm_last_path[0] = 2;
@@ -674,12 +676,44 @@ extern "C" int asr_lstm_forward(float* gx_act, const void* whh_f, const void* wh
   return ASR_OK;
 }
 
+// The opts of a backward entry point as the launchers read them (NULL: the
+// defaults), checked.  Only the packed-activation backward reads the dy flags
+// and the progress report.
+static int lstm_bwd_opts(const asr_lstm_opts_t* opts, bool packed, asr_lstm_opts_t* o) {
+  *o = asr_lstm_opts_t{0, 0, 0, nullptr, 16, 0, nullptr, -1, -1};
+  if (!opts) return ASR_OK;
+  const int kb = opts->bwd_pin_kb, xu = opts->bwd_units;
+  ASR_REQUIRE(kb == 0 || (kb > 80 && kb <= 160), ASR_ERR_ARG, "lstm pin: %d KB", kb);
+  ASR_REQUIRE(xu == 0 || xu == 16 || xu == 32, ASR_ERR_ARG, "lstm units: %d", xu);
+  o->ws_prezeroed = opts->ws_prezeroed;
+  o->bwd_pin_kb = kb;
+  o->bwd_units = xu;
+  if (packed && opts->dy_flags) {
+    ASR_REQUIRE(opts->dy_c0 > 0 && opts->dy_epoch != 0, ASR_ERR_ARG, "dy flags: c0 %d epoch %d",
+                opts->dy_c0, opts->dy_epoch);
+    o->dy_flags = opts->dy_flags;
+    o->dy_c0 = opts->dy_c0;
+    o->dy_epoch = opts->dy_epoch;
+  }
+  if (packed && opts->progress) {
+    const int q1 = opts->progress_q1, q2 = opts->progress_q2;
+    ASR_REQUIRE(q1 >= 0 && (q2 < 0 || q2 > q1), ASR_ERR_ARG, "bwd progress: q %d, %d", q1, q2);
+    o->progress = opts->progress;
+    o->progress_q1 = q1;
+    o->progress_q2 = q2 < 0 ? -1 : q2;
+  }
+  return ASR_OK;
+}
+
 static int lstm_backward_impl(const float* dy, const void* whh_f, const void* whh_r,
                               int w_dtype, const int32_t* lens, int B, int T, int H,
                               int compute_dtype, float* act_dg, const float* cst,
                               uint16_t* dgbf, float* dbpart, void* workspace, size_t ws_bytes,
-                              void* stream, bool* fused_bias, bool dg_f32 = true) {
+                              void* stream, const asr_lstm_opts_t* opts, bool* fused_bias,
+                              bool dg_f32 = true) {
   *fused_bias = false;
+  asr_lstm_opts_t o;
+  if (const int rc = lstm_bwd_opts(opts, false, &o)) return rc;
   ASR_REQUIRE(whh_f && whh_r && lens && act_dg && cst && workspace, ASR_ERR_ARG,
               "lstm_backward: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0, ASR_ERR_ARG, "lstm_backward: bad shape");
@@ -689,10 +723,10 @@ static int lstm_backward_impl(const float* dy, const void* whh_f, const void* wh
   const bool bf = compute_dtype == ASR_DT_BF16;
   if (bf && w_dtype == ASR_DT_F32 &&
       lstm_bwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy, act_dg, cst,
-                         workspace, dgbf, dbpart, s, true, dg_f32) == 1) {
+                         workspace, dgbf, dbpart, s, true, dg_f32, o) == 1) {
     const int slot = prof_begin_launch(ASR_PROF_LSTM_BWD_SEQ, s, 0.0, ASR_PTAG_LSTM_BWD_XG);
     const int rc = lstm_bwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy,
-                                      act_dg, cst, workspace, dgbf, dbpart, s, false, dg_f32);
+                                      act_dg, cst, workspace, dgbf, dbpart, s, false, dg_f32, o);
     ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_backward: tagged-granule launch failed");
     prof_end_launch(ASR_PROF_LSTM_BWD_SEQ, slot, s);
     *fused_bias = dbpart != nullptr;
@@ -701,10 +735,10 @@ static int lstm_backward_impl(const float* dy, const void* whh_f, const void* wh
   }
   if (!bf && w_dtype == ASR_DT_F32 && dg_f32 &&
       lstm_bwd_xg32_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy, act_dg, cst,
-                           workspace, dbpart, s, true) == 1) {
+                           workspace, dbpart, s, true, o) == 1) {
     const int slot = prof_begin_launch(ASR_PROF_LSTM_BWD_SEQ, s, 0.0, ASR_PTAG_LSTM_BWD_XG);
     const int rc = lstm_bwd_xg32_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy,
-                                        act_dg, cst, workspace, dbpart, s, false);
+                                        act_dg, cst, workspace, dbpart, s, false, o);
     ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_backward: f32 tagged-granule launch failed");
     prof_end_launch(ASR_PROF_LSTM_BWD_SEQ, slot, s);
     *fused_bias = dbpart != nullptr;
@@ -795,10 +829,10 @@ extern "C" int asr_lstm_backward(const float* dy, const void* whh_f, const void*
                                  int w_dtype, const int32_t* lens, int B, int T, int H,
                                  int compute_dtype, float* act_dg, const float* cst,
                                  uint16_t* dgbf, void* workspace, size_t ws_bytes,
-                                 void* stream) {
+                                 void* stream, const asr_lstm_opts_t* opts) {
   bool fused = false;
   return lstm_backward_impl(dy, whh_f, whh_r, w_dtype, lens, B, T, H, compute_dtype, act_dg, cst,
-                            dgbf, nullptr, workspace, ws_bytes, stream, &fused);
+                            dgbf, nullptr, workspace, ws_bytes, stream, opts, &fused);
 }
 
 // asr_lstm_backward plus the bias gradients: db_ih[n] += sum_{b,t} dG[b][t][n] and
@@ -809,7 +843,8 @@ static int lstm_backward_db_impl(const float* dy, const void* whh_f, const void*
                                  int w_dtype, const int32_t* lens, int B, int T, int H,
                                  int compute_dtype, float* act_dg, const float* cst,
                                  uint16_t* dgbf, float* db_ih, float* db_hh, void* workspace,
-                                 size_t ws_bytes, void* stream, bool dg_f32) {
+                                 size_t ws_bytes, void* stream, const asr_lstm_opts_t* opts,
+                                 bool dg_f32) {
   ASR_REQUIRE(db_ih, ASR_ERR_ARG, "lstm_backward_db: null bias gradient");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0, ASR_ERR_ARG, "lstm_backward_db: bad shape");
   ASR_REQUIRE(ws_bytes >= bwd_ws_bias(B, H, compute_dtype), ASR_ERR_WORKSPACE,
@@ -817,8 +852,8 @@ static int lstm_backward_db_impl(const float* dy, const void* whh_f, const void*
   float* part = (float*)((char*)workspace + bias_ws_off(B, H, compute_dtype));
   bool fused = false;
   const int rc = lstm_backward_impl(dy, whh_f, whh_r, w_dtype, lens, B, T, H, compute_dtype,
-                                    act_dg, cst, dgbf, part, workspace, ws_bytes, stream, &fused,
-                                    dg_f32);
+                                    act_dg, cst, dgbf, part, workspace, ws_bytes, stream, opts,
+                                    &fused, dg_f32);
   if (rc != ASR_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int N = 8 * H;
@@ -837,9 +872,9 @@ extern "C" int asr_lstm_backward_db(const float* dy, const void* whh_f, const vo
                                     int w_dtype, const int32_t* lens, int B, int T, int H,
                                     int compute_dtype, float* act_dg, const float* cst,
                                     uint16_t* dgbf, float* db_ih, float* db_hh, void* workspace,
-                                    size_t ws_bytes, void* stream) {
+                                    size_t ws_bytes, void* stream, const asr_lstm_opts_t* opts) {
   return lstm_backward_db_impl(dy, whh_f, whh_r, w_dtype, lens, B, T, H, compute_dtype, act_dg,
-                               cst, dgbf, db_ih, db_hh, workspace, ws_bytes, stream, true);
+                               cst, dgbf, db_ih, db_hh, workspace, ws_bytes, stream, opts, true);
 }
 
 // asr_lstm_backward_dgbf reading the packed fp16 gate activations of
@@ -851,7 +886,8 @@ extern "C" int asr_lstm_backward_dgbf_h(const float* dy, const void* whh_f, cons
                                         int w_dtype, const int32_t* lens, int B, int T, int H,
                                         int compute_dtype, const uint16_t* act_h, const float* cst,
                                         uint16_t* dgbf, float* db_ih, float* db_hh,
-                                        void* workspace, size_t ws_bytes, void* stream) {
+                                        void* workspace, size_t ws_bytes, void* stream,
+                                        const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(whh_f && whh_r && lens && act_h && cst && dgbf && db_ih && workspace, ASR_ERR_ARG,
               "lstm_backward_dgbf_h: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0, ASR_ERR_ARG, "lstm_backward_dgbf_h: bad shape");
@@ -859,14 +895,16 @@ extern "C" int asr_lstm_backward_dgbf_h(const float* dy, const void* whh_f, cons
               "lstm_backward_dgbf_h: bf16 compute with f32 W_hh only");
   ASR_REQUIRE(ws_bytes >= bwd_ws_bias(B, H, compute_dtype), ASR_ERR_WORKSPACE,
               "lstm_backward_dgbf_h: workspace too small");
+  asr_lstm_opts_t o;
+  if (const int rc = lstm_bwd_opts(opts, true, &o)) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)((char*)workspace + bias_ws_off(B, H, compute_dtype));
   if (lstm_bwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy, nullptr, cst,
-                         workspace, dgbf, part, s, true, false, act_h) != 1)
+                         workspace, dgbf, part, s, true, false, o, act_h) != 1)
     return ASR_ERR_UNSUPPORTED;
   const int slot = prof_begin_launch(ASR_PROF_LSTM_BWD_SEQ, s, 0.0, ASR_PTAG_LSTM_BWD_XG);
   const int rc = lstm_bwd_xg_launch(B, T, H, lens, (const float*)whh_f, (const float*)whh_r, dy,
-                                    nullptr, cst, workspace, dgbf, part, s, false, false, act_h);
+                                    nullptr, cst, workspace, dgbf, part, s, false, false, o, act_h);
   ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_backward_dgbf_h: tagged-granule launch failed");
   prof_end_launch(ASR_PROF_LSTM_BWD_SEQ, slot, s);
   g_lstm_last_path[1] = 1;
@@ -884,10 +922,11 @@ extern "C" int asr_lstm_backward_dgbf(const float* dy, const void* whh_f, const 
                                       int w_dtype, const int32_t* lens, int B, int T, int H,
                                       int compute_dtype, float* act_dg, const float* cst,
                                       uint16_t* dgbf, float* db_ih, float* db_hh, void* workspace,
-                                      size_t ws_bytes, void* stream) {
+                                      size_t ws_bytes, void* stream,
+                                      const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(dgbf, ASR_ERR_ARG, "lstm_backward_dgbf: null dgbf");
   const char* e = getenv("ASR_XG_DG_F32");
   const bool keep = e && e[0] == '1';
   return lstm_backward_db_impl(dy, whh_f, whh_r, w_dtype, lens, B, T, H, compute_dtype, act_dg,
-                               cst, dgbf, db_ih, db_hh, workspace, ws_bytes, stream, keep);
+                               cst, dgbf, db_ih, db_hh, workspace, ws_bytes, stream, opts, keep);
 }

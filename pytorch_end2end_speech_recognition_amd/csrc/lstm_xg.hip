@@ -89,9 +89,9 @@ constexpr size_t XG_PIN_BWD = 140 * 1024;
 // value above 80 KB still keeps one work-group per CU; 96 leaves 64 KB beside
 // it, room for one 128 x 128 GEMM work-group (the co-resident weight-gradient
 // mode of native_ops, ASR_OVERLAP_WGRAD=2).
-int g_pin_bwd_kb = 0;   // asr_lstm_set_bwd_pin_kb (0: ASR_XG_PIN_BWD_KB or the default)
-size_t xg_pin_bwd() {
-  if (g_pin_bwd_kb > 80 && g_pin_bwd_kb <= 160) return (size_t)g_pin_bwd_kb * 1024;
+// pin_kb: the call's asr_lstm_opts_t.bwd_pin_kb (0: ASR_XG_PIN_BWD_KB or the default).
+size_t xg_pin_bwd(int pin_kb) {
+  if (pin_kb) return (size_t)pin_kb * 1024;
   const char* e = getenv("ASR_XG_PIN_BWD_KB");
   const int kb = e ? atoi(e) : 0;
   static bool warned = false;
@@ -103,12 +103,10 @@ size_t xg_pin_bwd() {
   return (kb > 80 && kb <= 160) ? (size_t)kb * 1024 : XG_PIN_BWD;
 }
 
-// Units per backward work-group (lstm_bwd_xg's XB): asr_lstm_set_bwd_units, else
+// Units per backward work-group (lstm_bwd_xg's XB): the call's bwd_units, else
 // ASR_XG_BWD_XU, else 16.  32 only where it is supported: H % 32 == 0, R = 8 and
 // at most 32 A fragments per MFMA lane (H <= 512).
-int g_bwd_xu = 0;
-int xg_bwd_xu(int R, int H) {
-  int xu = g_bwd_xu;
+int xg_bwd_xu(int xu, int R, int H) {
   if (!xu) {
     const char* e = getenv("ASR_XG_BWD_XU");
     xu = e ? atoi(e) : 16;
@@ -116,19 +114,6 @@ int xg_bwd_xu(int R, int H) {
   if (xu == 32 && R == 8 && H % 32 == 0 && (H / 16 + 3) / 4 <= 8) return 32;
   return 16;
 }
-
-// asr_lstm_set_dy_flags: dy of the next packed-activation backward launch
-// arrives chunk by chunk (see lstm_bwd_xg's sweepers); NULL = off.
-const int* g_dyflag = nullptr;
-// asr_lstm_set_bwd_progress: the next packed-activation backward launch reports
-// when the gate gradients of processing steps <= g_prog_q are stored (every
-// cell wave adds 1 to *g_prog_ctr after a release), so the input-gradient GEMM
-// of the rows complete by then can start beside the rest of the pass.
-unsigned long long* g_prog_ctr = nullptr;
-int g_prog_q = -1;
-int g_prog_q2 = -1;   // a second reporting step (asr_lstm_set_bwd_progress2), -1: none
-int g_dyc0 = 16;
-unsigned g_dyepoch = 0;
 
 // The backward's pin leaves no room for the kernel's static LDS: the layer
 // would silently take the slower counter-form recurrence -- say so once.
@@ -1683,17 +1668,11 @@ void xg_trace_setup(hipStream_t s);
 
 constexpr size_t XG_HDR = 256;  // abort word + placement registry, zeroed with the granules
 
-// The caller's workspace is already zero (a per-step arena cleared by one fill
-// for every layer pass, native_ops.rec_arena_begin): the next launch skips its
-// own memset.  Thread-local like the other per-call settings.
-thread_local int g_ws_zeroed = 0;
-
-hipError_t xg_ws_clear(void* ws, size_t n, hipStream_t s) {
-  if (g_ws_zeroed) {
-    g_ws_zeroed = 0;
-    return hipSuccess;
-  }
-  return hipMemsetAsync(ws, 0, n, s);
+// prezeroed (the call's ws_prezeroed): the caller's workspace is already zero
+// (a per-step arena cleared by one fill for every layer pass,
+// native_ops.rec_arena_begin), so the launch skips its own memset.
+hipError_t xg_ws_clear(void* ws, size_t n, hipStream_t s, bool prezeroed) {
+  return prezeroed ? hipSuccess : hipMemsetAsync(ws, 0, n, s);
 }
 
 unsigned xg_next_epoch() {
@@ -1781,7 +1760,7 @@ bool xg32_shape_ok(int H, bool backward) { return H % 64 == 0 && H <= (backward 
 // Reference-precision (f32) forward: 1 launched / eligible (dry), 0 not, -1 error.
 int lstm_fwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                          const float* whh_r, float* gx_act, float* y, float* cst, void* ws,
-                         hipStream_t s, bool dry) {
+                         hipStream_t s, bool dry, bool prezeroed) {
   if (!xg_enabled()) return 0;
   const char* e = getenv("ASR_LSTM_XG32");
   if (e && e[0] == '0') return 0;
@@ -1797,7 +1776,7 @@ int lstm_fwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* 
   do {                                                                                           \
     if (!xg_fits(lstm_fwd_xg<RR, NL, 4, true, XV>, 256 + RR * XV, XG_PIN_FWD)) return 0;          \
     if (dry) return 1;                                                                           \
-    if (xg_ws_clear(ws, lstm_xg32_fwd_bytes(B, H), s) != hipSuccess) return -1;                  \
+    if (xg_ws_clear(ws, lstm_xg32_fwd_bytes(B, H), s, prezeroed) != hipSuccess) return -1;       \
     xg_trace_setup(s);                                                                           \
     hipLaunchKernelGGL((lstm_fwd_xg<RR, NL, 4, true, XV>), dim3(grid), dim3(256 + RR * XV),      \
                        XG_PIN_FWD, s, B, T, H, lens, whh_f, whh_r, gx_act, y, cst, g, hdr,       \
@@ -1828,7 +1807,8 @@ int lstm_fwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* 
 // per-utterance bias partials into dbpart (if given).
 int lstm_bwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                          const float* whh_r, const float* dy, float* act_dg, const float* cst,
-                         void* ws, float* dbpart, hipStream_t s, bool dry) {
+                         void* ws, float* dbpart, hipStream_t s, bool dry,
+                         const asr_lstm_opts_t& o) {
   if (!xg_enabled()) return 0;
   const char* e = getenv("ASR_LSTM_XG32");
   if (e && e[0] == '0') return 0;
@@ -1846,7 +1826,7 @@ int lstm_bwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* 
   do {                                                                                           \
     if (!xg_fits(lstm_bwd_xg<RR, M, false, XV, true>, 256 + RR * XV + 256, pin)) return 0;       \
     if (dry) return 1;                                                                           \
-    if (xg_ws_clear(ws, lstm_xg32_bwd_bytes(B, H), s) != hipSuccess) return -1;                  \
+    if (xg_ws_clear(ws, lstm_xg32_bwd_bytes(B, H), s, o.ws_prezeroed) != hipSuccess) return -1;  \
     xg_trace_setup(s);                                                                           \
     hipLaunchKernelGGL((lstm_bwd_xg<RR, M, false, XV, true>), dim3(grid),                        \
                        dim3(256 + RR * XV + 256), pin, s, B, T, H, lens, whh_f, whh_r, dy,      \
@@ -1876,7 +1856,7 @@ int lstm_bwd_xg32_launch(int B, int T, int H, const int32_t* lens, const float* 
 // lstm_xg_{fwd,bwd}_bytes; it is zeroed here before the launch.
 int lstm_fwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                        const float* whh_r, float* gx_act, float* y, float* cst, void* ws,
-                       uint16_t* ybf, hipStream_t s, bool dry) {
+                       uint16_t* ybf, hipStream_t s, bool dry, bool prezeroed) {
   if (!xg_enabled()) return 0;
   const int R = xg_rows(B, H);
   if (!R) return 0;
@@ -1896,7 +1876,7 @@ int lstm_fwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* wh
   do {                                                                                          \
     if (!xg_fits(lstm_fwd_xg<RR, KS, NS>, 64 * NS + RR * XU, PIN)) return 0;                     \
     if (dry) return 1;                                                                          \
-    if (xg_ws_clear(ws, lstm_xg_fwd_bytes(B, H), s) != hipSuccess) return -1;                   \
+    if (xg_ws_clear(ws, lstm_xg_fwd_bytes(B, H), s, prezeroed) != hipSuccess) return -1;        \
     xg_trace_setup(s);                                                                          \
     hipLaunchKernelGGL((lstm_fwd_xg<RR, KS, NS>), dim3(grid), dim3(64 * NS + RR * XU), PIN, s,   \
                        B, T, H, lens, whh_f, whh_r, gx_act, y, cst, g, hdr, ybf, ep, al);        \
@@ -1925,12 +1905,12 @@ int lstm_fwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* wh
 int lstm_bwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                        const float* whh_r, const float* dy, float* act_dg, const float* cst,
                        void* ws, uint16_t* dgbf, float* dbpart, hipStream_t s, bool dry,
-                       bool dg_f32, const uint16_t* acth) {
+                       bool dg_f32, const asr_lstm_opts_t& o, const uint16_t* acth) {
   if (acth && (dg_f32 || !dgbf)) return 0;   // packed activations: bf16 dG only
   if (!xg_enabled()) return 0;
   const int R = xg_rows(B, H);
   if (!R) return 0;
-  const int xb = xg_bwd_xu(R, H);
+  const int xb = xg_bwd_xu(o.bwd_units, R, H);
   const int mb = (H / 16 + xb / 4 - 1) / (xb / 4);   // M blocks per MFMA wave
   if (mb > 16) return 0;
   const int grid = 2 * ((B + R - 1) / R) * (H / xb);
@@ -1938,7 +1918,7 @@ int lstm_bwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* wh
   unsigned long long* g = (unsigned long long*)((char*)ws + XG_HDR);
   const unsigned ep = xg_bwd_seq(true);
   const int al = xg_allow_local();
-  const size_t pin = xg_pin_bwd();
+  const size_t pin = xg_pin_bwd(o.bwd_pin_kb);
   const char* li = getenv("ASR_XG_BWD_IO");   // cell I/O position (lstm_bwd_xg), A/B
   const int io_pos = (li && atoi(li) == 1) ? 1 : 0;
   const char* s16 = getenv("ASR_XG_DG_ST16");   // A/B: bf16 dG by 16-B stores from LDS
@@ -1950,14 +1930,14 @@ int lstm_bwd_xg_launch(int B, int T, int H, const int32_t* lens, const float* wh
       return 0;                                                                                 \
     }                                                                                           \
     if (dry) return 1;                                                                          \
-    if (xg_ws_clear(ws, lstm_xg_bwd_bytes(B, H), s) != hipSuccess) return -1;                   \
+    if (xg_ws_clear(ws, lstm_xg_bwd_bytes(B, H), s, o.ws_prezeroed) != hipSuccess) return -1;   \
     xg_trace_setup(s);                                                                          \
     hipLaunchKernelGGL((lstm_bwd_xg<RR, M, AHV, XBV>), dim3(grid), dim3(256 + (RR + 16) * XBV),   \
                        pin, s,                                                                  \
                        B, T, H, lens, whh_f, whh_r, dy, act_dg, cst, g, hdr, dgbf, dbpart, ep,   \
                        al, (dg_f32 || !dgbf) ? 1 : 0, io_pos, st16, (const h16x4*)acth,         \
-                       acth ? g_dyflag : nullptr, g_dyc0, (int)g_dyepoch,                        \
-                       acth ? g_prog_ctr : nullptr, g_prog_q, g_prog_q2);                        \
+                       o.dy_flags, o.dy_c0, o.dy_epoch, o.progress, o.progress_q1,              \
+                       o.progress_q2);                                                          \
   } while (0)
 #define ASR_XGB2(RR, M, AHV)                                  \
   do {                                                        \
@@ -2001,8 +1981,8 @@ constexpr int XGX_NPW = 6;   // 12 waves: 3 per SIMD, 170 registers per wave (8:
 int lstm_fwd_xgx_launch(int B, int T, int H, const int32_t* lens, const float* whh_f,
                         const float* whh_r, const uint16_t* x, int Din, const uint16_t* wih,
                         const float* b_ih, const float* b_hh, float* act, float* y, float* cst,
-                        void* ws, uint16_t* ybf, hipStream_t s, bool dry, uint16_t* acth,
-                        uint16_t* ydrop = nullptr, float drop_p = 0.f,
+                        void* ws, uint16_t* ybf, hipStream_t s, bool dry, bool prezeroed,
+                        uint16_t* acth, uint16_t* ydrop = nullptr, float drop_p = 0.f,
                         unsigned long long drop_seed = 0) {
   if (!xg_enabled()) return 0;
   const char* e = getenv("ASR_FUSE_XPROJ");
@@ -2034,7 +2014,7 @@ int lstm_fwd_xgx_launch(int B, int T, int H, const int32_t* lens, const float* w
     const size_t pin = fa.sharedSizeBytes >= 84 * 1024 ? 0 : 84 * 1024 - fa.sharedSizeBytes;   \
     if (!xg_fits(kfn, threads, pin)) return 0;                                                  \
     if (dry) return 1;                                                                          \
-    if (xg_ws_clear(ws, lstm_xg_fwd_bytes(B, H), s) != hipSuccess) return -1;                   \
+    if (xg_ws_clear(ws, lstm_xg_fwd_bytes(B, H), s, prezeroed) != hipSuccess) return -1;        \
     xg_trace_setup(s);                                                                          \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), pin, s, B, T, H, lens, whh_f, whh_r, x,  \
                        Din, wih, b_ih, b_hh, act, y, cst, g, hdr, ybf, al, late, defer,          \
@@ -2124,32 +2104,6 @@ extern "C" long long asr_xg_trace_read(unsigned long long* host) {
   return (long long)n;
 }
 
-// The backward recurrence's dynamic-LDS pin for the launches that follow
-// (kb in (80, 160]; 0 = ASR_XG_PIN_BWD_KB or the 140 KB default).  native_ops
-// sets 84 while weight-gradient GEMMs are meant to co-reside (opt-in
-// ASR_OVERLAP_WGRAD=2) and 0 otherwise: at 140 KB (+ 11 KB static) no kernel
-// with more than 9 KB of LDS -- every GEMM / convolution kernel -- can share a
-// CU with the recurrence.
-extern "C" int asr_lstm_set_bwd_pin_kb(int kb) {
-  ASR_REQUIRE(kb == 0 || (kb > 80 && kb <= 160), ASR_ERR_ARG, "lstm pin: %d KB", kb);
-  asr::g_pin_bwd_kb = kb;
-  return ASR_OK;
-}
-
-// dy of the backward recurrence launches that follow (asr_lstm_backward_dgbf_h
-// only) is written concurrently by input-gradient GEMMs on another stream:
-// processing steps [c0 k, c0 (k + 1)) -- dy rows t = q and t = T - 1 - q for
-// those steps q -- are complete once flags[k] == epoch
-// (set by asr_lstm_dy_signal after the chunk's GEMMs).  flags NULL: off.
-extern "C" int asr_lstm_set_dy_flags(const int* flags, int c0, int epoch) {
-  ASR_REQUIRE(!flags || (c0 > 0 && epoch != 0), ASR_ERR_ARG, "dy flags: c0 %d epoch %d", c0,
-              epoch);
-  asr::g_dyflag = flags;
-  asr::g_dyc0 = c0;
-  asr::g_dyepoch = (unsigned)epoch;
-  return ASR_OK;
-}
-
 namespace asr {
 namespace {
 __global__ void dy_signal(int* flags, int k, int epoch) {
@@ -2167,18 +2121,6 @@ extern "C" int asr_lstm_dy_signal(int* flags, int k, int epoch, void* stream) {
   return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ERR_HIP;
 }
 
-// The next packed-activation backward launch (asr_lstm_backward_dgbf_h) adds 1
-// to *counter per cell wave once the gate gradients of processing steps <= q
-// are stored and released; counter NULL: off.  Stream-ordered launches only
-// ever add, so a reader waits for the running total (asr_lstm_progress_gate).
-// The workspace of the next tagged-granule launch on this thread is already
-// zero (on: 1): it skips its memset.  Consumed by that launch; callers reset
-// it after the call (a call that took another path leaves it set).
-extern "C" int asr_lstm_ws_prezeroed(int on) {
-  asr::g_ws_zeroed = on ? 1 : 0;
-  return ASR_OK;
-}
-
 // Leading bytes of a recurrence workspace that a tagged-granule launch of
 // [B, *, H] zeroes (header + granules; the rest of asr_lstm_workspace_bytes
 // belongs to the per-step kernels, which clear their own).
@@ -2188,30 +2130,13 @@ extern "C" size_t asr_lstm_ws_zero_bytes(int B, int H) {
                   std::max(asr::lstm_xg32_fwd_bytes(B, H), asr::lstm_xg32_bwd_bytes(B, H)));
 }
 
-extern "C" int asr_lstm_set_bwd_progress(unsigned long long* counter, int q) {
-  ASR_REQUIRE(!counter || q >= 0, ASR_ERR_ARG, "bwd progress: q %d", q);
-  asr::g_prog_ctr = counter;
-  asr::g_prog_q = counter ? q : -1;
-  asr::g_prog_q2 = -1;
-  return ASR_OK;
-}
-
-// Two reporting steps q1 < q2: the counter gains one launch's arrivals at each.
-extern "C" int asr_lstm_set_bwd_progress2(unsigned long long* counter, int q1, int q2) {
-  ASR_REQUIRE(!counter || (q1 >= 0 && q2 > q1), ASR_ERR_ARG, "bwd progress: q %d, %d", q1, q2);
-  asr::g_prog_ctr = counter;
-  asr::g_prog_q = counter ? q1 : -1;
-  asr::g_prog_q2 = counter ? q2 : -1;
-  return ASR_OK;
-}
-
-// Arrivals one backward launch of this shape adds to the progress counter
-// (cell waves x work-groups), 0 if the shape does not take the tagged-granule
-// backward with the current units setting.
-extern "C" long long asr_lstm_bwd_progress_arrivals(int B, int H) {
+// Arrivals one backward launch of this shape with bwd_units = xu adds to the
+// progress counter at each reporting step (cell waves x work-groups), 0 if the
+// shape does not take the tagged-granule backward.
+extern "C" long long asr_lstm_bwd_progress_arrivals(int B, int H, int xu) {
   const int R = asr::xg_rows(B, H);
   if (!R) return 0;
-  const int xb = asr::xg_bwd_xu(R, H);
+  const int xb = asr::xg_bwd_xu(xu, R, H);
   return (long long)(2 * ((B + R - 1) / R) * (H / xb)) * (R * xb / 64);
 }
 
@@ -2246,21 +2171,13 @@ extern "C" int asr_lstm_progress_gate(const unsigned long long* counter, long lo
   return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ERR_HIP;
 }
 
-// Units per work-group of the backward recurrence for the launches that follow
-// (0: ASR_XG_BWD_XU or 16; 16; 32 -- half the work-groups, see lstm_bwd_xg).
-extern "C" int asr_lstm_set_bwd_units(int xu) {
-  ASR_REQUIRE(xu == 0 || xu == 16 || xu == 32, ASR_ERR_ARG, "lstm units: %d", xu);
-  asr::g_bwd_xu = xu;
-  return ASR_OK;
-}
-
 // Work-groups of the tagged-granule backward recurrence for [B, *, H] with xu
-// units per work-group (0: the current setting), 0 if the shape cannot take it.
+// units per work-group (0: ASR_XG_BWD_XU, else 16), 0 if the shape cannot take it.
 extern "C" int asr_lstm_backward_grid(int B, int H, int xu) {
   const int R = asr::xg_rows(B, H);
   if (!R) return 0;
   int xb = 16;
-  if (xu == 0) xb = asr::xg_bwd_xu(R, H);
+  if (xu == 0) xb = asr::xg_bwd_xu(0, R, H);
   else if (xu == 32) xb = (R == 8 && H % 32 == 0 && (H / 16 + 3) / 4 <= 8) ? 32 : 0;
   else if (xu != 16) return 0;
   if (!xb) return 0;
@@ -2366,19 +2283,21 @@ extern "C" int asr_lstm_forward_x(const uint16_t* x, int Din, const uint16_t* wi
                                   const float* b_ih, const float* b_hh, const float* whh_f,
                                   const float* whh_r, const int32_t* lens, int B, int T, int H,
                                   float* act, float* y, float* cst, uint16_t* ybf,
-                                  void* workspace, size_t ws_bytes, void* stream) {
+                                  void* workspace, size_t ws_bytes, void* stream,
+                                  const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(x && wih && b_ih && b_hh && whh_f && whh_r && lens && act && y && cst && workspace,
               ASR_ERR_ARG, "lstm_forward_x: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0 && Din > 0, ASR_ERR_ARG, "lstm_forward_x: bad shape");
   hipStream_t s = (hipStream_t)stream;
+  const bool pz = opts && opts->ws_prezeroed;
   if (asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh, act, y, cst,
-                               workspace, ybf, s, true, nullptr) != 1)
+                               workspace, ybf, s, true, pz, nullptr) != 1)
     return ASR_ERR_UNSUPPORTED;
   ASR_REQUIRE(ws_bytes >= asr::lstm_xg_fwd_bytes(B, H), ASR_ERR_WORKSPACE,
               "lstm_forward_x: workspace too small");
   const int slot = asr::prof_begin_launch(ASR_PROF_LSTM_FWD_SEQ, s, 0.0, ASR_PTAG_LSTM_FWD_XGX);
   const int rc = asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh,
-                                          act, y, cst, workspace, ybf, s, false, nullptr);
+                                          act, y, cst, workspace, ybf, s, false, pz, nullptr);
   ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_forward_x: launch failed");
   asr::prof_end_launch(ASR_PROF_LSTM_FWD_SEQ, slot, s);
   asr::g_lstm_last_path[0] = 3;
@@ -2393,20 +2312,22 @@ extern "C" int asr_lstm_forward_xh(const uint16_t* x, int Din, const uint16_t* w
                                    const float* b_ih, const float* b_hh, const float* whh_f,
                                    const float* whh_r, const int32_t* lens, int B, int T, int H,
                                    uint16_t* act_h, float* y, float* cst, uint16_t* ybf,
-                                   void* workspace, size_t ws_bytes, void* stream) {
+                                   void* workspace, size_t ws_bytes, void* stream,
+                                   const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(x && wih && b_ih && b_hh && whh_f && whh_r && lens && act_h && y && cst &&
               workspace, ASR_ERR_ARG, "lstm_forward_xh: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0 && Din > 0, ASR_ERR_ARG, "lstm_forward_xh: bad shape");
   ASR_REQUIRE(((uintptr_t)act_h & 7) == 0, ASR_ERR_ARG, "lstm_forward_xh: act_h not 8-B aligned");
   hipStream_t s = (hipStream_t)stream;
+  const bool pz = opts && opts->ws_prezeroed;
   if (asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh, nullptr, y,
-                               cst, workspace, ybf, s, true, act_h) != 1)
+                               cst, workspace, ybf, s, true, pz, act_h) != 1)
     return ASR_ERR_UNSUPPORTED;
   ASR_REQUIRE(ws_bytes >= asr::lstm_xg_fwd_bytes(B, H), ASR_ERR_WORKSPACE,
               "lstm_forward_xh: workspace too small");
   const int slot = asr::prof_begin_launch(ASR_PROF_LSTM_FWD_SEQ, s, 0.0, ASR_PTAG_LSTM_FWD_XGX);
   const int rc = asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh,
-                                          nullptr, y, cst, workspace, ybf, s, false, act_h);
+                                          nullptr, y, cst, workspace, ybf, s, false, pz, act_h);
   ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_forward_xh: launch failed");
   asr::prof_end_launch(ASR_PROF_LSTM_FWD_SEQ, slot, s);
   asr::g_lstm_last_path[0] = 3;
@@ -2425,7 +2346,8 @@ extern "C" int asr_lstm_forward_xh_drop(const uint16_t* x, int Din, const uint16
                                         int H, uint16_t* act_h, float* y, float* cst,
                                         uint16_t* ybf, uint16_t* ydrop, float drop_p,
                                         unsigned long long drop_seed, void* workspace,
-                                        size_t ws_bytes, void* stream) {
+                                        size_t ws_bytes, void* stream,
+                                        const asr_lstm_opts_t* opts) {
   ASR_REQUIRE(x && wih && b_ih && b_hh && whh_f && whh_r && lens && act_h && cst && ybf &&
               workspace, ASR_ERR_ARG, "lstm_forward_xh_drop: null pointer");
   ASR_REQUIRE(B > 0 && T > 0 && H > 0 && Din > 0, ASR_ERR_ARG, "lstm_forward_xh_drop: bad shape");
@@ -2434,15 +2356,16 @@ extern "C" int asr_lstm_forward_xh_drop(const uint16_t* x, int Din, const uint16
   ASR_REQUIRE(((uintptr_t)act_h & 7) == 0 && ((uintptr_t)ybf & 3) == 0 &&
               ((uintptr_t)ydrop & 3) == 0, ASR_ERR_ARG, "lstm_forward_xh_drop: misaligned");
   hipStream_t s = (hipStream_t)stream;
+  const bool pz = opts && opts->ws_prezeroed;
   if (asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh, nullptr, y,
-                               cst, workspace, ybf, s, true, act_h) != 1)
+                               cst, workspace, ybf, s, true, pz, act_h) != 1)
     return ASR_ERR_UNSUPPORTED;
   ASR_REQUIRE(ws_bytes >= asr::lstm_xg_fwd_bytes(B, H), ASR_ERR_WORKSPACE,
               "lstm_forward_xh_drop: workspace too small");
   const int slot = asr::prof_begin_launch(ASR_PROF_LSTM_FWD_SEQ, s, 0.0, ASR_PTAG_LSTM_FWD_XGX);
   const int rc = asr::lstm_fwd_xgx_launch(B, T, H, lens, whh_f, whh_r, x, Din, wih, b_ih, b_hh,
-                                          nullptr, y, cst, workspace, ybf, s, false, act_h, ydrop,
-                                          drop_p, drop_seed);
+                                          nullptr, y, cst, workspace, ybf, s, false, pz, act_h,
+                                          ydrop, drop_p, drop_seed);
   ASR_REQUIRE(rc == 1, ASR_ERR_HIP, "lstm_forward_xh_drop: launch failed");
   asr::prof_end_launch(ASR_PROF_LSTM_FWD_SEQ, slot, s);
   asr::g_lstm_last_path[0] = 3;
@@ -2491,5 +2414,5 @@ extern "C" int asr_lstm_forward_x_ok(int B, int H, int Din) {
   if (B <= 0 || H <= 0 || Din <= 0) return 0;
   return asr::lstm_fwd_xgx_launch(B, 1, H, nullptr, nullptr, nullptr, nullptr, Din, nullptr,
                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, true, nullptr) == 1;
+                                  nullptr, true, false, nullptr) == 1;
 }

@@ -9,7 +9,6 @@ Weight gradients are accumulated by the kernels directly into ``param.grad``
 the Functions therefore return ``None`` for weights.
 """
 import collections
-import contextlib
 import ctypes
 import os
 import weakref
@@ -60,8 +59,10 @@ _H2D_PINNED = os.environ.get('ASR_H2D_PINNED', '1') != '0'   # (A/B: 0 = pageabl
 # granule workspace zero (lstm_xg.hip); instead of one memset launch before
 # each of the 2 x L layer passes of a step, the encoder forward clears one
 # arena with a slot per pass (rec_arena_begin), each BLSTM forward takes a
-# slot for itself and reserves one for its backward, and those launches skip
-# their memset (asr_lstm_ws_prezeroed).  A slot is handed out once per
+# slot for itself and reserves one for its backward, and those launches are
+# told so with the call (asr_lstm_opts_t.ws_prezeroed, like every recurrence
+# launch setting: nothing is set in the library between calls) and skip their
+# memset.  A slot is handed out once per
 # generation; a backward whose reservation is from an older generation (the
 # arena was cleared again by another forward since) takes a private workspace
 # and the launch's own memset.  Only each slot's leading bytes are cleared --
@@ -127,17 +128,9 @@ def _rec_workspace(nbytes, dev, res):
     return (res[0] if pz else _ws(nbytes, dev)), pz
 
 
-@contextlib.contextmanager
-def _prezeroed(on):
-    """Tell the recurrence launch inside the block that its workspace is
-    already zero (asr_lstm_ws_prezeroed), and clear the setting after it."""
-    if on:
-        N.call('asr_lstm_ws_prezeroed', 1)
-    try:
-        yield
-    finally:
-        if on:
-            N.call('asr_lstm_ws_prezeroed', 0)
+def _lstm_opts(pz, **settings):
+    """asr_lstm_opts_t* of one recurrence call: pz, _rec_workspace's prezeroed."""
+    return ctypes.byref(N.LstmOpts(ws_prezeroed=int(pz), **settings))
 
 
 # Gradient-ready notifications for the data-parallel bucketed all-reduce
@@ -1542,10 +1535,9 @@ class BLSTMLayerFn(torch.autograd.Function):
             x_map = rowmap(Dp) if cd == BF16 else a_map
             run_gemm([gemm_problem(operand(x_op, 0, x_map), operand(w_op, 0, rowmap(Dp)), gx,
                                    rowmap(8 * H), B * T, 8 * H, Dp, bias=b_ih, bias2=b_hh)], dev)
-            with _prezeroed(pz):
-                N.call('asr_lstm_forward', N.ptr(gx), N.ptr(w_hh), ctypes.c_void_p(whh_r), F32,
-                       N.ptr(lens), B, T, H, cd, N.ptr(y), N.ptr(cst), N.ptr(y_bf), N.ptr(ws),
-                       nb, N.stream_handle(dev))
+            N.call('asr_lstm_forward', N.ptr(gx), N.ptr(w_hh), ctypes.c_void_p(whh_r), F32,
+                   N.ptr(lens), B, T, H, cd, N.ptr(y), N.ptr(cst), N.ptr(y_bf), N.ptr(ws), nb,
+                   N.stream_handle(dev), _lstm_opts(pz))
         ctx.save_for_backward(x_op, w_op, lens, w_hh, b_ih, b_hh, gx, cst,
                               y_bf if y_bf is not None else y)
         ctx.meta = (in_map, gbufs, cd, B, Dp, w_ih)
@@ -1630,21 +1622,16 @@ class _ProgressReport:
         self.targets = self.pre = None
 
     @classmethod
-    def request(cls, dev, B, H, steps):
-        """For the next backward of [B, *, H]; None where it would not report."""
-        arrivals = N.query('asr_lstm_bwd_progress_arrivals', B, H)
+    def request(cls, dev, B, H, xu, steps):
+        """For the next backward of [B, *, H] with xu units per work-group;
+        None where it would not report."""
+        arrivals = N.query('asr_lstm_bwd_progress_arrivals', B, H, xu)
         return cls(dev, arrivals, steps) if arrivals > 0 else None
 
     def arm(self, dev):
         """pre: all a gated consumer reads but the recurrence's writes is enqueued by now."""
-        N.call('asr_lstm_set_bwd_progress' + ('2' if len(self.steps) == 2 else ''),
-               N.ptr(self.counter), *self.steps)
         self.pre = torch.cuda.Event()
         self.pre.record(torch.cuda.current_stream(dev))
-
-    @staticmethod
-    def disarm():
-        N.call('asr_lstm_set_bwd_progress', None, 0)
 
     def commit(self, done):
         """The gate targets of a launch that ran (done): each step's arrivals on
@@ -1656,12 +1643,13 @@ class _ProgressReport:
         return self.targets
 
 
-_BwdPlan = collections.namedtuple('_BwdPlan', 'mode last_main wgrad_banded bands dx report')
+_BwdPlan = collections.namedtuple('_BwdPlan',
+                                  'mode pin_kb xu last_main wgrad_banded bands dx report')
 
 
 def _blstm_bwd_plan(ctx, act, pipe, in_map, B, H, dev):
     """What a BLSTM layer's backward runs, and its recurrence's launch settings
-    (made here: the progress arrivals follow the units setting).  bands
+    (pin_kb, xu: the progress arrivals follow the units).  bands
     (_dx_bands) come with dx and, where the recurrence reports progress, the
     report gating them; None: dX pipelined or whole, decided after it."""
     T = in_map.T
@@ -1669,8 +1657,7 @@ def _blstm_bwd_plan(ctx, act, pipe, in_map, B, H, dev):
     # opt-in mode 2 (84 KB); otherwise 140 KB excludes every GEMM kernel.
     # Units per work-group: 32 where that frees the CUs for mode 3.
     mode, xu = _overlap_plan(dev, B, H)
-    N.call('asr_lstm_set_bwd_pin_kb', 84 if mode == '2' else 0)
-    N.call('asr_lstm_set_bwd_units', xu)
+    pin_kb = 84 if mode == '2' else 0
     last_main = not ctx.next_rec and _wgrad_last_main_on()
     wgrad_banded = last_main and _wgrad_split_ok(ctx, T, mode)
     bands = dx = report = None
@@ -1679,11 +1666,12 @@ def _blstm_bwd_plan(ctx, act, pipe, in_map, B, H, dev):
         # beside the recurrence in mode 3; in the other modes the same bands after it
         bands = _dx_bands(T, _dx_split_chunks() == 2 and T >= 128)
         if mode == '3':
-            report = _ProgressReport.request(dev, B, H, [T - 1 - g[0][0] for g in bands[:-1]])
+            report = _ProgressReport.request(dev, B, H, xu,
+                                             [T - 1 - g[0][0] for g in bands[:-1]])
         # dX before the recurrence: its zero fill (non-identity maps) precedes
         # the side stream's writes
         dx = in_map.alloc_dx(B, dev)
-    return _BwdPlan(mode, last_main, wgrad_banded, bands, dx, report)
+    return _BwdPlan(mode, pin_kb, xu, last_main, wgrad_banded, bands, dx, report)
 
 
 def _blstm_bwd_recurrence(ctx, plan, dy, pipe, w_hh, lens, act, cst, gbufs, cd, B, T, H, dev):
@@ -1695,38 +1683,37 @@ def _blstm_bwd_recurrence(ctx, plan, dy, pipe, w_hh, lens, act, cst, gbufs, cd, 
     whh_r = ctypes.c_void_p(w_hh.data_ptr() + 4 * H * H * 4)
     dg_bf = torch.empty(B, T, 8 * H, dtype=torch.bfloat16, device=dev) if cd == BF16 else None
     done, gate = False, None
-    try:
-        if act.dtype == torch.float16:
-            # packed fp16 activations of asr_lstm_forward_xh: the tagged-granule
-            # backward reads them directly; otherwise they are unpacked to f32
-            done, gate = _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf,
-                                           gbufs, cd, B, T, H, dev)
-            if not done:
-                a32 = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
-                N.call('asr_lstm_unpack_act_h', N.ptr(act), B, T, H, N.ptr(a32),
-                       N.stream_handle(dev))
-                act = a32
-        nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2 if fused_db else 1)
-        ws = _ws(nb, dev)
-        # the bias gradients (sum of dG over b, t) are accumulated by the same call
-        if not done and fused_db:
-            # bf16 mode: only the bf16 dG feeds the GEMMs, so the f32 dG is not stored
-            fn = 'asr_lstm_backward_dgbf' if dg_bf is not None else 'asr_lstm_backward_db'
-            N.call(fn, N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H, cd, N.ptr(act),
-                   N.ptr(cst), N.ptr(dg_bf), N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb,
+    if act.dtype == torch.float16:
+        # packed fp16 activations of asr_lstm_forward_xh: the tagged-granule
+        # backward reads them directly; otherwise they are unpacked to f32
+        done, gate = _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf,
+                                       gbufs, cd, B, T, H, dev)
+        if not done:
+            a32 = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
+            N.call('asr_lstm_unpack_act_h', N.ptr(act), B, T, H, N.ptr(a32),
                    N.stream_handle(dev))
-        elif not done:   # A/B: separate column-sum pass over dG
-            N.call('asr_lstm_backward', N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H,
-                   cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf), N.ptr(ws), nb, N.stream_handle(dev))
-            colsum_accumulate(act.view(B * T, 8 * H), gbufs[2], gbufs[3])
-    finally:
-        N.call('asr_lstm_set_bwd_units', 0)   # direct API callers: the default again
+            act = a32
+    nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2 if fused_db else 1)
+    ws = _ws(nb, dev)
+    opts = _lstm_opts(False, bwd_pin_kb=plan.pin_kb, bwd_units=plan.xu)
+    # the bias gradients (sum of dG over b, t) are accumulated by the same call
+    if not done and fused_db:
+        # bf16 mode: only the bf16 dG feeds the GEMMs, so the f32 dG is not stored
+        fn = 'asr_lstm_backward_dgbf' if dg_bf is not None else 'asr_lstm_backward_db'
+        N.call(fn, N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H, cd, N.ptr(act),
+               N.ptr(cst), N.ptr(dg_bf), N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb,
+               N.stream_handle(dev), opts)
+    elif not done:   # A/B: separate column-sum pass over dG
+        N.call('asr_lstm_backward', N.ptr(dy), N.ptr(w_hh), whh_r, F32, N.ptr(lens), B, T, H,
+               cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf), N.ptr(ws), nb, N.stream_handle(dev),
+               opts)
+        colsum_accumulate(act.view(B * T, 8 * H), gbufs[2], gbufs[3])
     return (dg_bf if dg_bf is not None else act), act, gate
 
 
 def _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf, gbufs, cd, B, T, H,
                       dev):
-    """The packed-activation tagged-granule backward, armed with the plan's
+    """The packed-activation tagged-granule backward, given the plan's
     progress report (with none, banded weight gradients in mode 3 ask for one
     at their middle band's step) and the dy flags of a pipelined layer above.
     (ran, committed report or None); not ran: ASR_ERR_UNSUPPORTED, no report --
@@ -1734,23 +1721,23 @@ def _blstm_bwd_packed(ctx, plan, dy, pipe, w_hh, whh_r, lens, act, cst, dg_bf, g
     nb = N.query('asr_lstm_workspace_bytes', B, H, cd, 2)
     res, ctx.bws = ctx.bws, None      # a reserved slot serves one backward
     ws, pz = _rec_workspace(nb, dev, res)
+    settings = dict(bwd_pin_kb=plan.pin_kb, bwd_units=plan.xu)
     if pipe is not None:
-        N.call('asr_lstm_set_dy_flags', N.ptr(pipe[0]), pipe[1], pipe[2])
+        settings.update(dy_flags=pipe[0].data_ptr(), dy_c0=pipe[1], dy_epoch=pipe[2])
     report = plan.report
     if report is None and plan.wgrad_banded and plan.mode == '3':
-        report = _ProgressReport.request(dev, B, H, [T - 1 - T // 4])
+        report = _ProgressReport.request(dev, B, H, plan.xu, [T - 1 - T // 4])
     if report is not None:
         report.arm(dev)
+        q1, q2 = (report.steps + (-1,))[:2]
+        settings.update(progress=report.counter.data_ptr(), progress_q1=q1, progress_q2=q2)
     try:
-        with _prezeroed(pz):
-            rc = N.query('asr_lstm_backward_dgbf_h', N.ptr(dy), N.ptr(w_hh), whh_r, F32,
-                         N.ptr(lens), B, T, H, cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf),
-                         N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb, N.stream_handle(dev))
+        rc = N.query('asr_lstm_backward_dgbf_h', N.ptr(dy), N.ptr(w_hh), whh_r, F32,
+                     N.ptr(lens), B, T, H, cd, N.ptr(act), N.ptr(cst), N.ptr(dg_bf),
+                     N.ptr(gbufs[2]), N.ptr(gbufs[3]), N.ptr(ws), nb, N.stream_handle(dev),
+                     _lstm_opts(pz, **settings))
     finally:
-        if report is not None:
-            report.disarm()
         if pipe is not None:
-            N.call('asr_lstm_set_dy_flags', None, 16, 0)
             # (after the launch: later compute-stream work sees all of dy)
             torch.cuda.current_stream(dev).wait_event(pipe[3])
     if rc not in (0, N.ASR_ERR_UNSUPPORTED):
@@ -1920,20 +1907,19 @@ def _lstm_forward_fused(x_op, Dp, w_op, b_ih, b_hh, w_hh, lens, B, T, H, out_spe
     args = (N.ptr(x_op), Dp, N.ptr(w_op), N.ptr(b_ih), N.ptr(b_hh), N.ptr(w_hh),
             ctypes.c_void_p(w_hh.data_ptr() + 4 * H * H * 4), N.ptr(lens), B, T, H, N.ptr(gx))
     handoff = None
-    with _prezeroed(pz):
-        if packed and not y_f32:
-            fn = 'asr_lstm_forward_xh_drop'
-            y_d = (torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
-                   if out_drop is not None else None)
-            p, seed = out_drop if out_drop is not None else (0.0, 0)
-            rc = N.query(fn, *args, None, N.ptr(cst), N.ptr(y_bf), N.ptr(y_d), ctypes.c_float(p),
-                         ctypes.c_ulonglong(seed), N.ptr(ws), nb, N.stream_handle(dev))
-            if rc == 0:
-                handoff = (y_d if y_d is not None else y_bf, out_drop)
-        else:
-            fn = 'asr_lstm_forward_xh' if packed else 'asr_lstm_forward_x'
-            rc = N.query(fn, *args, N.ptr(y), N.ptr(cst), N.ptr(y_bf), N.ptr(ws), nb,
-                         N.stream_handle(dev))
+    tail = (N.ptr(ws), nb, N.stream_handle(dev), _lstm_opts(pz))
+    if packed and not y_f32:
+        fn = 'asr_lstm_forward_xh_drop'
+        y_d = (torch.empty(B, T, 2 * H, dtype=torch.bfloat16, device=dev)
+               if out_drop is not None else None)
+        p, seed = out_drop if out_drop is not None else (0.0, 0)
+        rc = N.query(fn, *args, None, N.ptr(cst), N.ptr(y_bf), N.ptr(y_d), ctypes.c_float(p),
+                     ctypes.c_ulonglong(seed), *tail)
+        if rc == 0:
+            handoff = (y_d if y_d is not None else y_bf, out_drop)
+    else:
+        fn = 'asr_lstm_forward_xh' if packed else 'asr_lstm_forward_x'
+        rc = N.query(fn, *args, N.ptr(y), N.ptr(cst), N.ptr(y_bf), *tail)
     if rc not in (0, N.ASR_ERR_UNSUPPORTED):
         raise N.NativeError('%s failed (rc=%d): %s' % (
             fn, rc, N.lib().asr_last_error().decode(errors='replace')))

@@ -488,7 +488,7 @@ def test_lstm_backward_db_is_column_sum_of_dg(B, T, H, cuda_dev, monkeypatch):
     nb = N.query('asr_lstm_workspace_bytes', B, H, BF, 0)
     ws = torch.empty(nb, dtype=torch.uint8, device=cuda_dev)
     N.call('asr_lstm_forward', N.ptr(gx), N.ptr(whh), whh_r, N.ASR_DT_F32, N.ptr(lens_d), B, T, H,
-           BF, N.ptr(y), N.ptr(cst), N.ptr(ybf), N.ptr(ws), nb, N.stream_handle(cuda_dev))
+           BF, N.ptr(y), N.ptr(cst), N.ptr(ybf), N.ptr(ws), nb, N.stream_handle(cuda_dev), None)
     outs = []
     for kind in (1, 2):
         act = gx.clone()
@@ -499,11 +499,11 @@ def test_lstm_backward_db_is_column_sum_of_dg(B, T, H, cuda_dev, monkeypatch):
         if kind == 1:
             N.call('asr_lstm_backward', N.ptr(dy), N.ptr(whh), whh_r, N.ASR_DT_F32, N.ptr(lens_d),
                    B, T, H, BF, N.ptr(act), N.ptr(cst), N.ptr(dgbf), N.ptr(ws), nb,
-                   N.stream_handle(cuda_dev))
+                   N.stream_handle(cuda_dev), None)
         else:
             N.call('asr_lstm_backward_db', N.ptr(dy), N.ptr(whh), whh_r, N.ASR_DT_F32,
                    N.ptr(lens_d), B, T, H, BF, N.ptr(act), N.ptr(cst), N.ptr(dgbf), N.ptr(db[0]),
-                   N.ptr(db[1]), N.ptr(ws), nb, N.stream_handle(cuda_dev))
+                   N.ptr(db[1]), N.ptr(ws), nb, N.stream_handle(cuda_dev), None)
         torch.cuda.synchronize()
         outs.append((act.cpu().numpy(), dgbf.cpu(), db.cpu().numpy()))
     (a1, g1, _), (a2, g2, db2) = outs
