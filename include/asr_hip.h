@@ -722,6 +722,62 @@ int asr_att_step_backward(const asr_attdec_dims_t* dims, const float* enc, const
                           float* dctx_tot, float* dwd, float* dv_part, float* dwc_part,
                           float* dcw_part, void* workspace, size_t ws_bytes, void* stream);
 
+/* Multi-head attention step (csrc/att_heads.hip): AttentionMechanism.forward
+ * (attention_layer.py:141-251) for H >= 1 heads of additive (location, or
+ * content with C = 0) or dot-product energies, all heads in one launch.  f32
+ * arithmetic whatever the compute mode.
+ * Dims as above; A is the width of enc_a (dot: A = D, C = 0; K is ignored when
+ * C = 0).  Layouts: enc [B][T][E]; enc_a HEAD-MAJOR [H][B][T][A] (each head's
+ * W_enc GEMM writes its own slice); dec_out [B][D]; aw_prev / aw_out / d_aw_out
+ * / d_aw_prev [B][H][T]; ctx_out / d_ctx / dctx_tot [B][H][E] (= [B][H*E], the
+ * head-major concatenation torch.cat(..., -1) gives).  Per-head weights by
+ * pointer: w_dec[h] [A][D], w_conv[h] [A][C], conv_w[h] [C][K], v[h] [A]
+ * (all unused for dot).
+ * Forward: per head conv of aw_prev, energies V.tanh(enc_a + W_dec dec_out +
+ * W_conv f) or enc_a . dec_out, multiplicative length mask, sharpening,
+ * softmax over all T frames / sigmoid, context.
+ * Backward (cotangents d_ctx, d_aw_out nullable), all written, none
+ * accumulated: d_enc_a [H][B][T][A]; d_dec [B][D], summed over the heads in
+ * the order h = 0 .. H-1 by one owner thread per element (no atomics: run to
+ * run bitwise); d_aw_prev (zero for C = 0 and dot); dctx_tot (= d_ctx; the
+ * caller forms d enc[b] = aw_out[b]^T dctx_tot[b], one product with K = H);
+ * additive only: dwd [H][B][A] (dW_dec_h = dwd_h^T dec_out) and the partial
+ * rows dv_part [H][B][A], dwc_part [H][B][A*C], dcw_part [H][B][C*K] whose
+ * column sums over B are dV_h, dW_conv_h and head h's conv-kernel gradient.
+ * asr_att_heads_workspace_bytes(p, backward): bytes the call needs (the
+ * backward's conv features; 0 for the forward, and 0 for a refused shape).
+ * ASR_ERR_UNSUPPORTED (nothing launched, asr_last_error says why): H >
+ * ASR_ATT_HEADS_MAX, C > ASR_ATT_HEADS_MAX_C, an even K, B > 65535, any
+ * operand or output of 2 GiB or more, or an LDS need over 64 KiB (forward
+ * about 4 (2 T + 2 A + A C + C K + K + 64 C) bytes, backward about
+ * 4 (2 T + E + D + 3 A + A C + C K + K)); forward and backward refuse the
+ * same shapes. */
+#define ASR_ATT_HEADS_MAX 8
+#define ASR_ATT_HEADS_MAX_C 16
+#define ASR_ATT_HEADS_ADDITIVE 0
+#define ASR_ATT_HEADS_DOT 1
+typedef struct {
+  int B, T, E, A, C, K, D, H;
+  int kind;
+  float sharpening;
+  int sigmoid_smoothing;
+  const float* w_dec[ASR_ATT_HEADS_MAX];
+  const float* w_conv[ASR_ATT_HEADS_MAX];
+  const float* conv_w[ASR_ATT_HEADS_MAX];
+  const float* v[ASR_ATT_HEADS_MAX];
+} asr_att_heads_t;
+size_t asr_att_heads_workspace_bytes(const asr_att_heads_t* p, int backward);
+int asr_att_heads_forward(const asr_att_heads_t* p, const float* enc, const float* enc_a,
+                          const int32_t* lens, const float* dec_out, const float* aw_prev,
+                          float* ctx_out, float* aw_out, void* workspace, size_t ws_bytes,
+                          void* stream);
+int asr_att_heads_backward(const asr_att_heads_t* p, const float* enc, const float* enc_a,
+                           const int32_t* lens, const float* dec_out, const float* aw_prev,
+                           const float* aw_out, const float* d_ctx, const float* d_aw_out,
+                           float* d_enc_a, float* d_dec, float* d_aw_prev, float* dctx_tot,
+                           float* dwd, float* dv_part, float* dwc_part, float* dcw_part,
+                           void* workspace, size_t ws_bytes, void* stream);
+
 /* Attention beam search on the device (AttentionSeq2seq._decode_infer_beam,
  * attention_seq2seq.py:1038-1237; csrc/att_beam.hip states the semantics) for
  * bahdanau order, a one-layer LSTMCell decoder without residual, location or

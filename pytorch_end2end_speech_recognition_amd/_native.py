@@ -224,6 +224,9 @@ SIGNATURES = {
     'asr_att_step_workspace_bytes': (c_size, [c_vp]),
     'asr_att_step_forward': (c_int, [c_vp] + [c_vp] * 12 + [c_size, c_vp]),
     'asr_att_step_backward': (c_int, [c_vp] + [c_vp] * 21 + [c_size, c_vp]),
+    'asr_att_heads_workspace_bytes': (c_size, [c_vp, c_int]),
+    'asr_att_heads_forward': (c_int, [c_vp] + [c_vp] * 8 + [c_size, c_vp]),
+    'asr_att_heads_backward': (c_int, [c_vp] + [c_vp] * 17 + [c_size, c_vp]),
     'asr_att_beam_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     'asr_att_beam_decode': (c_int, [c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
@@ -266,6 +269,19 @@ class AttDecDims(ctypes.Structure):
     """asr_attdec_dims_t"""
     _fields_ = [(n, c_int) for n in ('B', 'T', 'E', 'A', 'C', 'K', 'D', 'S')] + [
         ('sharpening', c_float), ('sigmoid_smoothing', c_int)]
+
+
+ATT_HEADS_MAX = 8
+ATT_HEADS_MAX_C = 16
+ATT_HEADS_ADDITIVE = 0
+ATT_HEADS_DOT = 1
+
+
+class AttHeads(ctypes.Structure):
+    """asr_att_heads_t"""
+    _fields_ = [(n, c_int) for n in ('B', 'T', 'E', 'A', 'C', 'K', 'D', 'H', 'kind')] + [
+        ('sharpening', c_float), ('sigmoid_smoothing', c_int)] + [
+        (n, c_vp * ATT_HEADS_MAX) for n in ('w_dec', 'w_conv', 'conv_w', 'v')]
 
 
 class AttDecOpts(ctypes.Structure):

@@ -320,10 +320,14 @@ class AttentionSeq2seq(ModelBase):
 
     def _fused_ok(self, task, dir):
         """The fused decoder op covers bahdanau order with a 1-layer decoder
-        without residual connections (location or content attention)."""
+        without residual connections and one head of location or content
+        attention; several heads and dot_product attention take the per-step
+        paths (AttentionMechanism.forward on native_ops.att_heads_step)."""
         dec = getattr(self, 'decoder_%d_%s' % (task, dir), None)
+        att = getattr(self, 'attend_%d_%s' % (task, dir), None)
         return (self.decoding_order == 'bahdanau' and dec is not None and dec.num_layers == 1
-                and dec.rnn_type == 'lstm' and not dec.residual and not dec.dense_residual)
+                and dec.rnn_type == 'lstm' and not dec.residual and not dec.dense_residual
+                and att is not None and att.single_additive)
 
     @staticmethod
     def _run_dec(mod, inp, hx, cx):
@@ -368,7 +372,8 @@ class AttentionSeq2seq(ModelBase):
         hx = [h0 if h0 is not None else zero for _ in range(nl)]
         cx = [zero for _ in range(nl)]
         dec_out = h0 if h0 is not None else zero
-        aw = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        nh = att.num_heads
+        aw = torch.zeros(B, T, nh, dtype=torch.float32, device=dev)
         ctx = torch.zeros(B, E, dtype=torch.float32, device=dev)
         lens = x_lens if torch.is_tensor(x_lens) else torch.from_numpy(
             np.asarray(x_lens, np.int32)).to(dev)
@@ -377,7 +382,7 @@ class AttentionSeq2seq(ModelBase):
         if ys_host is not None and tuple(ys_host.shape) != tuple(ys.shape):
             ys_host = None
         y_emb = embed(ys, ys_host)                                # [B, S, emb]
-        enc_a = att.W_enc_head0(enc_out).unsqueeze(3)             # [B, T, A, 1]
+        enc_a = att.enc_projection(enc_out)                       # [B, T, A, H]
         ss = self._ss_steps(S)
 
         def generate(d, c):
@@ -395,20 +400,20 @@ class AttentionSeq2seq(ModelBase):
                     d3, hx, cx = self._run_dec(dec1, torch.cat([y, ctx], dim=-1).unsqueeze(1),
                                                hx, cx)
                     dec_out = d3.squeeze(1)
-                c3, a3 = att(enc_out, enc_a, lens, dec_out.unsqueeze(1), aw.unsqueeze(2))
+                c3, a3 = att(enc_out, enc_a, lens, dec_out.unsqueeze(1), aw)
             elif order == 'luong':
                 d3, hx, cx = self._run_dec(dec1, torch.cat([y, ctx], dim=-1).unsqueeze(1), hx, cx)
                 dec_out = d3.squeeze(1)
-                c3, a3 = att(enc_out, enc_a, lens, dec_out.unsqueeze(1), aw.unsqueeze(2))
+                c3, a3 = att(enc_out, enc_a, lens, dec_out.unsqueeze(1), aw)
             else:                                                 # conditional
                 d3, hx, cx = self._run_dec(dec1, y.unsqueeze(1), hx, cx)
-                c3, a3 = att(enc_out, enc_a, lens, d3, aw.unsqueeze(2))
+                c3, a3 = att(enc_out, enc_a, lens, d3, aw)
                 d3, hx, cx = self._run_dec(dec2, c3, hx, cx)
                 dec_out = d3.squeeze(1)
-            ctx, aw = c3.squeeze(1), a3.squeeze(2)
+            ctx, aw = c3.squeeze(1), a3                           # aw [B, T, H]
             decs.append(dec_out)
             ctxs.append(ctx)
-            aws.append(aw)
+            aws.append(aw.squeeze(2) if nh == 1 else aw)          # [B, T] for one head
             if ss is not None:
                 step_logits.append(generate(dec_out.unsqueeze(1), ctx.unsqueeze(1)))
         if ss is not None:
@@ -527,7 +532,7 @@ class AttentionSeq2seq(ModelBase):
     def _infer_step(self, task, dir, t, y_emb, st, enc, enc_a, lens):
         """One inference decoder step (:963-1001) on the HIP per-step ops, for any
         decoding order / decoder depth.  st = dict(h, c (lists per layer), dec,
-        ctx, aw); y_emb [n, emb] (unused at t = 0 in bahdanau order).  Returns
+        ctx, aw [n, T, H]); y_emb [n, emb] (unused at t = 0 in bahdanau order).  Returns
         (new st, logits [n, V])."""
         att = getattr(self, 'attend_%d_%s' % (task, dir))
         W_d, W_c = getattr(self, 'W_d_%d_%s' % (task, dir)), getattr(self, 'W_c_%d_%s' % (task, dir))
@@ -539,7 +544,7 @@ class AttentionSeq2seq(ModelBase):
             d1 = getattr(self, 'decoder_first_%d_%s' % (task, dir))
             d2 = getattr(self, 'decoder_second_%d_%s' % (task, dir))
             dd, hx, cx = self._run_dec(d1, y_emb.unsqueeze(1), hx, cx)
-            c3, a3 = att(enc, enc_a, lens, dd, aw.unsqueeze(2))
+            c3, a3 = att(enc, enc_a, lens, dd, aw)
             d3, hx, cx = self._run_dec(d2, c3, hx, cx)
             dec = d3.squeeze(1)
         else:
@@ -548,8 +553,8 @@ class AttentionSeq2seq(ModelBase):
                 d3, hx, cx = self._run_dec(dm, torch.cat([y_emb, ctx], dim=-1).unsqueeze(1),
                                            hx, cx)
                 dec = d3.squeeze(1)
-            c3, a3 = att(enc, enc_a, lens, dec.unsqueeze(1), aw.unsqueeze(2))
-        ctx, aw = c3.reshape(n, -1), a3.reshape(n, L)
+            c3, a3 = att(enc, enc_a, lens, dec.unsqueeze(1), aw)
+        ctx, aw = c3.reshape(n, -1), a3.reshape(n, L, -1)
         logits = fc(ops.tanh(ops.linear2(dec, W_d.fc.weight, W_d.fc.bias, ctx, W_c.fc.weight,
                                          W_c.fc.bias)))
         return dict(h=hx, c=cx, dec=dec, ctx=ctx, aw=aw), logits
@@ -566,9 +571,10 @@ class AttentionSeq2seq(ModelBase):
         h0 = self._init_h0(enc_out, task, dir)
         zero = torch.zeros(B, D, dtype=torch.float32, device=dev)
         h = h0 if h0 is not None else zero
+        nh = getattr(self, 'attend_%d_%s' % (task, dir)).num_heads
         return dict(h=[h] * nl, c=[zero] * nl, dec=h,
                     ctx=torch.zeros(B, E, dtype=torch.float32, device=dev),
-                    aw=torch.zeros(B, T, dtype=torch.float32, device=dev))
+                    aw=torch.zeros(B, T, nh, dtype=torch.float32, device=dev))
 
     @staticmethod
     def _reverse_bwd(best_hyps, y_lens):
@@ -667,8 +673,7 @@ class AttentionSeq2seq(ModelBase):
         dev = enc_out.device
         B, _, E = enc_out.shape
         lens = np.asarray(x_lens).reshape(-1).astype(np.int64)
-        enc_a = att.W_enc_head0(enc_out)                            # [B, T, A]
-        A = enc_a.shape[2]
+        enc_a = att.enc_projection(enc_out)                         # [B, T, A, H]
         init = self._init_state(enc_out, task, dir)
         dm = getattr(self, 'decoder_%d_%s' % (task, dir), None)
         residual = dm is not None and dm.residual and dm.num_layers > 1
@@ -676,11 +681,17 @@ class AttentionSeq2seq(ModelBase):
         def _rows(st, i):
             return {k: ([x[i:i + 1] for x in v] if isinstance(v, list) else v[i:i + 1])
                     for k, v in st.items()}
+
+        def _enc_a_rows(e1, n):
+            """[1, L, A, H] -> n copies [n, L, A, H], head-major in memory (the
+            layout the attention step reads without a copy)."""
+            _, L_, A_, H_ = e1.shape
+            return e1.permute(3, 0, 1, 2).expand(H_, n, L_, A_).contiguous().permute(1, 2, 3, 0)
         best, aws = [], []
         for b in range(B):
             L = int(lens[b])
             enc_b = enc_out[b:b + 1, :L].contiguous()
-            enc_a_b = enc_a[b:b + 1, :L].contiguous()
+            enc_a_b = enc_a[b:b + 1, :L]
             state = dict(h=[x[b:b + 1] for x in init['h']], c=[x[b:b + 1] for x in init['c']],
                          dec=init['dec'][b:b + 1], ctx=init['ctx'][b:b + 1],
                          aw=init['aw'][b:b + 1, :L])
@@ -701,7 +712,7 @@ class AttentionSeq2seq(ModelBase):
                     # its residual decoder sums the lower layer over the batch
                     # (rnn_decoder.py:100-102): one step per hypothesis here too
                     outs = [self._infer_step(task, dir, t, y[i:i + 1], _rows(st, i), enc_b,
-                                             enc_a_b.unsqueeze(3), [L]) for i in range(n)]
+                                             _enc_a_rows(enc_a_b, 1), [L]) for i in range(n)]
                     state = {k: ([torch.cat([o[0][k][l] for o in outs]) for l in range(len(v))]
                                  if isinstance(v, list) else torch.cat([o[0][k] for o in outs]))
                              for k, v in outs[0][0].items()}
@@ -709,8 +720,8 @@ class AttentionSeq2seq(ModelBase):
                 else:
                     state, logits = self._infer_step(
                         task, dir, t, y, st, enc_b.expand(n, L, E).contiguous(),
-                        enc_a_b.expand(n, L, A).contiguous().unsqueeze(3), [L] * n)
-                aw_t = state['aw']
+                        _enc_a_rows(enc_a_b, n), [L] * n)
+                aw_t = state['aw'][..., 0]            # head 0's weights (:907)
                 lg = logits.float().cpu().numpy()
                 mx = lg.max(axis=1, keepdims=True)                          # log_softmax (f32)
                 lp = lg - mx - np.log(np.exp(lg - mx).sum(axis=1, keepdims=True))
@@ -783,7 +794,7 @@ class AttentionSeq2seq(ModelBase):
         eos, sos = getattr(self, 'eos_%d' % task), getattr(self, 'sos_%d' % task)
         B = enc_out.shape[0]
         dev = enc_out.device
-        enc_a = att.W_enc_head0(enc_out).unsqueeze(3)
+        enc_a = att.enc_projection(enc_out)
         lens = x_lens if torch.is_tensor(x_lens) else torch.from_numpy(
             np.asarray(x_lens, np.int32)).to(dev)
         st = self._init_state(enc_out, task, dir)
@@ -794,7 +805,7 @@ class AttentionSeq2seq(ModelBase):
                                           lens)
             y = ops.row_argmax(logits).view(B, 1)
             toks.append(y)
-            aws.append(st['aw'])
+            aws.append(st['aw'][..., 0])                          # head 0's weights (:907)
             if bool((y == eos).all().item()):                     # :1017-1019
                 break
         return (torch.cat(toks, dim=1).cpu().numpy(),

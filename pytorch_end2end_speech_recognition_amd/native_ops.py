@@ -208,11 +208,13 @@ def gemm_problem(a, b, c, c_map, M, N_, K, alpha=1.0, beta=0.0, bias=None, bias2
                   BF16 if c_bf16 else F32)
 
 
-def run_gemm(problems, device, lse=None):
+def run_gemm(problems, device, lse=None, cd=None):
     """One launch of up to two products; long-K / few-tile products (weight
     gradients) get a split-K workspace from torch's caching allocator.
     lse (one product): f32 [ceil(N / 64), M, 2] tensor receiving the row
-    log-sum-exp partials of the written C (asr_gemm_lse_ws)."""
+    log-sum-exp partials of the written C (asr_gemm_lse_ws).  cd: the
+    products' compute dtype when it is not the session's (an op that is f32
+    in both modes)."""
     arr = (N.Gemm * len(problems))(*problems)
     parr = ctypes.cast(arr, ctypes.c_void_p)
     nb = N.query('asr_gemm_workspace_bytes', parr, len(problems))
@@ -222,8 +224,8 @@ def run_gemm(problems, device, lse=None):
         N.call('asr_gemm_lse_ws', parr, compute_dtype(), N.ptr(lse), N.ptr(ws), nb,
                N.stream_handle(device))
         return
-    N.call('asr_gemm_ws', parr, len(problems), compute_dtype(), N.ptr(ws), nb,
-           N.stream_handle(device))
+    N.call('asr_gemm_ws', parr, len(problems), compute_dtype() if cd is None else cd, N.ptr(ws),
+           nb, N.stream_handle(device))
 
 
 def _ctc_lse_epilogue(V):
@@ -1306,6 +1308,166 @@ class AttStepFn(torch.autograd.Function):
                                d_enc, rowmap(E), T, E, 1, batch=B,
                                batch_strides=(T, E, T * E))], dev)
         return d_enc, d_enc_a, None, d_dec, d_aw_prev, None, None, None, None, None, None
+
+
+class AttHeadsRefused(N.NativeError):
+    """asr_att_heads_forward does not take the shape (ASR_ERR_UNSUPPORTED)."""
+
+
+_att_heads = {'path': None}
+
+
+def last_att_heads_path():
+    """'heads' (one launch over all heads) or 'loop' (a refused shape: one
+    att_step per head): what the last att_heads_step ran (tests read it)."""
+    return _att_heads['path']
+
+
+def _att_heads_params(B, T, E, A, C, K, D, H, kind, sharpen, sigmoid, weights):
+    """asr_att_heads_t; weights: per head (w_dec, w_conv, conv_w, v) tensors
+    (None where the kind has none)."""
+    P = N.AttHeads(B, T, E, A, C, K, D, H,
+                   N.ATT_HEADS_DOT if kind == 'dot' else N.ATT_HEADS_ADDITIVE, float(sharpen),
+                   int(bool(sigmoid)))
+    for h, ws in enumerate(weights[:N.ATT_HEADS_MAX]):
+        for name, w in zip(('w_dec', 'w_conv', 'conv_w', 'v'), ws):
+            getattr(P, name)[h] = None if w is None else w.data_ptr()
+    return P
+
+
+class AttHeadsStepFn(torch.autograd.Function):
+    """One attention step over H heads in one launch (csrc/att_heads.hip;
+    attention_layer.py:141-251): (enc [B,T,E], enc_a [H,B,T,A] head-major,
+    lens int32 [B], dec_out [B,D], aw_prev [B,H,T]) -> (ctx [B,H*E],
+    aw [B,H,T]).  kind 'additive' (per head W_dec [A,D], V [1,A] and, for
+    location attention, W_conv [A,C], conv [C,1,1,K]; the flat ``weights`` are
+    those four per head, absent ones left out) or 'dot' (no weights, A = D).
+    f32 in both compute modes, its backward products included.  Weight
+    gradients accumulate into their .grad."""
+
+    @staticmethod
+    def forward(ctx, enc, enc_a, lens, dec_out, aw_prev, kind, sharpen, sigmoid, C, *weights):
+        N.require_device(enc, enc_a, lens, dec_out, aw_prev)
+        enc, enc_a = enc.contiguous(), enc_a.contiguous()
+        dec_out, aw_prev = dec_out.contiguous(), aw_prev.contiguous()
+        B, T, E = enc.shape
+        H, A = enc_a.shape[0], enc_a.shape[3]
+        D = dec_out.shape[1]
+        per = 0 if kind == 'dot' else (4 if C else 2)
+        assert len(weights) == per * H
+        heads = []
+        for h in range(H):
+            w = [t.contiguous() for t in weights[per * h:per * (h + 1)]]
+            heads.append((None,) * 4 if kind == 'dot' else
+                         (w[0], w[1], w[2], w[3]) if C else (w[0], None, None, w[1]))
+        K = heads[0][2].shape[-1] if C else 1
+        P = _att_heads_params(B, T, E, A, C, K, D, H, kind, sharpen, sigmoid, heads)
+        dev = enc.device
+        ctx_out = torch.empty(B, H * E, dtype=torch.float32, device=dev)
+        aw_out = torch.empty(B, H, T, dtype=torch.float32, device=dev)
+        rc = N.lib().asr_att_heads_forward(
+            ctypes.byref(P), N.ptr(enc), N.ptr(enc_a), N.ptr(lens), N.ptr(dec_out),
+            N.ptr(aw_prev), N.ptr(ctx_out), N.ptr(aw_out), None, 0, N.stream_handle(dev))
+        if rc != N.ASR_OK:
+            msg = N.lib().asr_last_error().decode(errors='replace')
+            raise (AttHeadsRefused if rc == N.ASR_ERR_UNSUPPORTED else N.NativeError)(
+                'asr_att_heads_forward failed (rc=%d): %s' % (rc, msg))
+        ctx.save_for_backward(enc, enc_a, lens, dec_out, aw_prev, aw_out)
+        ctx.heads = heads
+        ctx.P = P
+        return ctx_out, aw_out
+
+    @staticmethod
+    def backward(ctx, d_ctx, d_aw):
+        enc, enc_a, lens, dec_out, aw_prev, aw_out = ctx.saved_tensors
+        P, heads = ctx.P, ctx.heads
+        B, T, E, A, C, K, D, H = P.B, P.T, P.E, P.A, P.C, P.K, P.D, P.H
+        dot = P.kind == N.ATT_HEADS_DOT
+        dev = enc.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_ctx = d_ctx.contiguous() if d_ctx is not None else torch.zeros(B, H * E, **f32)
+        d_aw = d_aw.contiguous() if d_aw is not None else None
+        d_enc_a = torch.empty(H, B, T, A, **f32)
+        d_dec = torch.empty(B, D, **f32)
+        d_aw_prev = torch.empty(B, H, T, **f32)
+        dctx_tot = torch.empty(B, H, E, **f32)
+        dwd = dv_part = dwc_part = dcw_part = None
+        if not dot:
+            dwd = torch.empty(H, B, A, **f32)
+            dv_part = torch.empty(H, B, A, **f32)
+            if C:
+                dwc_part = torch.empty(H, B, A * C, **f32)
+                dcw_part = torch.empty(H, B, C * K, **f32)
+        nb = N.query('asr_att_heads_workspace_bytes', ctypes.byref(P), 1)
+        ws = _ws(nb, dev)
+        N.call('asr_att_heads_backward', ctypes.byref(P), N.ptr(enc), N.ptr(enc_a), N.ptr(lens),
+               N.ptr(dec_out), N.ptr(aw_prev), N.ptr(aw_out), N.ptr(d_ctx), N.ptr(d_aw),
+               N.ptr(d_enc_a), N.ptr(d_dec), N.ptr(d_aw_prev), N.ptr(dctx_tot), N.ptr(dwd),
+               N.ptr(dv_part), N.ptr(dwc_part), N.ptr(dcw_part), N.ptr(ws), nb,
+               N.stream_handle(dev))
+        if not dot:
+            probs = [gemm_problem(operand(dwd[h], 1, rowmap(A)), operand(dec_out, 1, rowmap(D)),
+                                  grad_buffer(heads[h][0]), rowmap(D), A, D, B, beta=1.0)
+                     for h in range(H)]
+            for i in range(0, H, 2):           # dW_dec_h += dwd_h^T dec, two heads a launch
+                run_gemm(probs[i:i + 2], dev, cd=F32)
+            for h in range(H):
+                colsum_accumulate(dv_part[h], grad_buffer(heads[h][3]))
+                if C:
+                    colsum_accumulate(dwc_part[h], grad_buffer(heads[h][1]))
+                    colsum_accumulate(dcw_part[h], grad_buffer(heads[h][2]))
+        d_enc = torch.empty_like(enc)          # d enc[b] = aw[b]^T dctx_tot[b]  (K = H)
+        run_gemm([gemm_problem(operand(aw_out, 1, rowmap(T)), operand(dctx_tot, 1, rowmap(E)),
+                               d_enc, rowmap(E), T, E, H, batch=B,
+                               batch_strides=(H * T, H * E, T * E))], dev, cd=F32)
+        return (d_enc, d_enc_a, None, d_dec, d_aw_prev, None, None, None, None) + (None,) * (
+            len(heads) * (0 if dot else (4 if C else 2)))
+
+
+def att_heads_step(enc, enc_a, lens, dec_out, aw_prev, heads, kind, sharpen=1.0, sigmoid=False):
+    """One attention step over all heads at the layer boundary:
+    (enc [B,T,E], enc_a [B,T,A,H], lens int32 [B], dec_out [B,D], aw_prev
+    [B,T,H]) -> (ctx [B,H*E] head-major, aw [B,T,H]).  heads: per head a dict
+    of weight tensors -- 'additive': w_dec [A,D], v [1,A] and, for location
+    attention, w_conv [A,C], conv_w [C,1,1,K]; 'dot': empty.  An enc_a that is
+    the permuted view of a head-major [H,B,T,A] tensor
+    (AttentionMechanism.enc_projection) is passed on without a copy, as is the
+    aw this op returned.  A shape the kernels refuse runs one att_step per head
+    ('additive') or raises ('dot': there is no other dot-product kernel)."""
+    if kind not in ('additive', 'dot'):
+        raise ValueError("kind must be 'additive' or 'dot'")
+    H = len(heads)
+    C = 0
+    flat = []
+    if kind == 'additive':
+        C = heads[0]['conv_w'].shape[0] if heads[0].get('conv_w') is not None else 0
+        for hd in heads:
+            flat += [hd['w_dec'], hd['w_conv'], hd['conv_w'], hd['v']] if C else [hd['w_dec'],
+                                                                                  hd['v']]
+    try:
+        ctx, aw = AttHeadsStepFn.apply(enc, enc_a.permute(3, 0, 1, 2), lens, dec_out,
+                                       aw_prev.permute(0, 2, 1), kind, float(sharpen),
+                                       bool(sigmoid), C, *flat)
+        _att_heads['path'] = 'heads'
+        return ctx, aw.permute(0, 2, 1)
+    except AttHeadsRefused as e:
+        if kind == 'dot':
+            raise N.NativeError('dot-product attention: the shape is outside the multi-head '
+                                'kernel and there is no per-head kernel for it (%s)' % e)
+    _att_heads['path'] = 'loop'
+    A = enc_a.shape[2]
+    ctxs, aws = [], []
+    for h, hd in enumerate(heads):
+        if C:
+            w_conv, conv_w = hd['w_conv'], hd['conv_w']
+        else:       # content: one all-zero conv channel adds an exact 0.0
+            w_conv = torch.zeros(A, 1, device=enc.device)
+            conv_w = torch.zeros(1, 1, 1, 1, device=enc.device)
+        c, a = att_step(enc, enc_a[..., h], lens, dec_out, aw_prev[..., h], hd['w_dec'], w_conv,
+                        conv_w, hd['v'], sharpen, sigmoid)
+        ctxs.append(c)
+        aws.append(a)
+    return torch.cat(ctxs, dim=-1), torch.stack(aws, dim=-1)
 
 
 class LSTMCellFn(torch.autograd.Function):
