@@ -207,37 +207,40 @@ typedef struct {
   int c_dtype;
 } asr_gemm_t;
 
-int asr_gemm(const asr_gemm_t* problems, int nprob, int compute_dtype, void* stream);
+/* One call's settings (NULL = all zero = the defaults); a value other than 0 or
+ * 1 is ASR_ERR_ARG before any launch.
+ *   small_tiles: the call uses only the 128 x 128 kernel (64 KB of LDS per
+ *     work-group), so that its work-groups fit beside a persistent recurrence
+ *     work-group on every CU (weight gradients co-resident with the backward
+ *     recurrence).
+ *   nosplit: the call takes no split-K slabs, and asr_gemm_workspace_bytes
+ *     counts none (rows of one product computed by several launches then sum
+ *     every output element in the order one launch would: bitwise the same dX
+ *     either way).
+ *   n64_kmode: products with N <= 64 (M >= 4096) whose B is K-major also take
+ *     the 256 x 64 kernel. */
+typedef struct { int small_tiles, nosplit, n64_kmode; } asr_gemm_opts_t;
+
+int asr_gemm(const asr_gemm_t* problems, int nprob, int compute_dtype, void* stream,
+             const asr_gemm_opts_t* opts);
 
 /* Same product with a workspace for deterministic split-K: weight-gradient
  * GEMMs (dW = dgates^T x over B*T rows, K ~ 32000) have few output tiles and
  * a long K; they are split along K into fixed f32 slabs and summed in a fixed
  * order by a second kernel (bit-reproducible run to run).  The split is a pure
- * function of the shapes; asr_gemm_workspace_bytes returns 0 when no problem
- * splits (then workspace may be NULL and this equals asr_gemm). */
-size_t asr_gemm_workspace_bytes(const asr_gemm_t* problems, int nprob);
+ * function of the shapes and opts; asr_gemm_workspace_bytes returns 0 when no
+ * problem splits (then workspace may be NULL and this equals asr_gemm). */
+size_t asr_gemm_workspace_bytes(const asr_gemm_t* problems, int nprob,
+                                const asr_gemm_opts_t* opts);
 int asr_gemm_ws(const asr_gemm_t* problems, int nprob, int compute_dtype, void* workspace,
-                size_t ws_bytes, void* stream);
+                size_t ws_bytes, void* stream, const asr_gemm_opts_t* opts);
 /* asr_gemm_ws of ONE product (beta 0, no dropout, f32 C, batch 1) whose
  * epilogue also writes, for every row m < M and 64-column slab q < ceil(N/64),
  * the online log-sum-exp pair of the values written to C: lse[2 (q M + m)] =
  * max, lse[2 (q M + m) + 1] = sum exp(c - max) (the CTC normaliser of an
  * output layer, formed where the logits are produced; asr_ctc_forward_lse). */
 int asr_gemm_lse_ws(const asr_gemm_t* problem, int compute_dtype, float* lse, void* workspace,
-                    size_t ws_bytes, void* stream);
-
-/* on != 0: later asr_gemm / asr_gemm_ws calls FROM THIS HOST THREAD use only the
- * 128 x 128 kernel (64 KB of LDS per work-group) until reset with 0, so that
- * their work-groups fit beside a persistent recurrence work-group on every CU
- * (weight gradients co-resident with the backward recurrence). */
-int asr_gemm_set_small_tiles(int on);
-/* on != 0: later asr_gemm calls FROM THIS HOST THREAD take no split-K slabs
- * (rows of one product computed by several launches then sum every output
- * element in the order one launch would: bitwise the same dX either way). */
-int asr_gemm_set_nosplit(int on);
-/* asr_gemm_set_n64_kmode(1): products with N <= 64 (M >= 4096) whose B is
- * K-major also take the 256 x 64 kernel (launches from this host thread). */
-int asr_gemm_set_n64_kmode(int on);
+                    size_t ws_bytes, void* stream, const asr_gemm_opts_t* opts);
 
 /* Enqueue on `stream` a one-wave gate that releases once the NEXT persistent
  * backward recurrence (asr_lstm_backward*, any stream) has all its work-groups
@@ -635,7 +638,12 @@ typedef struct {
  *   tok_ss [B][S] (nullable) receives the sampled tokens.  In backward,
  *   d_pre [B][S][4D] = dG with sampled steps zeroed (the gradient of pre_emb)
  *   and dg_ss [B][S][4D] = dG at sampled steps only (for W_ih[:, :Y] and the
- *   biases through emb_ss); both NULL when no step is sampled. */
+ *   biases through emb_ss); both NULL when no step is sampled.
+ * conv_feat (NULL = off): a persistent forward pass keeps the conv features of
+ *   every decoder step here and a persistent backward pass reads them back
+ *   instead of recomputing them from aw; the buffer holds
+ *   asr_attdec_conv_feat_bytes(dims) bytes.  A backward may only be given the
+ *   buffer of a forward that ran persistent (asr_attdec_persist_last). */
 typedef struct {
   float dropout_hidden;
   unsigned long long seed_hidden;
@@ -664,6 +672,7 @@ typedef struct {
   long long* tok_ss;
   float* d_pre;
   float* dg_ss;
+  float* conv_feat;
 } asr_attdec_opts_t;
 
 /* Diagnostics: phase stamps (s_memrealtime ticks, 100 MHz) of the per-step
@@ -839,13 +848,6 @@ int asr_attdec_last_launch(int* out4);
  * persistent launch (bf16, B <= 32, no scheduled sampling; ASR_ATT_PERSIST=0
  * disables it). */
 int asr_attdec_persist_last(int* out2);
-/* Round 6: the conv features of every decoder step kept by the next
- * persistent forward pass from this host thread and read back by the next
- * persistent backward pass (instead of recomputing them from aw); buf holds
- * asr_attdec_conv_feat_bytes(dims) bytes, NULL turns it off.  The caller sets
- * it before each pass and resets it after; a backward may only be given the
- * buffer of a forward that ran persistent (asr_attdec_persist_last). */
-int asr_attdec_set_conv_feat(float* buf);
 size_t asr_attdec_conv_feat_bytes(const asr_attdec_dims_t* dims);
 int asr_attdec_backward_ex(const asr_attdec_dims_t* dims, const asr_attdec_opts_t* opts,
                            int compute_dtype, const float* enc, const float* enc_a,

@@ -52,13 +52,11 @@ SIGNATURES = {
                                          c_size, c_vp, c_vp, c_size, c_vp]),
     'asr_ctc_fwd_bwd': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int,
                                 c_int, c_int, c_vp, c_vp, c_vp, c_size, c_vp]),
-    'asr_gemm': (c_int, [c_vp, c_int, c_int, c_vp]),
-    'asr_gemm_workspace_bytes': (c_size, [c_vp, c_int]),
-    'asr_gemm_ws': (c_int, [c_vp, c_int, c_int, c_vp, c_size, c_vp]),
-    'asr_gemm_lse_ws': (c_int, [c_vp, c_int, c_vp, c_vp, c_size, c_vp]),
-    'asr_gemm_set_small_tiles': (c_int, [c_int]),
-    'asr_gemm_set_nosplit': (c_int, [c_int]),
-    'asr_gemm_set_n64_kmode': (c_int, [c_int]),
+    # the four GEMM entry points end in (..., opts: GemmOpts* or NULL)
+    'asr_gemm': (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
+    'asr_gemm_workspace_bytes': (c_size, [c_vp, c_int, c_vp]),
+    'asr_gemm_ws': (c_int, [c_vp, c_int, c_int, c_vp, c_size, c_vp, c_vp]),
+    'asr_gemm_lse_ws': (c_int, [c_vp, c_int, c_vp, c_vp, c_size, c_vp, c_vp]),
     'asr_lstm_wgrad_gate': (c_int, [c_vp]),
     'asr_colsum_workspace_bytes': (c_size, [c_int, c_int]),
     'asr_colsum_accumulate': (c_int, [c_vp, c_ll, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_size,
@@ -234,7 +232,6 @@ SIGNATURES = {
     'asr_ctc_last_path': (c_int, [c_vp]),
     'asr_ctc_last_lattice_waves': (c_int, []),
     'asr_gemm_last_family': (c_int, []),
-    'asr_attdec_set_conv_feat': (c_int, [c_vp]),
     'asr_attdec_conv_feat_bytes': (c_size, [c_vp]),
     'asr_lstm_ws_zero_bytes': (c_size, [c_int, c_int]),
     'asr_lstm_bwd_progress_arrivals': (c_ll, [c_int, c_int, c_int]),
@@ -285,7 +282,7 @@ class AttHeads(ctypes.Structure):
 
 
 class AttDecOpts(ctypes.Structure):
-    """asr_attdec_opts_t (decoder dropout + scheduled sampling)"""
+    """asr_attdec_opts_t (decoder dropout + scheduled sampling + kept conv features)"""
     _fields_ = [('dropout_hidden', c_float), ('seed_hidden', ctypes.c_ulonglong),
                 ('ss_steps_host', c_vp), ('Y', c_int), ('Dz', c_int), ('V', c_int),
                 ('w_d', c_vp), ('b_d', c_vp), ('drop_d', c_float), ('seed_d', ctypes.c_ulonglong),
@@ -293,7 +290,8 @@ class AttDecOpts(ctypes.Structure):
                 ('w_fc', c_vp), ('b_fc', c_vp), ('emb_w', c_vp), ('emb_trans', c_int),
                 ('drop_emb', c_float), ('seed_emb', ctypes.c_ulonglong), ('w_ih_emb', c_vp),
                 ('ld_ih', c_ll), ('b_ih', c_vp), ('b_hh', c_vp), ('pre_ss', c_vp),
-                ('emb_ss', c_vp), ('tok_ss', c_vp), ('d_pre', c_vp), ('dg_ss', c_vp)]
+                ('emb_ss', c_vp), ('tok_ss', c_vp), ('d_pre', c_vp), ('dg_ss', c_vp),
+                ('conv_feat', c_vp)]
 
 
 class LstmOpts(ctypes.Structure):
@@ -301,6 +299,11 @@ class LstmOpts(ctypes.Structure):
     _fields_ = [('ws_prezeroed', c_int), ('bwd_pin_kb', c_int), ('bwd_units', c_int),
                 ('dy_flags', c_vp), ('dy_c0', c_int), ('dy_epoch', c_int), ('progress', c_vp),
                 ('progress_q1', c_int), ('progress_q2', c_int)]
+
+
+class GemmOpts(ctypes.Structure):
+    """asr_gemm_opts_t (one GEMM call's settings; all zero: the defaults)"""
+    _fields_ = [('small_tiles', c_int), ('nosplit', c_int), ('n64_kmode', c_int)]
 
 
 class AttBeamOpts(ctypes.Structure):

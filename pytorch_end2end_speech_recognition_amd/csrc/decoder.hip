@@ -1188,11 +1188,6 @@ struct PdSs {
 };
 static_assert(sizeof(PdSs) <= 512, "AttWs::ssd holds one PdSs");
 
-// asr_attdec_set_conv_feat: the next persistent decoder pass from this host
-// thread writes (forward) / reads (backward) the conv features of every step
-// here ([B][S][8 chunks][FCH][FS] f32), NULL: recomputed in the backward.
-thread_local float* g_pd_fsave = nullptr;
-
 // Host staging of the PdSs records: a ring of pinned slots, each reused only
 // after the copy that read it has completed (its event).
 int pd_ss_upload(const PdSs& v, void* dst, hipStream_t s) {
@@ -2866,6 +2861,9 @@ extern "C" int asr_attdec_forward_ex(const asr_attdec_dims_t* dims, const asr_at
   if (rc) return rc;
   const float drop_h = opts ? opts->dropout_hidden : 0.f;
   const unsigned long long seed_h = opts ? opts->seed_hidden : 0ull;
+  // a persistent pass writes (forward) / reads (backward) the conv features of
+  // every step here ([B][S][8 chunks][FCH][FS] f32); NULL: recomputed in the backward
+  float* const fsave = opts ? opts->conv_feat : nullptr;
   ASR_REQUIRE(enc && enc_a && lens && w_ih_ctx && w_hh && w_dec && w_conv && conv_w && v &&
                   pre_emb && dec && c_all && gates && x && ctx_all && aw_all && workspace,
               ASR_ERR_ARG, "attdec_forward: null pointer");
@@ -2950,7 +2948,7 @@ extern "C" int asr_attdec_forward_ex(const asr_attdec_dims_t* dims, const asr_at
   hipLaunchKernelGGL((attdec_fwd_persist<CC, NQ, SA, SE, SD, SK, F>), grid, dim3(PD_THREADS), lds,  \
                      s, d, (const void*)workspace, pre_emb, h0, enc, enc_a, lens, w_dec, w_conv,  \
                      conv_w, v, dec, c_all, gates, x, ctx_all, aw_all, pbuf, ebuf, ctr,          \
-                     lstm_persist_status_word(), drop_h, seed_h, ssdev, g_pd_fsave)
+                     lstm_persist_status_word(), drop_h, seed_h, ssdev, fsave)
 #define ASR_PD(CC, NQ, SA, SE, SD, SK)                  \
   do {                                                  \
     if (bf) ASR_PD2(CC, NQ, SA, SE, SD, SK, false);     \
@@ -3012,13 +3010,7 @@ extern "C" int asr_attdec_persist_last(int* out2) {
   return ASR_OK;
 }
 
-// The conv-feature buffer of the next persistent decoder pass from this host
-// thread (NULL: none); asr_attdec_conv_feat_bytes: its size for dims.
-extern "C" int asr_attdec_set_conv_feat(float* buf) {
-  g_pd_fsave = buf;
-  return ASR_OK;
-}
-
+// Bytes of asr_attdec_opts_t::conv_feat for dims.
 extern "C" size_t asr_attdec_conv_feat_bytes(const asr_attdec_dims_t* dims) {
   if (!dims || dims->B <= 0 || dims->S <= 0 || dims->T <= 0) return 0;
   const size_t fch = (size_t)(dims->T + PD_CHUNKS - 1) / PD_CHUNKS;
@@ -3070,6 +3062,9 @@ extern "C" int asr_attdec_backward_ex(const asr_attdec_dims_t* dims, const asr_a
               "attdec_backward: scheduled sampling needs d_pre and dg_ss");
   const float drop_h = opts ? opts->dropout_hidden : 0.f;
   const unsigned long long seed_h = opts ? opts->seed_hidden : 0ull;
+  // a persistent pass writes (forward) / reads (backward) the conv features of
+  // every step here ([B][S][8 chunks][FCH][FS] f32); NULL: recomputed in the backward
+  float* const fsave = opts ? opts->conv_feat : nullptr;
   ASR_REQUIRE(enc && enc_a && lens && w_ih_ctx && w_hh && w_dec && w_conv && conv_w && v &&
                   dec && c_all && aw_all && d_dec_in && d_ctx_in && gates_dg && dctx_tot &&
                   d_enc_a && dwd_all && dv_part && dwc_part && dcw_part && workspace,
@@ -3106,7 +3101,7 @@ extern "C" int asr_attdec_backward_ex(const asr_attdec_dims_t* dims, const asr_a
     g.c_map.stride_t = d.A;
     g.M = d.B * d.S; g.N = d.A; g.K = d.D;
     g.alpha = 1.f; g.beta = 0.f; g.batch = 1;
-    rc = asr_gemm(&g, 1, ASR_DT_F32, stream);
+    rc = asr_gemm(&g, 1, ASR_DT_F32, stream, nullptr);
     if (rc) return rc;
   }
   const long long nw = 4LL * d.D * ED;
@@ -3140,10 +3135,10 @@ extern "C" int asr_attdec_backward_ex(const asr_attdec_dims_t* dims, const asr_a
                      s, d, (const void*)wcatT, enc, enc_a, lens, w_dec, w_conv, conv_w, v, c_all, \
                      aw_all, wd_all, d_dec_in, d_ctx_in, gates_dg, dctx_tot, d_enc_a, d_h0,      \
                      dwd_all, dv_part, dwc_part, dcw_part, r, sbuf, dwd_chunk, dFbuf, ctr,       \
-                     lstm_persist_status_word(), drop_h, seed_h, (const float*)g_pd_fsave)
+                     lstm_persist_status_word(), drop_h, seed_h, (const float*)fsave)
 #define ASR_PB2(CC, NQ, SA, SE, SD, SK, F)                                       \
   do {                                                                          \
-    if (g_pd_fsave) ASR_PB3(CC, NQ, SA, SE, SD, SK, F, true);                   \
+    if (fsave) ASR_PB3(CC, NQ, SA, SE, SD, SK, F, true);                        \
     else ASR_PB3(CC, NQ, SA, SE, SD, SK, F, false);                             \
   } while (0)
 #define ASR_PB(CC, NQ, SA, SE, SD, SK)                  \
@@ -3391,7 +3386,7 @@ extern "C" int asr_att_step_backward(const asr_attdec_dims_t* dims, const float*
     g.c_map.stride_t = d.A;
     g.M = d.B * 2; g.N = d.A; g.K = d.D;
     g.alpha = 1.f; g.beta = 0.f; g.batch = 1;
-    rc = asr_gemm(&g, 1, ASR_DT_F32, stream);
+    rc = asr_gemm(&g, 1, ASR_DT_F32, stream, nullptr);
     if (rc) return rc;
   }
   const size_t en_lds = en_lds_floats(d) * 4;

@@ -2258,21 +2258,32 @@ struct SplitPlan {
   size_t bytes;
 };
 
-// asr_gemm_set_nosplit(1): launches from this host thread take no split-K
-// slabs until reset (products whose rows are computed in several launches
-// that must sum each output element in the same order as one launch would)
-thread_local int g_nosplit = 0;
+// One call's settings as planning and launch read them: the caller's
+// asr_gemm_opts_t (NULL: all off), with ASR_GEMM_NOSPLIT=1 (diagnostics: no
+// split-K slabs) or-ed into nosplit, and asr_gemm_lse_ws's row-LSE partials.
+struct CallOpts {
+  bool small_tiles, nosplit, n64_kmode;
+  float* lse;
+};
 
-SplitPlan plan_split(const asr_gemm_t* g, int nprob) {
+int call_opts(const asr_gemm_opts_t* opts, float* lse, CallOpts* o) {
+  const asr_gemm_opts_t v = opts ? *opts : asr_gemm_opts_t{0, 0, 0};
+  ASR_REQUIRE(!(v.small_tiles & ~1) && !(v.nosplit & ~1) && !(v.n64_kmode & ~1), ASR_ERR_ARG,
+              "gemm opts: small_tiles %d, nosplit %d, n64_kmode %d (each 0 or 1)", v.small_tiles,
+              v.nosplit, v.n64_kmode);
+  const char* ns = getenv("ASR_GEMM_NOSPLIT");
+  *o = CallOpts{v.small_tiles != 0, v.nosplit || (ns && ns[0] == '1'), v.n64_kmode != 0, lse};
+  return ASR_OK;
+}
+
+SplitPlan plan_split(const asr_gemm_t* g, int nprob, const CallOpts& o) {
   SplitPlan sp{};
-  const char* ns = getenv("ASR_GEMM_NOSPLIT");   // diagnostics: no split-K slabs
-  const bool nosplit = (ns && ns[0] == '1') || g_nosplit;
   for (int i = 0; i < nprob; ++i) {
     // per problem: the problems of one launch run side by side (blockIdx.z), so
     // a few-tile dW next to a many-tile dX still gets its own K split
     const int tiles = ceil_div(g[i].M, BM) * ceil_div(g[i].N, BN);
     int ks = 1;
-    if (!nosplit && g[i].c_dtype != ASR_DT_BF16 && g[i].batch <= 1 && tiles > 0 &&
+    if (!o.nosplit && g[i].c_dtype != ASR_DT_BF16 && g[i].batch <= 1 && tiles > 0 &&
         tiles < 512 && g[i].K >= 1024) {
       // a few-tile, long-K product (the decoder / projection weight gradients,
       // K = B*S or B*T) is latency-bound per work-group: chunks >= 128
@@ -2307,27 +2318,47 @@ bool fast_operand_ok(const asr_operand_t& o, const Operand& op, long long batch_
   return true;
 }
 
+// The fast kernel families' instantiations.  Every kernel takes the launch's
+// Params; `mode` below is the operand mode pair 2 * a.trans + b.trans.
+using GemmKernel = void (*)(Params);
+#define ASR_MODES(K, ...) \
+  { K<0, 0, __VA_ARGS__>, K<0, 1, __VA_ARGS__>, K<1, 0, __VA_ARGS__>, K<1, 1, __VA_ARGS__> }
+constexpr GemmKernel K_8R[4] = {gemm_bf16_8r<0, 0>, gemm_bf16_8r<0, 1>, gemm_bf16_8r<1, 0>,
+                                gemm_bf16_8r<1, 1>};   // [mode]
+constexpr GemmKernel K_8W[4] = {gemm_bf16_8w<0, 0>, gemm_bf16_8w<0, 1>, gemm_bf16_8w<1, 0>,
+                                gemm_bf16_8w<1, 1>};   // [mode]
+// [stages - 2][b.trans][a.trans]: the two kernels of a [b.trans] row share their LDS size
+constexpr GemmKernel K_N64[2][2][2] = {
+    {{gemm_bf16_n64<0, 0, 2>, gemm_bf16_n64<1, 0, 2>}, {gemm_bf16_n64<0, 1, 2>, gemm_bf16_n64<1, 1, 2>}},
+    {{gemm_bf16_n64<0, 0, 3>, gemm_bf16_n64<1, 0, 3>}, {gemm_bf16_n64<0, 1, 3>, gemm_bf16_n64<1, 1, 3>}}};
+constexpr GemmKernel K_FAST[2][4] = {ASR_MODES(gemm_bf16_fast, 2),    // [stages == 4][mode]
+                                     ASR_MODES(gemm_bf16_fast, 4)};
+// [three-stage ring][tile: 64 x 256, 128 x 128, 256 x 64][mode]
+constexpr GemmKernel K_F32[2][3][4] = {
+    {ASR_MODES(gemm_f32_fast, 1, 2), ASR_MODES(gemm_f32_fast, 2, 2), ASR_MODES(gemm_f32_fast, 4, 2)},
+    {ASR_MODES(gemm_f32_fast, 1, 3), ASR_MODES(gemm_f32_fast, 2, 3), ASR_MODES(gemm_f32_fast, 4, 3)}};
+#undef ASR_MODES
+
+// Raises the dynamic-LDS limit of the n kernels at k to `bytes`, once per
+// process (*done); false while the runtime refuses one of them.
+bool raise_lds(bool* done, const GemmKernel* k, int n, int bytes) {
+  if (*done) return true;
+  bool ok = true;
+  for (int i = 0; i < n; ++i)
+    ok &= hipFuncSetAttribute((const void*)k[i], hipFuncAttributeMaxDynamicSharedMemorySize,
+                              bytes) == hipSuccess;
+  return *done = ok;
+}
+
 // LDS stages of the bf16 fast path (ASR_GEMM_STAGES = 2 | 4, default 2: the
 // 4-deep ring halves occupancy and measured 226 vs 391 TF/s on the encoder
 // products); the 128 KB ring needs the dynamic-LDS limit raised once per kernel.
 int fast_stages() {
   static int n = 0;
   if (n == 0) {
+    static bool raised = false;
     const char* e = getenv("ASR_GEMM_STAGES");
-    n = (e && atoi(e) == 4) ? 4 : 2;
-    if (n == 4) {
-      const int bytes = 4 * 2 * FTILE;
-      bool ok = true;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_fast<0, 0, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_fast<0, 1, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_fast<1, 0, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_fast<1, 1, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-      if (!ok) n = 2;
-    }
+    n = (e && atoi(e) == 4 && raise_lds(&raised, K_FAST[1], 4, 4 * 2 * FTILE)) ? 4 : 2;
   }
   return n;
 }
@@ -2392,7 +2423,8 @@ int fast_modes(const asr_gemm_t* g, const Params& P) {
 // 5x512 weight-gradient shapes it measured 511 vs 482 TF/s (tools/gemm_bench.py)
 // but the whole step did not move beyond noise, and the 4x320 / VGG configs
 // ran 0.2-0.5 ms/step slower with it (fewer work-groups per product).
-bool kk256_ok(const asr_gemm_t* g, int nprob) {
+bool kk256_ok(const asr_gemm_t* g, int nprob, const CallOpts& o) {
+  if (o.lse) return false;   // asr_gemm_lse_ws: its own epilogue writes no row-LSE partials
   for (int i = 0; i < nprob; ++i)
     if (g[i].c_dtype == ASR_DT_BF16) return false;   // its own f32 epilogue
   const char* e = getenv("ASR_GEMM_KK256");
@@ -2413,33 +2445,27 @@ int split_target() {
   return v > 0 ? v : 512;
 }
 
-// asr_gemm_set_small_tiles(1): launches from this host thread keep to the
-// 128 x 128 kernel (64 KB of LDS) until reset -- the weight-gradient GEMMs that
-// run co-resident with the persistent backward recurrence (native_ops,
-// ASR_OVERLAP_WGRAD=2) must fit beside its work-group on every CU.
-thread_local int g_small_tiles = 0;
-thread_local float* g_row_lse = nullptr;   // asr_gemm_lse_ws: the product's row-LSE partials
-thread_local int g_n64_kmode = 0;
-
 // Products with N <= 64 and many rows take the 256 x 64 kernel (B in R mode;
-// ASR_GEMM_N64=0 keeps them on the 128 x 128 kernel; read per launch).
-bool n64_ok(const asr_gemm_t* g, int nprob, int bmode) {
-  if (g_small_tiles) return false;
+// ASR_GEMM_N64=0 keeps them on the 128 x 128 kernel; read per launch).  Not
+// under small_tiles: weight-gradient GEMMs co-resident with the persistent
+// backward recurrence (native_ops, ASR_OVERLAP_WGRAD=2) keep to the 128 x 128
+// kernel's 64 KB of LDS, to fit beside its work-group on every CU.
+bool n64_ok(const asr_gemm_t* g, int nprob, int bmode, const CallOpts& o) {
+  if (o.small_tiles) return false;
   const char* e = getenv("ASR_GEMM_N64");
   if (e && e[0] == '0') return false;
   // K-mode B (its tile keeps the 128-column layout, 96 KB of LDS): opt-in per
-  // launch thread (asr_gemm_set_n64_kmode), used by the VGG weight gradients
-  if (bmode && !g_n64_kmode) return false;
+  // call (n64_kmode), used by the VGG weight gradients
+  if (bmode && !o.n64_kmode) return false;
   for (int i = 0; i < nprob; ++i)   // many rows, or a long K that split-K spreads
     if (g[i].N > 64 || (g[i].M < 4096 && g[i].K < 65536)) return false;
   return true;
 }
 
-
-bool big8_ok(const asr_gemm_t* g, int nprob) {
+bool big8_ok(const asr_gemm_t* g, int nprob, const CallOpts& o) {
   const char* e = getenv("ASR_GEMM_8W");
   if (e && e[0] == '0') return false;
-  if (g_small_tiles) return false;
+  if (o.small_tiles) return false;
   for (int i = 0; i < nprob; ++i) {
     if (g[i].c_dtype == ASR_DT_BF16) return false;   // its own f32 epilogue
     if (g[i].M < T8 || g[i].N < T8) return false;
@@ -2451,18 +2477,21 @@ bool big8_ok(const asr_gemm_t* g, int nprob) {
   return true;
 }
 
-int gemm_launch_own(const asr_gemm_t* problems, int nprob, int compute_dtype, void* workspace,
-                    size_t ws_bytes, void* stream) {
+// The launch's Params from its problems (checked) and the split-K plan; *maxwg:
+// work-groups per problem at 128 x 128 tiles (0: nothing to do), *maxb: batches.
+int fill_params(const asr_gemm_t* problems, int nprob, int compute_dtype, void* workspace,
+                size_t ws_bytes, const CallOpts& o, Params* Pp, int* maxwg, int* maxb) {
   SplitPlan sp{};
   if (workspace) {
-    sp = plan_split(problems, nprob);
+    sp = plan_split(problems, nprob, o);
     ASR_REQUIRE(ws_bytes >= sp.bytes, ASR_ERR_WORKSPACE, "gemm: workspace too small");
   } else {
     for (int i = 0; i < nprob; ++i) { sp.ksplit[i] = 1; sp.kchunk[i] = problems[i].K; }
   }
-  Params P;
+  Params& P = *Pp;
   P.nprob = nprob;
-  int maxwg = 0, maxb = 1;
+  *maxwg = 0;
+  *maxb = 1;
   for (int i = 0; i < nprob; ++i) {
     const asr_gemm_t& g = problems[i];
     ASR_REQUIRE(g.M >= 0 && g.N >= 0 && g.K >= 0, ASR_ERR_ARG, "gemm: negative size");
@@ -2498,259 +2527,211 @@ int gemm_launch_own(const asr_gemm_t* problems, int nprob, int compute_dtype, vo
     p.ksplit = sp.ksplit[i];
     p.kchunk = sp.kchunk[i];
     p.slab = p.ksplit > 1 ? (float*)((char*)workspace + sp.slab_off[i]) : nullptr;
-    maxwg = max(maxwg, ceil_div(g.M, BM) * ceil_div(g.N, BN) * p.ksplit);
-    maxb = max(maxb, p.batch);
+    *maxwg = max(*maxwg, ceil_div(g.M, BM) * ceil_div(g.N, BN) * p.ksplit);
+    *maxb = max(*maxb, p.batch);
   }
-  if (g_row_lse) {   // asr_gemm_lse_ws: one product, whole-K tiles (no split slabs)
-    P.p[0].lse = g_row_lse;
+  if (o.lse) {   // asr_gemm_lse_ws: one product, whole-K tiles (no split slabs)
+    P.p[0].lse = o.lse;
     P.p[0].ksplit = 1;
     P.p[0].kchunk = P.p[0].K;
     P.p[0].slab = nullptr;
-    maxwg = ceil_div(problems[0].M, BM) * ceil_div(problems[0].N, BN);
+    *maxwg = ceil_div(problems[0].M, BM) * ceil_div(problems[0].N, BN);
   }
   if (nprob == 1) { P.p[1] = P.p[0]; P.p[1].batch = 0; }
-  if (maxwg == 0) return ASR_OK;
+  return ASR_OK;
+}
+
+// The 256 x 256 kernels re-plan each problem's split for their tile (k-tile
+// depth bk) towards `target` work-groups, never beyond the workspace plan's
+// (128 x 128) split; returns the work-groups per problem.
+int resplit256(Params& P, int bk, int target) {
+  int maxwg = 0;
+  for (int i = 0; i < P.nprob; ++i) {
+    Problem& p = P.p[i];
+    const int tiles = ceil_div(p.M, 256) * ceil_div(p.N, 256);
+    int ks = 1;
+    if (p.ksplit > 1) {
+      ks = min(p.ksplit, max(1, ceil_div(target, tiles)));
+      const int kc = ceil_div(ceil_div(p.K, ks), bk) * bk;
+      ks = ceil_div(p.K, kc);
+      p.kchunk = kc;
+    }
+    if (ks <= 1) { ks = 1; p.kchunk = p.K; }
+    p.ksplit = ks;
+    maxwg = max(maxwg, tiles * ks);
+  }
+  return maxwg;
+}
+
+// Tile rows of the f32 fast kernel in 64s: 256 x 64 tiles (4) when every
+// N <= 64, 64 x 256 (1) when every M <= 64, else 128 x 128 (2).
+int f32_tile_rows(const asr_gemm_t* g, int nprob) {
+  bool n64 = true, m64 = true;
+  for (int i = 0; i < nprob; ++i) {
+    n64 &= g[i].N <= 64;
+    m64 &= g[i].M <= 64;
+  }
+  return n64 ? 4 : m64 ? 1 : 2;
+}
+
+// Which kernel family the launch takes (an ASR_PTAG_GEMM_* of prof.h), with
+// its operand mode pair in *mode.  *wg comes in as the work-groups per problem
+// at 128 x 128 tiles and leaves as the family's own (whose split it re-plans
+// where its tile is larger).
+int choose_family(const asr_gemm_t* g, int nprob, int compute_dtype, const CallOpts& o, Params& P,
+                  int* mode, int* wg) {
+  static_assert(T8 == 256 && BT2 == 256, "resplit256");
+  const int fast = compute_dtype == ASR_DT_BF16 ? fast_modes(g, P) : -1;
+  *mode = max(fast, 0);
+  if (fast >= 0 && big8_ok(g, nprob, o)) {
+    *wg = resplit256(P, BK8, split_target());
+    const char* er = getenv("ASR_GEMM_8R");   // ring form by default (ASR_GEMM_8R=0: two buffers)
+    return (er && er[0] == '0') ? ASR_PTAG_GEMM_8W : ASR_PTAG_GEMM_8R;
+  }
+  if (fast == 3 && kk256_ok(g, nprob, o)) {
+    *wg = resplit256(P, BK2, 256);
+    return ASR_PTAG_GEMM_KK256;
+  }
+  if (fast >= 0 && n64_ok(g, nprob, fast & 1, o)) {
+    *wg = 0;
+    for (int i = 0; i < nprob; ++i)
+      *wg = max(*wg, ceil_div(P.p[i].M, N64_BM) * max(1, P.p[i].ksplit));
+    return ASR_PTAG_GEMM_N64;
+  }
+  if (fast >= 0)
+    return (o.small_tiles ? 2 : fast_stages()) == 4 ? ASR_PTAG_GEMM_FAST4 : ASR_PTAG_GEMM_FAST2;
+  if (compute_dtype == ASR_DT_BF16) return ASR_PTAG_GEMM_GEN_BF16;
+  const int f32m = fast32_modes(g, P);
+  if (f32m < 0) return ASR_PTAG_GEMM_GEN_F32;
+  *mode = f32m;
+  const int tmr = 64 * f32_tile_rows(g, nprob), tnr = 256 * 64 / tmr;
+  *wg = 0;
+  for (int i = 0; i < nprob; ++i)
+    *wg = max(*wg, ceil_div(P.p[i].M, tmr) * ceil_div(P.p[i].N, tnr) * max(1, P.p[i].ksplit));
+  return ASR_PTAG_GEMM_F32F;
+}
+
+// ASR_GEMM_DEBUG=1 lists every product that misses the fast kernels; without
+// it a bf16-mode product of real size on the slow path is reported once.
+void report_generic(const asr_gemm_t* problems, int nprob, bool bf16) {
+  static bool warned = false;
+  if (bf16 && !warned && !getenv("ASR_GEMM_DEBUG")) {
+    for (int i = 0; i < nprob; ++i) {
+      const double fl = 2.0 * problems[i].M * problems[i].N * problems[i].K * problems[i].batch;
+      if (fl >= 32e6) {
+        warned = true;
+        fprintf(stderr, "[asr_gemm] warning: a bf16-mode product (M=%d N=%d K=%d batch=%d) runs "
+                "on the generic register-staged kernel, not the LDS-DMA fast kernels "
+                "(ASR_GEMM_DEBUG=1 lists every such product)\n", problems[i].M, problems[i].N,
+                problems[i].K, problems[i].batch);
+        break;
+      }
+    }
+  }
+  if (!getenv("ASR_GEMM_DEBUG")) return;
+  for (int i = 0; i < nprob; ++i)
+    if (bf16)
+      fprintf(stderr, "[asr_gemm generic] M=%d N=%d K=%d batch=%d a(dt=%d tr=%d tap=%d perm=%d) "
+              "b(dt=%d tr=%d tap=%d perm=%d)\n", problems[i].M, problems[i].N, problems[i].K,
+              problems[i].batch, problems[i].a.dtype, problems[i].a.trans,
+              problems[i].a.tap_group, problems[i].a.map.perm != nullptr, problems[i].b.dtype,
+              problems[i].b.trans, problems[i].b.tap_group, problems[i].b.map.perm != nullptr);
+    else
+      fprintf(stderr, "[asr_gemm generic f32] M=%d N=%d K=%d batch=%d a(dt=%d tr=%d tap=%d "
+              "perm=%d ld=%lld al=%d) b(dt=%d tr=%d tap=%d perm=%d ld=%lld al=%d)\n",
+              problems[i].M, problems[i].N, problems[i].K, problems[i].batch,
+              problems[i].a.dtype, problems[i].a.trans, problems[i].a.tap_group,
+              problems[i].a.map.perm != nullptr, problems[i].a.map.stride_t,
+              (int)aligned16(problems[i].a.ptr), problems[i].b.dtype, problems[i].b.trans,
+              problems[i].b.tap_group, problems[i].b.map.perm != nullptr,
+              problems[i].b.map.stride_t, (int)aligned16(problems[i].b.ptr));
+}
+
+// One launch of the chosen family's kernel for `mode` (no check of the launch).
+int launch_family(int family, int mode, dim3 grid, const asr_gemm_t* problems, int nprob,
+                  const Params& P, hipStream_t s) {
+  switch (family) {
+    case ASR_PTAG_GEMM_8R:
+    case ASR_PTAG_GEMM_8W: {
+      static bool raised8 = false, raisedr = false;
+      ASR_REQUIRE(raise_lds(&raised8, K_8W, 4, 4 * TILE8), ASR_ERR_HIP,
+                  "gemm: cannot raise the LDS limit of the 8-wave kernel");
+      if (family == ASR_PTAG_GEMM_8W) {
+        hipLaunchKernelGGL(K_8W[mode], grid, dim3(NT8), 4 * TILE8, s, P);
+        break;
+      }
+      ASR_REQUIRE(raise_lds(&raisedr, K_8R, 4, NSLOT * 2 * TILER), ASR_ERR_HIP,
+                  "gemm: cannot raise the LDS limit of the ring kernel");
+      hipLaunchKernelGGL(K_8R[mode], grid, dim3(NT8), NSLOT * 2 * TILER, s, P);
+      break;
+    }
+    case ASR_PTAG_GEMM_KK256: {
+      static bool raised = false;
+      const GemmKernel kk256 = gemm_bf16_kk256;
+      ASR_REQUIRE(raise_lds(&raised, &kk256, 1, NST2 * 2 * FTILE2), ASR_ERR_HIP,
+                  "gemm: cannot raise the LDS limit of the 256x256 kernel");
+      hipLaunchKernelGGL(gemm_bf16_kk256, grid, dim3(NT), (size_t)NST2 * 2 * FTILE2, s, P);
+      break;
+    }
+    case ASR_PTAG_GEMM_N64: {
+      // ASR_GEMM_N64_STAGES=3: the three-stage ring (read per launch)
+      const char* e = getenv("ASR_GEMM_N64_STAGES");
+      const int nst = (e && e[0] == '3') ? 3 : 2;
+      static bool raised[2][2] = {};
+      bool ok = true;
+      for (int ns = 2; ns <= 3; ++ns)
+        for (int b = 0; b < 2; ++b)
+          ok &= raise_lds(&raised[ns - 2][b], K_N64[ns - 2][b], 2, ns * n64_stage(b));
+      ASR_REQUIRE(ok, ASR_ERR_HIP, "gemm: cannot raise the LDS limit of the 256x64 kernel");
+      hipLaunchKernelGGL(K_N64[nst - 2][mode & 1][mode >> 1], grid, dim3(NT),
+                         nst * n64_stage(mode & 1), s, P);
+      break;
+    }
+    case ASR_PTAG_GEMM_FAST2:
+    case ASR_PTAG_GEMM_FAST4: {
+      const int nst = family == ASR_PTAG_GEMM_FAST4 ? 4 : 2;
+      hipLaunchKernelGGL(K_FAST[nst == 4][mode], grid, dim3(NT), (size_t)nst * 2 * FTILE, s, P);
+      break;
+    }
+    case ASR_PTAG_GEMM_F32F: {
+      const char* e = getenv("ASR_GEMM_F32_STAGES");   // 3: the ring (A/B; read per launch)
+      const int nst = (e && e[0] == '3') ? 3 : 2;
+      static bool raised = false;   // the ring's limit; a refusal shows at the launch
+      if (nst == 3) (void)raise_lds(&raised, &K_F32[1][0][0], 12, 3 * 320 * FBK32 * 4);
+      const int tmw = f32_tile_rows(problems, nprob);
+      const size_t lds = (size_t)nst * (64 * tmw + 256 / tmw) * FBK32 * 4;
+      hipLaunchKernelGGL(K_F32[nst == 3][tmw >> 1][mode], grid, dim3(NT), lds, s, P);
+      break;
+    }
+    default: {
+      const bool bf16 = family == ASR_PTAG_GEMM_GEN_BF16;
+      report_generic(problems, nprob, bf16);
+      if (bf16) hipLaunchKernelGGL(gemm_kernel<true>, grid, dim3(NT), 2 * BM * LDB16 * 2, s, P);
+      else hipLaunchKernelGGL(gemm_kernel<false>, grid, dim3(NT), 2 * BM * LDF32 * 4, s, P);
+    }
+  }
+  return ASR_OK;
+}
+
+int gemm_launch_own(const asr_gemm_t* problems, int nprob, int compute_dtype, void* workspace,
+                    size_t ws_bytes, void* stream, const CallOpts& o) {
+  Params P;
+  int wg, maxb;
+  if (const int rc = fill_params(problems, nprob, compute_dtype, workspace, ws_bytes, o, &P, &wg,
+                                 &maxb))
+    return rc;
+  if (wg == 0) return ASR_OK;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(maxwg, 1, nprob * maxb);
-  ASR_REQUIRE(grid.z <= 65535, ASR_ERR_ARG, "gemm: batch too large");
+  ASR_REQUIRE(nprob * maxb <= 65535, ASR_ERR_ARG, "gemm: batch too large");
   double flops = 0.0;
   for (int i = 0; i < nprob; ++i)
     flops += 2.0 * problems[i].M * problems[i].N * problems[i].K * P.p[i].batch;
   const int slot = prof_begin_launch(ASR_PROF_GEMM, s, flops);
-  const int fast = compute_dtype == ASR_DT_BF16 ? fast_modes(problems, P) : -1;
-  if (fast >= 0 && big8_ok(problems, nprob)) {
-    // 256 x 256 8-wave kernel; the split never exceeds the workspace plan's
-    int maxwg8 = 0;
-    for (int i = 0; i < nprob; ++i) {
-      Problem& p = P.p[i];
-      const int tiles8 = ceil_div(p.M, T8) * ceil_div(p.N, T8);
-      int ks = 1;
-      if (p.ksplit > 1) {
-        ks = min(p.ksplit, max(1, ceil_div(split_target(), tiles8)));
-        const int kc = ceil_div(ceil_div(p.K, ks), BK8) * BK8;
-        ks = ceil_div(p.K, kc);
-        p.kchunk = kc;
-      }
-      if (ks <= 1) { ks = 1; p.kchunk = p.K; }
-      p.ksplit = ks;
-      maxwg8 = max(maxwg8, tiles8 * ks);
-    }
-    static bool attr8 = false;
-    if (!attr8) {
-      bool ok = true;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_8w<0, 0>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE8) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_8w<0, 1>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE8) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_8w<1, 0>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE8) == hipSuccess;
-      ok &= hipFuncSetAttribute((const void*)gemm_bf16_8w<1, 1>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE8) == hipSuccess;
-      ASR_REQUIRE(ok, ASR_ERR_HIP, "gemm: cannot raise the LDS limit of the 8-wave kernel");
-      attr8 = true;
-    }
-    const dim3 g8(maxwg8, 1, nprob * maxb);
-    const size_t lds8 = 4 * TILE8;
-    const char* er = getenv("ASR_GEMM_8R");   // ring form by default (ASR_GEMM_8R=0: two buffers)
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ((er && er[0] == '0') ? ASR_PTAG_GEMM_8W : ASR_PTAG_GEMM_8R) + fast);
-    if (!(er && er[0] == '0')) {
-      static bool attrr = false;
-      const int ldsr = NSLOT * 2 * TILER;
-      if (!attrr) {
-        bool ok = true;
-        ok &= hipFuncSetAttribute((const void*)gemm_bf16_8r<0, 0>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, ldsr) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void*)gemm_bf16_8r<0, 1>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, ldsr) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void*)gemm_bf16_8r<1, 0>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, ldsr) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void*)gemm_bf16_8r<1, 1>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, ldsr) == hipSuccess;
-        ASR_REQUIRE(ok, ASR_ERR_HIP, "gemm: cannot raise the LDS limit of the ring kernel");
-        attrr = true;
-      }
-      switch (fast) {
-        case 0: hipLaunchKernelGGL((gemm_bf16_8r<0, 0>), g8, dim3(NT8), ldsr, s, P); break;
-        case 1: hipLaunchKernelGGL((gemm_bf16_8r<0, 1>), g8, dim3(NT8), ldsr, s, P); break;
-        case 2: hipLaunchKernelGGL((gemm_bf16_8r<1, 0>), g8, dim3(NT8), ldsr, s, P); break;
-        default: hipLaunchKernelGGL((gemm_bf16_8r<1, 1>), g8, dim3(NT8), ldsr, s, P); break;
-      }
-    } else switch (fast) {
-      case 0: hipLaunchKernelGGL((gemm_bf16_8w<0, 0>), g8, dim3(NT8), lds8, s, P); break;
-      case 1: hipLaunchKernelGGL((gemm_bf16_8w<0, 1>), g8, dim3(NT8), lds8, s, P); break;
-      case 2: hipLaunchKernelGGL((gemm_bf16_8w<1, 0>), g8, dim3(NT8), lds8, s, P); break;
-      default: hipLaunchKernelGGL((gemm_bf16_8w<1, 1>), g8, dim3(NT8), lds8, s, P); break;
-    }
-  } else if (fast == 3 && !g_row_lse && kk256_ok(problems, nprob)) {
-    // 256 x 256 tiles; the split never exceeds the workspace plan's (128 x 128) split
-    int maxwg2 = 0;
-    for (int i = 0; i < nprob; ++i) {
-      Problem& p = P.p[i];
-      const int tiles2 = ceil_div(p.M, BT2) * ceil_div(p.N, BT2);
-      int ks = 1;
-      if (p.ksplit > 1) {
-        ks = min(p.ksplit, max(1, ceil_div(256, tiles2)));
-        const int kc = ceil_div(ceil_div(p.K, ks), BK2) * BK2;
-        ks = ceil_div(p.K, kc);
-        p.kchunk = kc;
-      }
-      if (ks <= 1) { ks = 1; p.kchunk = p.K; }
-      p.ksplit = ks;
-      maxwg2 = max(maxwg2, tiles2 * ks);
-    }
-    static bool attr = false;
-    if (!attr) {
-      ASR_REQUIRE(hipFuncSetAttribute((const void*)gemm_bf16_kk256,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      NST2 * 2 * FTILE2) == hipSuccess,
-                  ASR_ERR_HIP, "gemm: cannot raise the LDS limit of the 256x256 kernel");
-      attr = true;
-    }
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ASR_PTAG_GEMM_KK256 + fast);
-    hipLaunchKernelGGL(gemm_bf16_kk256, dim3(maxwg2, 1, nprob * maxb), dim3(NT),
-                       (size_t)NST2 * 2 * FTILE2, s, P);
-  } else if (fast >= 0 && n64_ok(problems, nprob, fast & 1)) {
-    // ASR_GEMM_N64_STAGES=3: the three-stage ring (read per launch)
-    const char* n64e = getenv("ASR_GEMM_N64_STAGES");
-    const int n64st = (n64e && n64e[0] == '3') ? 3 : 2;
-    static bool attr64 = false;
-    if (!attr64) {
-      bool ok = true;
-#define ASR_N64_ATTR(A, B, NS)                                                               \
-  ok &= hipFuncSetAttribute((const void*)gemm_bf16_n64<A, B, NS>,                            \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, NS * n64_stage(B)) ==   \
-        hipSuccess
-      ASR_N64_ATTR(0, 0, 2); ASR_N64_ATTR(1, 0, 2); ASR_N64_ATTR(0, 1, 2); ASR_N64_ATTR(1, 1, 2);
-      ASR_N64_ATTR(0, 0, 3); ASR_N64_ATTR(1, 0, 3); ASR_N64_ATTR(0, 1, 3); ASR_N64_ATTR(1, 1, 3);
-#undef ASR_N64_ATTR
-      ASR_REQUIRE(ok, ASR_ERR_HIP, "gemm: cannot raise the LDS limit of the 256x64 kernel");
-      attr64 = true;
-    }
-    int maxwg64 = 0;
-    for (int i = 0; i < nprob; ++i)
-      maxwg64 = max(maxwg64, ceil_div(P.p[i].M, N64_BM) * max(1, P.p[i].ksplit));
-    const dim3 g64(maxwg64, 1, nprob * maxb);
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ASR_PTAG_GEMM_N64 + fast);
-#define ASR_N64(A, B)                                                                          \
-  do {                                                                                         \
-    if (n64st == 3)                                                                            \
-      hipLaunchKernelGGL((gemm_bf16_n64<A, B, 3>), g64, dim3(NT), 3 * n64_stage(B), s, P);     \
-    else                                                                                       \
-      hipLaunchKernelGGL((gemm_bf16_n64<A, B, 2>), g64, dim3(NT), 2 * n64_stage(B), s, P);     \
-  } while (0)
-    switch (fast) {
-      case 0: ASR_N64(0, 0); break;
-      case 2: ASR_N64(1, 0); break;
-      case 1: ASR_N64(0, 1); break;
-      default: ASR_N64(1, 1); break;
-    }
-#undef ASR_N64
-  } else if (fast >= 0) {
-    const int nst = g_small_tiles ? 2 : fast_stages();
-    const size_t lds = (size_t)nst * 2 * FTILE;
-    prof_set_tag(ASR_PROF_GEMM, slot,
-                 4 * (nst == 4 ? ASR_PTAG_GEMM_FAST4 : ASR_PTAG_GEMM_FAST2) + fast);
-    switch (fast) {
-#define ASR_FAST(A, B)                                                                   \
-  do {                                                                                   \
-    if (nst == 4) hipLaunchKernelGGL((gemm_bf16_fast<A, B, 4>), grid, dim3(NT), lds, s, P); \
-    else hipLaunchKernelGGL((gemm_bf16_fast<A, B, 2>), grid, dim3(NT), lds, s, P);          \
-  } while (0)
-      case 0: ASR_FAST(0, 0); break;
-      case 1: ASR_FAST(0, 1); break;
-      case 2: ASR_FAST(1, 0); break;
-      default: ASR_FAST(1, 1); break;
-#undef ASR_FAST
-    }
-  } else if (compute_dtype == ASR_DT_BF16) {
-    static bool warned = false;   // a bf16-mode product of real size on the slow path: say so once
-    if (!warned && !getenv("ASR_GEMM_DEBUG")) {
-      for (int i = 0; i < nprob; ++i) {
-        const double fl = 2.0 * problems[i].M * problems[i].N * problems[i].K * problems[i].batch;
-        if (fl >= 32e6) {
-          warned = true;
-          fprintf(stderr, "[asr_gemm] warning: a bf16-mode product (M=%d N=%d K=%d batch=%d) runs "
-                  "on the generic register-staged kernel, not the LDS-DMA fast kernels "
-                  "(ASR_GEMM_DEBUG=1 lists every such product)\n", problems[i].M, problems[i].N,
-                  problems[i].K, problems[i].batch);
-          break;
-        }
-      }
-    }
-    if (getenv("ASR_GEMM_DEBUG"))   // which bf16-mode products miss the fast kernels
-      for (int i = 0; i < nprob; ++i)
-        fprintf(stderr, "[asr_gemm generic] M=%d N=%d K=%d batch=%d a(dt=%d tr=%d tap=%d perm=%d) "
-                "b(dt=%d tr=%d tap=%d perm=%d)\n", problems[i].M, problems[i].N, problems[i].K,
-                problems[i].batch, problems[i].a.dtype, problems[i].a.trans,
-                problems[i].a.tap_group, problems[i].a.map.perm != nullptr, problems[i].b.dtype,
-                problems[i].b.trans, problems[i].b.tap_group, problems[i].b.map.perm != nullptr);
-    const size_t lds = 2 * BM * LDB16 * 2;
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ASR_PTAG_GEMM_GEN_BF16);
-    hipLaunchKernelGGL(gemm_kernel<true>, grid, dim3(NT), lds, s, P);
-  } else if (const int f32m = fast32_modes(problems, P); f32m >= 0) {
-    // tile shape: 256 x 64 when every N <= 64, 64 x 256 when every M <= 64
-    bool n64 = true, m64 = true;
-    for (int i = 0; i < nprob; ++i) {
-      n64 &= problems[i].N <= 64;
-      m64 &= problems[i].M <= 64;
-    }
-    const int tmw = n64 ? 4 : m64 ? 1 : 2;
-    const int tmr = 64 * tmw, tnr = 256 / tmw;
-    int wg32 = 0;
-    for (int i = 0; i < nprob; ++i)
-      wg32 = max(wg32, ceil_div(P.p[i].M, tmr) * ceil_div(P.p[i].N, tnr) * max(1, P.p[i].ksplit));
-    const dim3 g32(wg32, 1, nprob * maxb);
-    const size_t lds = 2 * (size_t)(tmr + tnr) * FBK32 * 4;
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ASR_PTAG_GEMM_F32F + f32m);
-    const char* fst = getenv("ASR_GEMM_F32_STAGES");   // 3: the ring (A/B; read per launch)
-    const bool ring = fst && fst[0] == '3';
-    if (ring) {
-      static bool attr = false;
-      if (!attr) {
-        attr = true;
-#define ASR_F32R_ATTR(A, B, TW)                                                                  \
-  (void)hipFuncSetAttribute((const void*)gemm_f32_fast<A, B, TW, 3>,                             \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 320 * FBK32 * 4)
-        ASR_F32R_ATTR(0, 0, 1); ASR_F32R_ATTR(0, 0, 2); ASR_F32R_ATTR(0, 0, 4);
-        ASR_F32R_ATTR(0, 1, 1); ASR_F32R_ATTR(0, 1, 2); ASR_F32R_ATTR(0, 1, 4);
-        ASR_F32R_ATTR(1, 0, 1); ASR_F32R_ATTR(1, 0, 2); ASR_F32R_ATTR(1, 0, 4);
-        ASR_F32R_ATTR(1, 1, 1); ASR_F32R_ATTR(1, 1, 2); ASR_F32R_ATTR(1, 1, 4);
-#undef ASR_F32R_ATTR
-      }
-    }
-    const size_t ldsr = ring ? lds / 2 * 3 : lds;
-#define ASR_F32F(A, B)                                                                           \
-  do {                                                                                           \
-    if (ring) {                                                                                  \
-      if (tmw == 4) hipLaunchKernelGGL((gemm_f32_fast<A, B, 4, 3>), g32, dim3(NT), ldsr, s, P);   \
-      else if (tmw == 1) hipLaunchKernelGGL((gemm_f32_fast<A, B, 1, 3>), g32, dim3(NT), ldsr, s, P); \
-      else hipLaunchKernelGGL((gemm_f32_fast<A, B, 2, 3>), g32, dim3(NT), ldsr, s, P);            \
-    } else if (tmw == 4) hipLaunchKernelGGL((gemm_f32_fast<A, B, 4>), g32, dim3(NT), lds, s, P);  \
-    else if (tmw == 1) hipLaunchKernelGGL((gemm_f32_fast<A, B, 1>), g32, dim3(NT), lds, s, P);    \
-    else hipLaunchKernelGGL((gemm_f32_fast<A, B, 2>), g32, dim3(NT), lds, s, P);                  \
-  } while (0)
-    switch (f32m) {
-      case 0: ASR_F32F(0, 0); break;
-      case 1: ASR_F32F(0, 1); break;
-      case 2: ASR_F32F(1, 0); break;
-      default: ASR_F32F(1, 1); break;
-    }
-#undef ASR_F32F
-  } else {
-    if (getenv("ASR_GEMM_DEBUG"))   // which fp32-mode products miss the f32 fast kernel
-      for (int i = 0; i < nprob; ++i)
-        fprintf(stderr, "[asr_gemm generic f32] M=%d N=%d K=%d batch=%d a(dt=%d tr=%d tap=%d "
-                "perm=%d ld=%lld al=%d) b(dt=%d tr=%d tap=%d perm=%d ld=%lld al=%d)\n",
-                problems[i].M, problems[i].N, problems[i].K, problems[i].batch,
-                problems[i].a.dtype, problems[i].a.trans, problems[i].a.tap_group,
-                problems[i].a.map.perm != nullptr, problems[i].a.map.stride_t,
-                (int)aligned16(problems[i].a.ptr), problems[i].b.dtype, problems[i].b.trans,
-                problems[i].b.tap_group, problems[i].b.map.perm != nullptr,
-                problems[i].b.map.stride_t, (int)aligned16(problems[i].b.ptr));
-    const size_t lds = 2 * BM * LDF32 * 4;
-    prof_set_tag(ASR_PROF_GEMM, slot, 4 * ASR_PTAG_GEMM_GEN_F32);
-    hipLaunchKernelGGL(gemm_kernel<false>, grid, dim3(NT), lds, s, P);
-  }
+  int mode;
+  const int family = choose_family(problems, nprob, compute_dtype, o, P, &mode, &wg);
+  prof_set_tag(ASR_PROF_GEMM, slot, 4 * family + mode);
+  if (const int rc = launch_family(family, mode, dim3(wg, 1, nprob * maxb), problems, nprob, P, s))
+    return rc;
   ASR_LAUNCH_CHECK();
   prof_end_launch(ASR_PROF_GEMM, slot, s);
   for (int i = 0; i < nprob; ++i) {
@@ -2853,12 +2834,12 @@ asr_rowmap_t stage_map(const asr_gemm_t& g, int j, int rows) {
   return m;
 }
 
-size_t split_bytes_aligned(const asr_gemm_t* g, int nprob) {
-  return (plan_split(g, nprob).bytes + 255) & ~(size_t)255;
+size_t split_bytes_aligned(const asr_gemm_t* g, int nprob, const CallOpts& o) {
+  return (plan_split(g, nprob, o).bytes + 255) & ~(size_t)255;
 }
 
 int gemm_launch(const asr_gemm_t* problems, int nprob, int compute_dtype, void* workspace,
-                size_t ws_bytes, void* stream) {
+                size_t ws_bytes, void* stream, const CallOpts& o) {
   ASR_REQUIRE(problems && nprob >= 1 && nprob <= 2, ASR_ERR_ARG, "gemm: nprob must be 1 or 2");
   // The fast kernels take one operand-layout pair per launch: two products with
   // different layouts (a Linear backward's dX + dW) run as two launches, one
@@ -2867,12 +2848,12 @@ int gemm_launch(const asr_gemm_t* problems, int nprob, int compute_dtype, void* 
   if (nprob == 2 && compute_dtype == ASR_DT_BF16 &&
       2 * problems[0].a.trans + problems[0].b.trans !=
           2 * problems[1].a.trans + problems[1].b.trans) {
-    const int rc = gemm_launch(problems, 1, compute_dtype, workspace, ws_bytes, stream);
+    const int rc = gemm_launch(problems, 1, compute_dtype, workspace, ws_bytes, stream, o);
     if (rc) return rc;
-    return gemm_launch(problems + 1, 1, compute_dtype, workspace, ws_bytes, stream);
+    return gemm_launch(problems + 1, 1, compute_dtype, workspace, ws_bytes, stream, o);
   }
   if (compute_dtype == ASR_DT_BF16 && workspace) {
-    const size_t base = split_bytes_aligned(problems, nprob);
+    const size_t base = split_bytes_aligned(problems, nprob, o);
     const StagePlan st = plan_stage(problems, nprob, base);
     if (st.bytes > 0 && ws_bytes >= base + st.bytes) {
       // every staged operand in one launch when all take the vector form
@@ -2922,10 +2903,10 @@ int gemm_launch(const asr_gemm_t* problems, int nprob, int compute_dtype, void* 
               (long long)st.rows[i][j] * st.ld[i][j];
         }
       }
-      return gemm_launch_own(g2, nprob, compute_dtype, workspace, ws_bytes, stream);
+      return gemm_launch_own(g2, nprob, compute_dtype, workspace, ws_bytes, stream, o);
     }
   }
-  return gemm_launch_own(problems, nprob, compute_dtype, workspace, ws_bytes, stream);
+  return gemm_launch_own(problems, nprob, compute_dtype, workspace, ws_bytes, stream, o);
 }
 
 }  // namespace
@@ -2933,52 +2914,43 @@ int gemm_launch(const asr_gemm_t* problems, int nprob, int compute_dtype, void* 
 
 using namespace asr;
 
-extern "C" int asr_gemm_set_nosplit(int on) {
-  g_nosplit = on ? 1 : 0;
-  return ASR_OK;
+extern "C" int asr_gemm(const asr_gemm_t* problems, int nprob, int compute_dtype, void* stream,
+                        const asr_gemm_opts_t* opts) {
+  CallOpts o;
+  if (const int rc = call_opts(opts, nullptr, &o)) return rc;
+  return gemm_launch(problems, nprob, compute_dtype, nullptr, 0, stream, o);
 }
 
-extern "C" int asr_gemm_set_small_tiles(int on) {
-  g_small_tiles = on ? 1 : 0;
-  return ASR_OK;
-}
-
-// asr_gemm_set_n64_kmode(1): products with N <= 64 and a K-major B (the VGG
-// weight gradients computed transposed) take the 256 x 64 kernel too.
-extern "C" int asr_gemm_set_n64_kmode(int on) {
-  g_n64_kmode = on ? 1 : 0;
-  return ASR_OK;
-}
-
-extern "C" int asr_gemm(const asr_gemm_t* problems, int nprob, int compute_dtype, void* stream) {
-  return gemm_launch(problems, nprob, compute_dtype, nullptr, 0, stream);
-}
-
-extern "C" size_t asr_gemm_workspace_bytes(const asr_gemm_t* problems, int nprob) {
-  if (!problems || nprob < 1 || nprob > 2) return 0;
+extern "C" size_t asr_gemm_workspace_bytes(const asr_gemm_t* problems, int nprob,
+                                           const asr_gemm_opts_t* opts) {
+  CallOpts o;
+  if (!problems || nprob < 1 || nprob > 2 || call_opts(opts, nullptr, &o)) return 0;
   // split-K slabs, then the bf16 staging copies (used in bf16 mode only)
-  const size_t base = split_bytes_aligned(problems, nprob);
+  const size_t base = split_bytes_aligned(problems, nprob, o);
   const size_t stage = plan_stage(problems, nprob, base).bytes;
-  return stage ? base + stage : plan_split(problems, nprob).bytes;
+  return stage ? base + stage : plan_split(problems, nprob, o).bytes;
 }
 
 extern "C" int asr_gemm_lse_ws(const asr_gemm_t* problem, int compute_dtype, float* lse,
-                               void* workspace, size_t ws_bytes, void* stream) {
+                               void* workspace, size_t ws_bytes, void* stream,
+                               const asr_gemm_opts_t* opts) {
+  CallOpts o;
+  if (const int rc = call_opts(opts, lse, &o)) return rc;
   ASR_REQUIRE(problem && lse, ASR_ERR_ARG, "gemm_lse: null pointer");
   ASR_REQUIRE(problem->beta == 0.f && problem->drop_p == 0.f && problem->c_dtype == ASR_DT_F32 &&
                   problem->batch <= 1,
               ASR_ERR_ARG, "gemm_lse: needs beta 0, no dropout, f32 C, one batch");
-  g_row_lse = lse;
-  const int rc = gemm_launch(problem, 1, compute_dtype, workspace, ws_bytes, stream);
-  g_row_lse = nullptr;
-  return rc;
+  return gemm_launch(problem, 1, compute_dtype, workspace, ws_bytes, stream, o);
 }
 
 extern "C" int asr_gemm_ws(const asr_gemm_t* problems, int nprob, int compute_dtype,
-                           void* workspace, size_t ws_bytes, void* stream) {
-  if (!workspace) ASR_REQUIRE(plan_split(problems, nprob).bytes == 0, ASR_ERR_WORKSPACE,
+                           void* workspace, size_t ws_bytes, void* stream,
+                           const asr_gemm_opts_t* opts) {
+  CallOpts o;
+  if (const int rc = call_opts(opts, nullptr, &o)) return rc;
+  if (!workspace) ASR_REQUIRE(plan_split(problems, nprob, o).bytes == 0, ASR_ERR_WORKSPACE,
                               "gemm: split-K workspace required");   // (staging is optional)
-  return gemm_launch(problems, nprob, compute_dtype, workspace, ws_bytes, stream);
+  return gemm_launch(problems, nprob, compute_dtype, workspace, ws_bytes, stream, o);
 }
 
 // Row chunks of a column sum: enough (64-column, chunk) work-groups to cover

@@ -208,24 +208,31 @@ def gemm_problem(a, b, c, c_map, M, N_, K, alpha=1.0, beta=0.0, bias=None, bias2
                   BF16 if c_bf16 else F32)
 
 
-def run_gemm(problems, device, lse=None, cd=None):
+# run_gemm's opts (asr_gemm_opts_t; None: the defaults)
+SMALL_TILES = N.GemmOpts(small_tiles=1)
+NOSPLIT = N.GemmOpts(nosplit=1)
+N64_KMODE = N.GemmOpts(n64_kmode=1)
+
+
+def run_gemm(problems, device, lse=None, cd=None, opts=None):
     """One launch of up to two products; long-K / few-tile products (weight
     gradients) get a split-K workspace from torch's caching allocator.
     lse (one product): f32 [ceil(N / 64), M, 2] tensor receiving the row
     log-sum-exp partials of the written C (asr_gemm_lse_ws).  cd: the
     products' compute dtype when it is not the session's (an op that is f32
-    in both modes)."""
+    in both modes).  opts: the GemmOpts of the workspace query and the launch."""
     arr = (N.Gemm * len(problems))(*problems)
     parr = ctypes.cast(arr, ctypes.c_void_p)
-    nb = N.query('asr_gemm_workspace_bytes', parr, len(problems))
+    po = N.ptr_struct(opts)
+    nb = N.query('asr_gemm_workspace_bytes', parr, len(problems), po)
     ws = _ws(nb, device) if nb else None
     if lse is not None:
         assert len(problems) == 1
         N.call('asr_gemm_lse_ws', parr, compute_dtype(), N.ptr(lse), N.ptr(ws), nb,
-               N.stream_handle(device))
+               N.stream_handle(device), po)
         return
     N.call('asr_gemm_ws', parr, len(problems), compute_dtype() if cd is None else cd, N.ptr(ws),
-           nb, N.stream_handle(device))
+           nb, N.stream_handle(device), po)
 
 
 def _ctc_lse_epilogue(V):
@@ -486,7 +493,7 @@ def _linear_backward(xo, wo, bias, stage, xshape, weight, drop, dyo, need_dx, dy
     return dx
 
 
-def _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo, dy_bias=None):
+def _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo, dy_bias=None, gemm_opts=None):
     """dW (+ db) of _linear_backward alone."""
     K = xshape[-1]
     Nout = weight.shape[0]
@@ -494,7 +501,8 @@ def _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo, dy_bias=None):
     dev = dyo.device
     Kp, Np = (xo.shape[-1], wo.shape[0]) if stage else (K, Nout)
     run_gemm([gemm_problem(operand(dyo, 1, rowmap(Np)), operand(xo, 1, rowmap(Kp)),
-                           grad_buffer(weight), rowmap(K), Nout, K, M, beta=1.0)], dev)
+                           grad_buffer(weight), rowmap(K), Nout, K, M, beta=1.0)], dev,
+             opts=gemm_opts)
     _linear_bias_grad(bias, dy_bias, M, Nout, dev)
 
 
@@ -510,33 +518,23 @@ def _linear_bias_grad(bias, dy_bias, M, Nout, dev):
 
 
 def _wgrad_beside(dev, plan, fn, keep, gbufs):
-    """Enqueue the weight-gradient work fn() on the weight-gradient side stream
-    of the recurrence shape plan = (B, H), gated on the next backward
-    recurrence (as a BLSTM layer's own weight gradients); keep: tensors the
-    side stream reads.  False when that shape runs weight gradients on the
-    compute stream (the caller then runs fn itself)."""
+    """Enqueue the weight-gradient work fn(gemm_opts) on the weight-gradient
+    side stream of the recurrence shape plan = (B, H), gated on the next
+    backward recurrence (as a BLSTM layer's own weight gradients); fn gives
+    gemm_opts to each run_gemm; keep: tensors the side stream reads.  False
+    when that shape runs weight gradients on the compute stream (the caller
+    then runs fn(None) itself)."""
     side_ent = _wgrad_side_stream(dev, *plan)
     if side_ent is None:
         return False
     side, small, gated = side_ent
     main = torch.cuda.current_stream(dev)
     side.wait_stream(main)
-    if small:
-        N.call('asr_gemm_set_small_tiles', 1)
-    try:
-        with torch.cuda.stream(side):
-            if gated:
-                N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
-            fn()
-    finally:
-        if small:
-            N.call('asr_gemm_set_small_tiles', 0)
-    for t in keep:
-        t.record_stream(side)
-    if not _side_pending:
-        torch.autograd.Variable._execution_engine.queue_callback(
-            lambda: _join_side_wgrads(dev, notify=False))
-    _side_pending.append((side, gbufs, main))
+    with torch.cuda.stream(side):
+        if gated:
+            N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
+        fn(SMALL_TILES if small else None)
+    _defer_side_join(dev, side, main, keep, gbufs)
     return True
 
 
@@ -592,11 +590,10 @@ class LinearFn(torch.autograd.Function):
             dx = _linear_backward(xo, wo, bias, stage, xshape, weight, ctx.drop, dyo,
                                   ctx.needs_input_grad[0], dy_bias=dy, wgrad=False)
             gb = (grad_buffer(weight),) + ((grad_buffer(bias),) if bias is not None else ())
-            if not _wgrad_beside(dy.device, ctx.beside,
-                                 lambda: _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo,
-                                                       dy_bias=dy),
-                                 (xo, wo, dyo, dy), gb):
-                _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo, dy_bias=dy)
+            wgrad = lambda go: _linear_wgrad(xo, wo, bias, stage, xshape, weight, dyo,  # noqa: E731
+                                             dy_bias=dy, gemm_opts=go)
+            if not _wgrad_beside(dy.device, ctx.beside, wgrad, (xo, wo, dyo, dy), gb):
+                wgrad(None)
             return dx, None, None, None
         dx = _linear_backward(xo, wo, bias, stage, xshape, weight, ctx.drop, dyo,
                               ctx.needs_input_grad[0], dy_bias=dy)
@@ -696,11 +693,10 @@ class LinearCTCFn(torch.autograd.Function):
             dx = _linear_backward(xo, wo, bias_w, True, xshape, weight, ctx.drop, dyo,
                                   ctx.needs_input_grad[0], dy_bias=dyo, wgrad=False)
             gb = (grad_buffer(weight),) + ((grad_buffer(bias),) if bias is not None else ())
-            if not _wgrad_beside(dev, ctx.from_blstm,
-                                 lambda: _linear_wgrad(xo, wo, bias_w, True, xshape, weight, dyo,
-                                                       dy_bias=dyo),
-                                 (xo, wo, dyo), gb):
-                _linear_wgrad(xo, wo, bias_w, True, xshape, weight, dyo, dy_bias=dyo)
+            wgrad = lambda go: _linear_wgrad(xo, wo, bias_w, True, xshape, weight, dyo,  # noqa: E731
+                                             dy_bias=dyo, gemm_opts=go)
+            if not _wgrad_beside(dev, ctx.from_blstm, wgrad, (xo, wo, dyo), gb):
+                wgrad(None)
             return (dx,) + (None,) * 10
         dx = _linear_backward(xo, wo, bias_w, True, xshape, weight, ctx.drop, dyo,
                               ctx.needs_input_grad[0], dy_bias=dyo)
@@ -773,16 +769,17 @@ class LinearCTC32Fn(torch.autograd.Function):
                 run_gemm([gemm_problem(operand(dl, 0, rowmap(Vp)), operand(weight, 1, rowmap(K)),
                                        dx, rowmap(K), M, K, V, drop=ctx.drop)], dev)
 
-        def wgrad():
+        def wgrad(gemm_opts):
             if M > 0:
                 run_gemm([gemm_problem(operand(dl, 1, rowmap(Vp)), operand(x, 1, rowmap(K)),
-                                       grad_buffer(weight), rowmap(K), V, K, M, beta=1.0)], dev)
+                                       grad_buffer(weight), rowmap(K), V, K, M, beta=1.0)], dev,
+                         opts=gemm_opts)
             if bias is not None:
                 colsum_accumulate(dl[:, :V], grad_buffer(bias))
         gb = (grad_buffer(weight),) + ((grad_buffer(bias),) if bias is not None else ())
         if not (ctx.from_blstm is not None and os.environ.get('ASR_HEAD_WGRAD_SIDE', '1') != '0'
                 and _wgrad_beside(dev, ctx.from_blstm, wgrad, (x, dl), gb)):
-            wgrad()
+            wgrad(None)
         return (dx,) + (None,) * 10
 
 
@@ -873,10 +870,10 @@ class LinearExFn(torch.autograd.Function):
                                       operand(weight, 1, rowmap(ldw), offset=c0), dx, amap, M, K,
                                       Nout, c_offset=a_off))
 
-        def wgrad():
+        def wgrad(gemm_opts):
             run_gemm([gemm_problem(operand(dy, 1, rowmap(Nout)), operand(x, 1, amap, offset=a_off),
                                    grad_buffer(weight), rowmap(ldw), Nout, K, M, beta=1.0,
-                                   c_offset=c0)], x.device)
+                                   c_offset=c0)], x.device, opts=gemm_opts)
             if bias is not None:
                 colsum_accumulate(dy.view(M, Nout), grad_buffer(bias),
                                   grad_buffer(bias2) if bias2 is not None else None)
@@ -888,7 +885,7 @@ class LinearExFn(torch.autograd.Function):
                 run_gemm(probs, x.device)
             gb = tuple(grad_buffer(t) for t in (weight, bias, bias2) if t is not None)
             if not _wgrad_beside(dy.device, ctx.beside, wgrad, (x, dy), gb):
-                wgrad()
+                wgrad(None)
             return dx, None, None, None, None, None, None
         probs.append(gemm_problem(operand(dy, 1, rowmap(Nout)), operand(x, 1, amap, offset=a_off),
                                   grad_buffer(weight), rowmap(ldw), Nout, K, M, beta=1.0,
@@ -1015,22 +1012,20 @@ def _attdec_forward(enc, enc_a, lens, pre_emb, h0, emb_dim, sharpen, sigmoid, w_
     w_ih_ctx = ctypes.c_void_p(w_ih.data_ptr() + 4 * emb_dim)
     opts, keep = _attdec_opts(train_opts, B, S, D, emb_dim, w_ih, dev)
     # a backward will follow: the persistent pass keeps every step's conv
-    # features for it (asr_attdec_set_conv_feat; ASR_ATT_CONV_FEAT=0: recomputed)
+    # features for it (opts.conv_feat; ASR_ATT_CONV_FEAT=0: recomputed)
     feat = None
     if keep_feat and os.environ.get('ASR_ATT_CONV_FEAT', '1') != '0':
         fb = N.query('asr_attdec_conv_feat_bytes', ctypes.byref(dims))
         feat = torch.empty(max(int(fb) // 4, 1), dtype=torch.float32, device=dev)
-        N.call('asr_attdec_set_conv_feat', N.ptr(feat))
-    try:
-        N.call('asr_attdec_forward_ex', ctypes.byref(dims), N.ptr_struct(opts), cd, N.ptr(enc),
-               N.ptr(enc_a), N.ptr(lens), w_ih_ctx, ld_ih, N.ptr(w_hh), N.ptr(w_dec),
-               N.ptr(w_conv), N.ptr(conv_w), N.ptr(v), N.ptr(pre_emb),
-               N.ptr(h0.contiguous() if h0 is not None else None), N.ptr(dec), N.ptr(cst),
-               N.ptr(gates), N.ptr(x), N.ptr(ctxv), N.ptr(aw), N.ptr(ws), nb,
-               N.stream_handle(dev))
-    finally:
-        if feat is not None:
-            N.call('asr_attdec_set_conv_feat', None)
+        if opts is None:
+            opts = N.AttDecOpts()    # all zero: what NULL means, plus the buffer
+        opts.conv_feat = feat.data_ptr()
+    N.call('asr_attdec_forward_ex', ctypes.byref(dims), N.ptr_struct(opts), cd, N.ptr(enc),
+           N.ptr(enc_a), N.ptr(lens), w_ih_ctx, ld_ih, N.ptr(w_hh), N.ptr(w_dec),
+           N.ptr(w_conv), N.ptr(conv_w), N.ptr(v), N.ptr(pre_emb),
+           N.ptr(h0.contiguous() if h0 is not None else None), N.ptr(dec), N.ptr(cst),
+           N.ptr(gates), N.ptr(x), N.ptr(ctxv), N.ptr(aw), N.ptr(ws), nb,
+           N.stream_handle(dev))
     if feat is not None:
         ran = (ctypes.c_int * 2)()
         N.call("asr_attdec_persist_last", ctypes.cast(ran, ctypes.c_void_p))
@@ -1193,19 +1188,15 @@ class AttDecoderFn(torch.autograd.Function):
             d_pre = torch.empty(B, S, 4 * D, **f32)
             dg_ss = torch.empty(B, S, 4 * D, **f32)
             opts.d_pre, opts.dg_ss = d_pre.data_ptr(), dg_ss.data_ptr()
-        feat = keep.get('conv_feat')
-        if feat is not None:
-            N.call('asr_attdec_set_conv_feat', N.ptr(feat))
-        try:
-            N.call('asr_attdec_backward_ex', ctypes.byref(dims), N.ptr_struct(opts), cd,
-                   N.ptr(enc), N.ptr(enc_a), N.ptr(lens), w_ih_ctx, ld_ih, N.ptr(w_hh),
-                   N.ptr(w_dec), N.ptr(w_conv), N.ptr(conv_w), N.ptr(v), N.ptr(dec), N.ptr(cst),
-                   N.ptr(aw), N.ptr(d_dec), N.ptr(d_ctx), N.ptr(gates), N.ptr(dctx_tot),
-                   N.ptr(d_enc_a), N.ptr(d_h0), N.ptr(dwd), N.ptr(dv_part), N.ptr(dwc_part),
-                   N.ptr(dcw_part), N.ptr(ws), nb, N.stream_handle(dev))
-        finally:
-            if feat is not None:
-                N.call('asr_attdec_set_conv_feat', None)
+        if opts is not None:   # only the buffer a persistent forward wrote
+            feat = keep.get('conv_feat')
+            opts.conv_feat = feat.data_ptr() if feat is not None else None
+        N.call('asr_attdec_backward_ex', ctypes.byref(dims), N.ptr_struct(opts), cd,
+               N.ptr(enc), N.ptr(enc_a), N.ptr(lens), w_ih_ctx, ld_ih, N.ptr(w_hh),
+               N.ptr(w_dec), N.ptr(w_conv), N.ptr(conv_w), N.ptr(v), N.ptr(dec), N.ptr(cst),
+               N.ptr(aw), N.ptr(d_dec), N.ptr(d_ctx), N.ptr(gates), N.ptr(dctx_tot),
+               N.ptr(d_enc_a), N.ptr(d_h0), N.ptr(dwd), N.ptr(dv_part), N.ptr(dwc_part),
+               N.ptr(dcw_part), N.ptr(ws), nb, N.stream_handle(dev))
         dg = gates                          # dgates (row t = 0 is zero)
         d_pre_out = dg
         if sampled:
@@ -1930,31 +1921,22 @@ def _blstm_bwd_wgrads(ctx, plan, gate, side_ent, dx_done, dg_op, act, x_op, y_op
     side, small, gated = side_ent
     main = torch.cuda.current_stream(dev)
     side.wait_stream(main)
-    if small:
-        N.call('asr_gemm_set_small_tiles', 1)
-    try:
-        with torch.cuda.stream(side):
-            if dx_done is not None:
-                # the pipelined input gradient first, so the CUs the next
-                # recurrence leaves free serve dX -- which that recurrence waits
-                # for -- before the weight gradients, which only the optimizer needs
-                side.wait_event(dx_done)
-            elif gated and ctx.next_rec:
-                # hold the GEMMs back until the previous layer's backward
-                # recurrence (launched next on the main stream) is resident
-                N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
-            # (tools/cores_locate.py replaces _blstm_wgrad with stand-in
-            # side-stream workloads; nothing diagnostic runs here)
-            _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev)
-    finally:
-        if small:
-            N.call('asr_gemm_set_small_tiles', 0)
-    for t in (dg_op, act, x_op, y_op) + ((in_map.perm,) if in_map.perm is not None else ()):
-        t.record_stream(side)
-    if not _side_pending:
-        torch.autograd.Variable._execution_engine.queue_callback(
-            lambda: _join_side_wgrads(dev, notify=False))
-    _side_pending.append((side, gbufs, main))
+    with torch.cuda.stream(side):
+        if dx_done is not None:
+            # the pipelined input gradient first, so the CUs the next
+            # recurrence leaves free serve dX -- which that recurrence waits
+            # for -- before the weight gradients, which only the optimizer needs
+            side.wait_event(dx_done)
+        elif gated and ctx.next_rec:
+            # hold the GEMMs back until the previous layer's backward
+            # recurrence (launched next on the main stream) is resident
+            N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
+        # (tools/cores_locate.py replaces _blstm_wgrad with stand-in
+        # side-stream workloads taking the same positional arguments;
+        # nothing diagnostic runs here)
+        _blstm_wgrad(dg_op, act, x_op, x_map, y_op, T, gbufs, dev, SMALL_TILES if small else None)
+    _defer_side_join(dev, side, main, (dg_op, act, x_op, y_op) +
+                     ((in_map.perm,) if in_map.perm is not None else ()), gbufs)
 
 
 def _wgrad_main_banded(gate, dg_op, x_op, y_op, T, gbufs, B, H, dev):
@@ -2012,16 +1994,12 @@ def _blstm_bwd_dx_ahead(ctx, plan, gate, dg_op, w_op, in_map, B, H, Dp, dev):
 def _dx_run_bands(groups, dg_op, w_op, dx, in_map, H, Dp, drop, dev, gate=None):
     """One launch per band group, in order, on the current stream; gate: each
     first waits for the recurrence's progress to reach its target."""
-    N.call('asr_gemm_set_nosplit', 1)     # per output element: one launch's sum
-    try:
-        for k, group in enumerate(groups):
-            if gate is not None:
-                N.call('asr_lstm_progress_gate', N.ptr(gate.counter), gate.targets[k],
-                       N.stream_handle(dev))
-            run_gemm([_dx_rows_problem(dg_op, w_op, dx, in_map, H, Dp, drop, ta, tb)
-                      for ta, tb in group], dev)
-    finally:
-        N.call('asr_gemm_set_nosplit', 0)
+    for k, group in enumerate(groups):
+        if gate is not None:
+            N.call('asr_lstm_progress_gate', N.ptr(gate.counter), gate.targets[k],
+                   N.stream_handle(dev))
+        run_gemm([_dx_rows_problem(dg_op, w_op, dx, in_map, H, Dp, drop, ta, tb)
+                  for ta, tb in group], dev, opts=NOSPLIT)   # per output element: one launch's sum
 
 
 def _blstm_bwd_dx_rest(ctx, plan, dx, bands_done, dg_op, w_op, in_map, B, H, Dp, dev):
@@ -2216,14 +2194,15 @@ def fuse_dropout_ok():
     return compute_dtype() == BF16 and os.environ.get('ASR_FUSE_DROPOUT', '1') != '0'
 
 
-def _blstm_wgrad(dg, dg_f32, x_op, x_map, y_op, T, gbufs, dev):
+def _blstm_wgrad(dg, dg_f32, x_op, x_map, y_op, T, gbufs, dev, gemm_opts=None):
     """dW_ih, dW_hh of one BLSTM layer from its gate gradients (dg: bf16 copy
     in bf16 mode, else the f32 tensor).  db_ih / db_hh were accumulated by
-    asr_lstm_backward_db."""
+    asr_lstm_backward_db.  gemm_opts: run_gemm's opts for both launches."""
     H = y_op.shape[2] // 2
     hp = lambda add: rowmap(2 * H, stride_b=T * 2 * H, rows_per_b=T, t_add=add,  # noqa: E731
                             t_limit=T)
-    _wgrad_gemms(dg, x_op, y_op, gbufs, dev, dg.shape[0] * T, rowmap(8 * H), x_map, hp(-1), hp(1))
+    _wgrad_gemms(dg, x_op, y_op, gbufs, dev, dg.shape[0] * T, rowmap(8 * H), x_map, hp(-1), hp(1),
+                 gemm_opts)
 
 
 def _blstm_wgrad_rows(dg, x_op, Dx, y_op, T, gbufs, dev, ta, tb):
@@ -2240,21 +2219,21 @@ def _blstm_wgrad_rows(dg, x_op, Dx, y_op, T, gbufs, dev, ta, tb):
                  band(2 * H, -1), band(2 * H, 1))
 
 
-def _wgrad_gemms(dg, x_op, y_op, gbufs, dev, rows, dg_map, x_map, hp_f, hp_r):
+def _wgrad_gemms(dg, x_op, y_op, gbufs, dev, rows, dg_map, x_map, hp_f, hp_r, gemm_opts=None):
     """The two weight-gradient launches over `rows` rows addressed by the maps."""
     H = y_op.shape[2] // 2
     g_ih, g_hh = gbufs[:2]
     Din = g_ih.shape[-1]          # != x_op's width for 'concat' input rows
     # dW_ih [8H, Din] += dG^T x   (both directions in one problem)
     run_gemm([gemm_problem(operand(dg, 1, dg_map), operand(x_op, 1, x_map), g_ih, rowmap(Din),
-                           8 * H, Din, rows, beta=1.0)], dev)
+                           8 * H, Din, rows, beta=1.0)], dev, opts=gemm_opts)
     # dW_hh[dir] += dG_dir^T h_prev_dir ; h_prev = y[b, t-1, :H] (fwd), y[b, t+1, H:] (rev)
     run_gemm([
         gemm_problem(operand(dg, 1, dg_map), operand(y_op, 1, hp_f), g_hh, rowmap(H), 4 * H, H,
                      rows, beta=1.0),
         gemm_problem(operand(dg, 1, dg_map, offset=4 * H), operand(y_op, 1, hp_r, offset=H), g_hh,
                      rowmap(H), 4 * H, H, rows, beta=1.0, c_offset=4 * H * H),
-    ], dev)
+    ], dev, opts=gemm_opts)
 
 
 def _wgrad_split_ok(ctx, T, mode):
@@ -2273,6 +2252,18 @@ def _wgrad_split_ok(ctx, T, mode):
 
 _side_streams = {}
 _side_pending = []     # (side stream, gbufs, compute stream) of weight gradients not joined yet
+
+
+def _defer_side_join(dev, side, main, keep, gbufs):
+    """After weight-gradient work enqueued on `side`: the tensors of keep stay
+    allocated until it has run, and the compute stream `main` joins it
+    (_join_side_wgrads) at the end of the backward pass."""
+    for t in keep:
+        t.record_stream(side)
+    if not _side_pending:
+        torch.autograd.Variable._execution_engine.queue_callback(
+            lambda: _join_side_wgrads(dev, notify=False))
+    _side_pending.append((side, gbufs, main))
 
 
 def _join_side_wgrads(dev, notify=True):
@@ -2463,7 +2454,7 @@ def _dx_pipelined(dx, dg_op, w_op, B, T, H, Din, Dp, drop, dev):
     if head_main and 'ASR_DX_CHUNK' not in os.environ:
         c0 = (half + 1) // 2
 
-    def chunk(k):
+    def chunk(k, gemm_opts=None):
         s0, s1 = k * c0, (k + 1) * c0
         probs = []
         for t0, t1 in ((s0, min(s1, half)), (max(T - s1, half), T - s0)):
@@ -2474,7 +2465,7 @@ def _dx_pipelined(dx, dg_op, w_op, B, T, H, Din, Dp, drop, dev):
             c_map = rowmap(Din, stride_b=T * Din, rows_per_b=n, t_add=t0)
             probs.append(gemm_problem(a, operand(w_op, 1, rowmap(Dp)), dx, c_map, B * n,
                                       Din, 8 * H, drop=drop))
-        run_gemm(probs, dev)
+        run_gemm(probs, dev, opts=gemm_opts)
         N.call('asr_lstm_dy_signal', N.ptr(flags), k, epoch, N.stream_handle(dev))
 
     nch = (half + c0 - 1) // c0
@@ -2487,14 +2478,8 @@ def _dx_pipelined(dx, dg_op, w_op, B, T, H, Din, Dp, drop, dev):
     with torch.cuda.stream(side):
         if k0 < nch:
             N.call('asr_lstm_wgrad_gate', N.stream_handle(dev))
-        if small:
-            N.call('asr_gemm_set_small_tiles', 1)
-        try:
-            for k in range(k0, nch):
-                chunk(k)
-        finally:
-            if small:
-                N.call('asr_gemm_set_small_tiles', 0)
+        for k in range(k0, nch):
+            chunk(k, SMALL_TILES if small else None)
         done = torch.cuda.Event()
         done.record(side)
     for t in (dx, dg_op, w_op, flags):
@@ -2746,12 +2731,12 @@ class EmbeddingFn(torch.autograd.Function):
             order_d = h2d(order, dev)
             starts_d = h2d(starts, dev)
 
-            def wgrad():
+            def wgrad(_gemm_opts):   # (no GEMM in either form)
                 N.call('asr_embedding_backward_csr', N.ptr(order_d), N.ptr(starts_d), N.ptr(dout),
                        V, E, int(trans), pad, N.ptr(grad_buffer(weight)), N.stream_handle(dev))
             keep = (order_d, starts_d, dout)
         else:
-            def wgrad():
+            def wgrad(_gemm_opts):
                 N.call('asr_embedding_backward', N.ptr(idx), N.ptr(dout), idx.numel(), V, E,
                        int(trans), pad, N.ptr(grad_buffer(weight)), N.stream_handle(dev))
             keep = (idx, dout)
@@ -2760,7 +2745,7 @@ class EmbeddingFn(torch.autograd.Function):
         # wgrad_beside_encoder
         if ctx.beside is None or not _wgrad_beside(dev, ctx.beside, wgrad, keep,
                                                    (grad_buffer(weight),)):
-            wgrad()
+            wgrad(None)
         return None, None, None, None, None
 
 
@@ -3199,19 +3184,16 @@ class VGGFn(torch.autograd.Function):
                        N.stream_handle(dev))
                 dnext, flat = dx, 0
                 continue
-            if Co <= 64 and cd == BF16 and os.environ.get('ASR_VGG_DW_T', '0') == '1':
+            if (Co <= 64 and cd == BF16 and os.environ.get('ASR_VGG_DW_T', '0') == '1'
+                    and not (l == 0 and ctx.c1w)):   # (there x_op is the raw features xs)
                 # transposed image [9 Ci][Co] = X^T dz: C_out becomes the narrow N
                 # of the 256 x 64 kernel (dz^T X puts C_out on half-empty 128-row
                 # tiles).  Opt-in: measured 0.27 ms / step SLOWER at vgg_hier (the
                 # K-major 256 x 64 tile needs 96 KB of LDS, one work-group per CU)
                 packed_t = torch.empty(9 * cCp, Co, **f32)
-                N.call('asr_gemm_set_n64_kmode', 1)
-                try:
-                    run_gemm([gemm_problem(_tap_operand(x_op, 1, cCp, cCp, cF + 2, 1),
-                                           operand(dz, 1, rowmap(Co)), packed_t, rowmap(Co),
-                                           9 * cCp, Co, npad)], dev)
-                finally:
-                    N.call('asr_gemm_set_n64_kmode', 0)
+                run_gemm([gemm_problem(_tap_operand(x_op, 1, cCp, cCp, cF + 2, 1),
+                                       operand(dz, 1, rowmap(Co)), packed_t, rowmap(Co),
+                                       9 * cCp, Co, npad)], dev, opts=N64_KMODE)
                 N.call('asr_conv_weight_unpack_acc_pad_t', N.ptr(packed_t), Co, cC, cCp,
                        N.ptr(grad_buffer(w)), N.stream_handle(dev))
             else:
@@ -3237,12 +3219,7 @@ class VGGFn(torch.autograd.Function):
                     N.call('asr_conv_weight_unpack_acc_pad', N.ptr(packed), Co, cC, cCp,
                            N.ptr(grad_buffer(w)), N.stream_handle(dev))
                 if side is not None:
-                    for t in (x_op, dz):
-                        t.record_stream(side)
-                    if not _side_pending:
-                        torch.autograd.Variable._execution_engine.queue_callback(
-                            lambda: _join_side_wgrads(dev, notify=False))
-                    _side_pending.append((side, (grad_buffer(w),), main))
+                    _defer_side_join(dev, side, main, (x_op, dz), (grad_buffer(w),))
             if l == 0:
                 break
             # d input (padded rows of layer l's input) = dz (taps, mirrored) x W^T image

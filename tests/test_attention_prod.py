@@ -197,7 +197,7 @@ def test_decoder_weight_gradients_beside_encoder_bitwise(name, cuda_dev, monkeyp
 @pytest.mark.parametrize('prec', ['bf16', 'fp32'])
 def test_saved_conv_features_bitwise(prec, cuda_dev, monkeypatch):
     """Round 6: the persistent forward keeps every step's conv features and
-    the persistent backward reads them (asr_attdec_set_conv_feat) instead of
+    the persistent backward reads them (asr_attdec_opts_t.conv_feat) instead of
     recomputing them from aw -- the same pd_conv_feat on the same values, so
     the loss and every gradient are bitwise those of the recomputing pass
     (ASR_ATT_CONV_FEAT=0), at the production hybrid shape."""
@@ -210,6 +210,87 @@ def test_saved_conv_features_bitwise(prec, cuda_dev, monkeypatch):
     assert out['1'][0] == out['0'][0]
     for k in out['0'][1]:
         np.testing.assert_array_equal(out['1'][1][k], out['0'][1][k], err_msg=k)
+
+
+def _decoder_case(dev):
+    """The production decoder geometry at a few utterances and steps
+    (attdec_ref's prod_geom: persistent in both directions), on the device."""
+    import attdec_ref as R
+    inp = R.case_inputs('prod_geom')
+    t = {k: inp[k].detach().to(dev) for k in R.IN_KEYS}
+    lens = torch.from_numpy(inp['lens']).to(dev)
+    cot = inp['cot_dec'].to(dev), inp['cot_ctx'].to(dev)
+    return R.dims_of('prod_geom'), t, lens, cot
+
+
+def _persist_last():
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    persist = (ctypes.c_int * 2)()
+    N.call('asr_attdec_persist_last', ctypes.cast(persist, ctypes.c_void_p))
+    return list(persist)
+
+
+@pytest.mark.gpu
+def test_conv_feat_option_bitwise(cuda_dev, monkeypatch):
+    """asr_attdec_opts_t.conv_feat: a decoder forward + backward given the
+    buffer runs persistent in both directions and its gradients are bitwise
+    those of the same pass with conv_feat NULL (NULL opts: features recomputed)."""
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    import attdec_ref as R
+    monkeypatch.delenv('ASR_ATT_CONV_FEAT', raising=False)
+    p, t0, lens, cot = _decoder_case(cuda_dev)
+    fwd = native_ops._attdec_forward
+    grads = []
+    native_ops.set_compute_dtype('bf16')
+    try:
+        for keep_feat in (True, False):
+            monkeypatch.setattr(native_ops, '_attdec_forward',
+                                lambda *a, **k: fwd(*a, **dict(k, keep_feat=keep_feat)))
+            t = {k: v.clone().requires_grad_(True) for k, v in t0.items()}
+            dec, ctx, _ = native_ops.att_decoder(
+                t['enc'], t['enc_a'], lens, t['pre_emb'], t['h0'], p['Y'], 1.0, False,
+                *[t[k] for k in ('w_ih', 'w_hh', 'w_dec', 'w_conv', 'conv_w', 'v')], None)
+            opts, keep, _ = dec.grad_fn.opts
+            if keep_feat:
+                assert opts is not None and opts.conv_feat == keep['conv_feat'].data_ptr()
+            else:
+                assert opts is None and 'conv_feat' not in keep
+            ((dec * cot[0]).sum() + (ctx * cot[1]).sum()).backward()
+            torch.cuda.synchronize()
+            assert _persist_last() == [1, 1]
+            grads.append({k: t[k].grad.cpu().numpy() for k in R.IN_KEYS})
+    finally:
+        native_ops.set_compute_dtype('fp32')
+    for k in R.IN_KEYS:
+        assert np.abs(grads[0][k]).max() > 0, k
+        np.testing.assert_array_equal(grads[0][k], grads[1][k], err_msg=k)
+
+
+@pytest.mark.gpu
+def test_conv_feat_option_is_not_inherited(cuda_dev, monkeypatch):
+    """A persistent asr_attdec_forward_ex with NULL opts, directly after one
+    that was given a conv_feat buffer, does not write that buffer."""
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    monkeypatch.delenv('ASR_ATT_CONV_FEAT', raising=False)
+    p, t, lens, _ = _decoder_case(cuda_dev)
+    args = (t['enc'], t['enc_a'], lens, t['pre_emb'], t['h0'], p['Y'], 1.0, False,
+            t['w_ih'], t['w_hh'], t['w_dec'], t['w_conv'], t['conv_w'], t['v'], None)
+    native_ops.set_compute_dtype('bf16')
+    try:
+        with torch.no_grad():
+            _, _, opts, keep = native_ops._attdec_forward(*args, keep_feat=True)
+            torch.cuda.synchronize()
+            assert _persist_last()[0] == 1
+            feat = keep['conv_feat']
+            assert opts.conv_feat == feat.data_ptr()
+            feat.fill_(-77.0)   # (that the pass wrote it: test_conv_feat_option_bitwise)
+            _, _, opts2, keep2 = native_ops._attdec_forward(*args)
+            torch.cuda.synchronize()
+            assert _persist_last()[0] == 1
+            assert opts2 is None and 'conv_feat' not in keep2
+            assert bool((feat == -77.0).all())
+    finally:
+        native_ops.set_compute_dtype('fp32')
 
 
 @pytest.mark.gpu

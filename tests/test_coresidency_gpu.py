@@ -305,18 +305,15 @@ def test_split_row_problems_equal_whole_product(B, T, T_src, H, Dsrc, t_mul, t_a
     whole = torch.zeros(B, T_src, Dsrc, device=cuda_dev)
     c_map = ops.rowmap(Dsrc, stride_b=T_src * Dsrc, rows_per_b=T, t_mul=t_mul, t_add=t_add,
                        t_limit=T_src, perm=perm)
-    N.call('asr_gemm_set_nosplit', 1)
-    try:
-        ops.run_gemm([ops.gemm_problem(ops.operand(dg, 0, ops.rowmap(8 * H)),
-                                       ops.operand(w, 1, ops.rowmap(Dsrc)), whole, c_map,
-                                       B * T, Dsrc, 8 * H)], cuda_dev)
-        parts = torch.zeros_like(whole)
-        t0 = T // 4
-        for ta, tb in ((t0, T - t0), (0, t0), (T - t0, T)):
-            ops.run_gemm([ops._dx_rows_problem(dg, w, parts, in_map, H, Dsrc, None, ta, tb)],
-                         cuda_dev)
-    finally:
-        N.call('asr_gemm_set_nosplit', 0)
+    nosplit = N.GemmOpts(nosplit=1)
+    ops.run_gemm([ops.gemm_problem(ops.operand(dg, 0, ops.rowmap(8 * H)),
+                                   ops.operand(w, 1, ops.rowmap(Dsrc)), whole, c_map,
+                                   B * T, Dsrc, 8 * H)], cuda_dev, opts=nosplit)
+    parts = torch.zeros_like(whole)
+    t0 = T // 4
+    for ta, tb in ((t0, T - t0), (0, t0), (T - t0, T)):
+        ops.run_gemm([ops._dx_rows_problem(dg, w, parts, in_map, H, Dsrc, None, ta, tb)],
+                     cuda_dev, opts=nosplit)
     torch.cuda.synchronize()
     d = (whole != parts).nonzero()
     assert d.numel() == 0, (d[:5].tolist(), float((whole - parts).abs().max()))

@@ -616,11 +616,7 @@ def test_n64_kernel_exact(M, N, K, atrans, btrans, cuda_dev, monkeypatch):
             p = ops.gemm_problem(ops.operand(a, atrans, ops.rowmap(M if atrans else K)),
                                  ops.operand(b, btrans, ops.rowmap(N if btrans else K)), c,
                                  ops.rowmap(N), M, N, K, bias=bias, beta=1.0)
-            NL.call('asr_gemm_set_n64_kmode', 1)
-            try:
-                ops.run_gemm([p], cuda_dev)
-            finally:
-                NL.call('asr_gemm_set_n64_kmode', 0)
+            ops.run_gemm([p], cuda_dev, opts=NL.GemmOpts(n64_kmode=1))
             torch.cuda.synchronize()
             outs.append(c.cpu().numpy())
         ref = a_np.astype(np.float64) @ b_np.astype(np.float64).T + bias.cpu().numpy() + c0
@@ -827,3 +823,76 @@ def test_f32_fast_kernel_batch_permutation_matches_generic(cuda_dev, monkeypatch
         b = _f32_run(ops, cuda_dev, fn, '0', monkeypatch)[0]
         assert np.abs(b).max() > 0
         np.testing.assert_array_equal(a, b)
+
+
+# kernel families of asr_gemm_last_family() // 4 (csrc/prof.h, ASR_PTAG_GEMM_*)
+FAM_8R, FAM_N64, FAM_FAST2 = 1, 4, 5
+
+
+def _opts_problem(M, N, K, btrans, dev):
+    """A product of small-integer bf16 operands (A [M][K]; B [N][K], or [K][N]
+    with btrans) into a C prefilled with 7: (problem, C, float64 product)."""
+    ops = _ops()
+    rng = np.random.RandomState(M + N + K)
+    a_np = rng.randint(-3, 4, (M, K)).astype(np.float32)
+    b_np = rng.randint(-3, 4, (N, K)).astype(np.float32)
+    a = torch.from_numpy(a_np).to(torch.bfloat16).to(dev)
+    b = torch.from_numpy(b_np.T.copy() if btrans else b_np).to(torch.bfloat16).to(dev)
+    c = torch.full((M, N), 7.0, device=dev)
+    p = ops.gemm_problem(ops.operand(a, 0, ops.rowmap(K)),
+                         ops.operand(b, btrans, ops.rowmap(N if btrans else K)), c, ops.rowmap(N),
+                         M, N, K)
+    p.keep = (a, b)
+    return p, c, a_np.astype(np.float64) @ b_np.astype(np.float64).T
+
+
+@pytest.mark.parametrize('name,M,N,K,btrans,fam_default,fam_opt', [
+    ('small_tiles', 256, 256, 64, 0, FAM_8R, FAM_FAST2),
+    ('n64_kmode', 4100, 48, 264, 1, FAM_FAST2, FAM_N64),
+    ('nosplit', 128, 128, 1024, 0, FAM_FAST2, FAM_FAST2)])
+def test_gemm_opts_select_per_call(name, M, N, K, btrans, fam_default, fam_opt, cuda_dev):
+    """asr_gemm_opts_t through run_gemm: each setting changes the call it is
+    given to and no other.  small_tiles keeps a 256 x 256 product off the ring
+    8-wave kernel (2-stage 128 x 128 instead); n64_kmode lets a K-major B with
+    N <= 64 take the 256 x 64 kernel; nosplit plans no split-K slabs, the
+    workspace query agrees (0 bytes) and the launch runs with a NULL workspace.
+    A NULL-opts call afterwards takes the default kernel and plan again.
+    Results equal float64 exactly (small integers)."""
+    import ctypes
+    from pytorch_end2end_speech_recognition_amd import _native as NL
+    ops = _ops()
+    ops.set_compute_dtype('bf16')
+    try:
+        for opts, fam in ((None, fam_default), (NL.GemmOpts(**{name: 1}), fam_opt),
+                          (None, fam_default)):
+            p, c, ref = _opts_problem(M, N, K, btrans, cuda_dev)
+            ops.run_gemm([p], cuda_dev, opts=opts)
+            torch.cuda.synchronize()
+            assert NL.query('asr_gemm_last_family') // 4 == fam, (name, opts is not None)
+            np.testing.assert_array_equal(c.cpu().numpy(), ref)
+            if name != 'nosplit':
+                continue
+            parr = ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+            nb = NL.query('asr_gemm_workspace_bytes', parr, 1, NL.ptr_struct(opts))
+            assert (nb == 0) if opts is not None else (nb > 0), nb
+            if opts is not None:    # and straight at the entry point: no workspace at all
+                c.fill_(7.0)
+                NL.call('asr_gemm_ws', parr, 1, NL.ASR_DT_BF16, None, 0,
+                        NL.stream_handle(cuda_dev), NL.ptr_struct(opts))
+                torch.cuda.synchronize()
+                np.testing.assert_array_equal(c.cpu().numpy(), ref)
+    finally:
+        ops.set_compute_dtype('fp32')
+
+
+def test_gemm_opts_bad_value_is_refused(cuda_dev):
+    """A setting other than 0 or 1: ASR_ERR_ARG (-1), nothing launched."""
+    import ctypes
+    from pytorch_end2end_speech_recognition_amd import _native as NL
+    p, c, _ = _opts_problem(256, 256, 64, 0, cuda_dev)
+    rc = NL.lib().asr_gemm_ws(ctypes.cast(ctypes.pointer(p), ctypes.c_void_p), 1, NL.ASR_DT_BF16,
+                              None, 0, NL.stream_handle(cuda_dev),
+                              ctypes.byref(NL.GemmOpts(small_tiles=2)))
+    torch.cuda.synchronize()
+    assert rc == -1
+    assert bool((c == 7.0).all())

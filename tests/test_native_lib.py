@@ -73,7 +73,8 @@ def test_gemm_split_plan_without_gpu():
 
     def nbytes(*ps):
         arr = (N.Gemm * len(ps))(*ps)
-        return N.query('asr_gemm_workspace_bytes', ctypes.cast(arr, ctypes.c_void_p), len(ps))
+        return N.query('asr_gemm_workspace_bytes', ctypes.cast(arr, ctypes.c_void_p), len(ps),
+                       None)
 
     n = nbytes(prob(2048, 512, 32000), prob(2048, 512, 32000))
     assert n >= 2 * 2 * 2048 * 512 * 4
