@@ -568,6 +568,60 @@ int asr_ctc_beam_rows(const float* logits, long long stride_t, long long stride_
                       int V, const int32_t* lens, int blank, int beam_width, int normalize,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------ hypothesis scoring
+ * asr_edit_distance: per utterance pair the edit distance between a decoded
+ *   hypothesis and its transcript with the substitution / insertion / deletion
+ *   counts of the reference's backtrace (utils/evaluation/edit_distance.py:
+ *   53-126), after the token-level form of the recipes' text clean-up.  One
+ *   launch on `stream`, integers only (bitwise reproducible), no allocation,
+ *   no host synchronisation, no library state.
+ *   hyp: int32 (int64 with opts->hyp_i64) [B][ld_hyp], ref: int32 [B][ld_ref];
+ *   hyp_lens / ref_lens int32 [B] are clipped to [0, max_hyp] / [0, max_ref],
+ *   and max_hyp <= ld_hyp, max_ref <= ld_ref.  out int32 [B][5] = {distance,
+ *   sub, ins, del, ref_units}; totals (nullable) int64 [5] += the column sums
+ *   (64-bit atomics: zero it once, read it once per evaluation).
+ *   Clean-up, in this order, of both sequences:
+ *     1. hypothesis only: cut before the first opts->eos (-1: no cut); entries
+ *        at or past the length and negative entries are not part of a sequence;
+ *     2. opts->map (nullable, int32 [map_len] on the device): token -> token,
+ *        a negative value deletes the token; tokens >= map_len pass unchanged;
+ *     3. opts->space >= 0: runs of the separator collapse to one, a leading
+ *        and a trailing separator go;
+ *     4. ASR_ED_WORD: the units are the maximal runs of non-separator tokens,
+ *        equal iff their token sequences are (a hash match is confirmed token
+ *        by token).  An empty sequence has ZERO units (Python's ''.split('_')
+ *        gives one empty word; deliberate);
+ *     5. ASR_ED_TOKEN: the units are the tokens left, separators included.
+ *   Table: d[i][0] = i, d[0][j] = j, d[i][j] = d[i-1][j-1] on a match, else
+ *   1 + min(diagonal, left, up).  Counts: the walk from (ref, hyp) to (0, 0)
+ *   that at each cell prefers correct (units match), then insertion (d[x][y]
+ *   == d[x][y-1] + 1), then substitution (d[x][y] == d[x-1][y-1] + 1), then
+ *   deletion; at x == 0 only insertions, at y == 0 only deletions.
+ *   ASR_ERR_UNSUPPORTED (nothing launched, asr_last_error says why): max_ref or
+ *   max_hyp above 4095, or an operand of 2 GiB or more.  ASR_ERR_ARG:
+ *   ASR_ED_WORD without a separator, a null pointer, a bad shape.
+ *   ASR_ERR_WORKSPACE: less than asr_edit_distance_ws_bytes(B, max_ref,
+ *   max_hyp), which is 0 for a refused shape; the workspace (the backtrace's
+ *   2-bit move codes when max_ref * ceil(max_hyp / 16) words exceed the 16 KB
+ *   kept in LDS) needs no initialisation.
+ */
+#define ASR_ED_TOKEN 0
+#define ASR_ED_WORD 1
+typedef struct {
+  int unit;            /* ASR_ED_TOKEN | ASR_ED_WORD */
+  int eos;             /* hypothesis is cut before its first eos; -1: no cut */
+  int space;           /* separator token; -1: none (required >= 0 for ASR_ED_WORD) */
+  const int32_t* map;  /* nullable LUT [map_len]: token -> token, or -1 = delete the token */
+  int map_len;         /* tokens outside [0, map_len) pass unchanged */
+  int hyp_i64;         /* hyp tokens are int64 (attention decoders) instead of int32 */
+} asr_edit_opts_t;
+size_t asr_edit_distance_ws_bytes(int B, int max_ref, int max_hyp);
+int asr_edit_distance(const void* hyp, long long ld_hyp, const int32_t* hyp_lens,
+                      const int32_t* ref, long long ld_ref, const int32_t* ref_lens, int B,
+                      int max_ref, int max_hyp, const asr_edit_opts_t* opts,
+                      int32_t* out /* [B][5] */, long long* totals /* [5], += , nullable */,
+                      void* workspace, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------- losses
  * Fused softmax cross-entropy + uniform label smoothing over rows of V logits
  * (attention_seq2seq.py:588-601, criterion.py:51-80, ctc.py:329-337):

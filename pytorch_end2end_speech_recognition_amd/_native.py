@@ -135,6 +135,9 @@ SIGNATURES = {
                                     c_int, c_vp, c_size, c_vp, c_vp, c_vp, c_vp]),
     'asr_ctc_beam_rows': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                   c_vp, c_size, c_vp]),
+    'asr_edit_distance_ws_bytes': (c_size, [c_int, c_int, c_int]),
+    'asr_edit_distance': (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp,
+                                  c_vp, c_vp, c_vp, c_size, c_vp]),
     'asr_xent_workspace_bytes': (c_size, [c_int]),
     'asr_xent_forward': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_float, c_float, c_vp,
                                  c_vp, c_size, c_vp]),
@@ -313,6 +316,16 @@ class AttBeamOpts(ctypes.Structure):
         ('length_penalty', ctypes.c_double), ('ld_ih', c_ll)] + [
         (n, c_vp) for n in ('w_ih', 'w_hh', 'b_ih', 'b_hh', 'w_dec', 'w_conv', 'conv_w', 'v',
                             'w_d', 'b_d', 'w_c', 'b_c', 'w_fc', 'b_fc', 'emb_w')]
+
+
+ASR_ED_TOKEN = 0
+ASR_ED_WORD = 1
+
+
+class EditOpts(ctypes.Structure):
+    """asr_edit_opts_t"""
+    _fields_ = [('unit', c_int), ('eos', c_int), ('space', c_int), ('map', c_vp),
+                ('map_len', c_int), ('hyp_i64', c_int)]
 
 
 class Gemm(ctypes.Structure):

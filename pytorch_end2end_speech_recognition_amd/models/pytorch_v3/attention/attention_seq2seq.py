@@ -529,6 +529,37 @@ class AttentionSeq2seq(ModelBase):
         check_recurrences(self)
         return best_hyps, aw, self.encoder.last_perm_np.copy()
 
+    # error_rate() sets a list here for the length of one decode(): the device
+    # decode paths append their (tokens, lengths) device tensors to it and
+    # return (None, None) instead of host copies
+    _hyp_capture = None
+
+    def error_rate(self, xs, x_lens, ys, y_lens, beam_width, max_decode_len=None, meter=None,
+                   **decode_kwargs):
+        """decode() scored against ys: the same decode path (device beam
+        search, fused greedy pass, or the step-by-step / host paths), the
+        hypotheses of the device paths kept as device tensors, those of a path
+        that only yields host arrays uploaded; ys [B, L] (padded, decode()'s
+        index space) and y_lens reordered by the decode's perm_idx; the batch
+        fed to `meter` (utils.evaluation.edit_distance.ErrorRateMeter; None: a
+        throw-away token meter that cuts at <eos>).  Returns the batch's int32
+        [B, 5] device tensor (distance, sub, ins, del, reference units), rows
+        in perm_idx order.  decode_kwargs: decode()'s remaining arguments."""
+        from ....utils.evaluation.edit_distance import ErrorRateMeter, score_decoded
+        if max_decode_len is None:
+            raise ValueError('error_rate: an attention model needs max_decode_len')
+        task = decode_kwargs.get('task_index', 0)
+        cap = []
+        self._hyp_capture = cap
+        try:
+            hyps, _, perm = self.decode(xs, x_lens, beam_width, max_decode_len, **decode_kwargs)
+        finally:
+            self._hyp_capture = None
+        if meter is None:
+            meter = ErrorRateMeter('token', eos=getattr(self, 'eos_%d' % task))
+        hyp_d, hl_d = cap[-1] if hyps is None else (None, None)
+        return score_decoded(meter, self.device, hyp_d, hl_d, hyps, ys, y_lens, perm)
+
     def _infer_step(self, task, dir, t, y_emb, st, enc, enc_a, lens):
         """One inference decoder step (:963-1001) on the HIP per-step ops, for any
         decoding order / decoder depth.  st = dict(h, c (lists per layer), dec,
@@ -640,6 +671,9 @@ class AttentionSeq2seq(ModelBase):
                                   getattr(self, 'eos_%d' % task))
         if out is None:
             return None
+        if self._hyp_capture is not None and dir == 'fwd':
+            self._hyp_capture.append((out[0], out[1]))     # error_rate(): stay on the device
+            return None, None
         toks, hl, sc, aw = (t.cpu().numpy() for t in out)
         if _scores is not None:
             _scores.extend(float(v) for v in sc)
@@ -835,6 +869,12 @@ class AttentionSeq2seq(ModelBase):
                                          att.W_dec_head0.fc.weight, *att.conv_weights(),
                                          att.V_head0.fc.weight, gen,
                                          max_decode_len)
+        if self._hyp_capture is not None and dir == 'fwd':   # error_rate(): stay on the device
+            all_eos = (toks == getattr(self, 'eos_%d' % task)).all(dim=0)
+            n = torch.where(all_eos.any(), all_eos.int().argmax() + 1,
+                            torch.tensor(toks.shape[1], device=toks.device))
+            self._hyp_capture.append((toks, n.to(torch.int32).expand(toks.shape[0]).contiguous()))
+            return None, None
         toks = toks.cpu().numpy()
         all_eos = np.nonzero((toks == getattr(self, 'eos_%d' % task)).all(axis=0))[0]
         n = int(all_eos[0]) + 1 if len(all_eos) else toks.shape[1]   # :1017-1019

@@ -230,6 +230,35 @@ class CTC(ModelBase):
 
     @eval_retry
     @torch.no_grad()
+    def error_rate(self, xs, x_lens, ys, y_lens, beam_width, max_decode_len=None, meter=None,
+                   task_index=0, **decode_kwargs):
+        """decode() scored against ys without leaving the device: the same
+        best path / prefix beam search, the hypotheses kept as device tensors,
+        ys [B, L] (padded, the index space decode() returns) and y_lens
+        reordered by the decode's perm_idx, and the batch fed to `meter`
+        (utils.evaluation.edit_distance.ErrorRateMeter; a throw-away token
+        meter when None).  Returns the batch's int32 [B, 5] device tensor
+        (distance, sub, ins, del, reference units), rows in perm_idx order.
+        decode_kwargs: decode()'s remaining arguments (they do not affect CTC
+        decoding)."""
+        from ....utils.evaluation.edit_distance import ErrorRateMeter, score_decoded
+        self.eval()
+        xs_d = self.np2var(xs, dtype='float')
+        logits, out_lens_d, _ = self._task_logits(xs_d, x_lens, task_index)
+        check_recurrences(self)
+        lens = out_lens_d.to(logits.device).int()
+        if beam_width == 1:
+            hyps, hl = ops.ctc_best_path(logits, lens, 0)
+        else:
+            hyps, hl, _ = ops.ctc_beam_search(logits, lens, int(beam_width), 0, normalize=True)
+        if meter is None:
+            meter = ErrorRateMeter('token')
+        # blank = 0 on the device, labels from 0 in decode()'s index space
+        return score_decoded(meter, logits.device, hyps - 1, hl, None, ys, y_lens,
+                             self.encoder.last_perm_np)
+
+    @eval_retry
+    @torch.no_grad()
     def posteriors(self, xs, x_lens, temperature=1, blank_scale=None, task_idx=0):
         """ctc.py:455-502."""
         self.eval()

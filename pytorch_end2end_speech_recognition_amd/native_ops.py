@@ -2879,6 +2879,170 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True):
     return hyps, hl, scores
 
 
+# ---------------------------------------------------------------------------
+# Hypothesis scoring (csrc/edit_distance.hip)
+# ---------------------------------------------------------------------------
+_edit = {'path': None, 'ws': {}}   # ws: device -> workspace of the largest call so far
+
+
+def last_edit_distance_path():
+    """'device' or 'host': where the last edit_distance ran (None before the
+    first one).  'host': the kernel refused the shape (ASR_ERR_UNSUPPORTED)."""
+    return _edit['path']
+
+
+def edit_clean_host(seq, n, is_hyp, eos, space, token_map):
+    """Steps 1-3 of asr_edit_distance's clean-up on a host row."""
+    out = []
+    for t in list(seq)[:max(0, int(n))]:
+        t = int(t)
+        if t < 0:
+            continue
+        if is_hyp and eos is not None and eos >= 0 and t == eos:
+            break
+        if token_map is not None and t < len(token_map):
+            t = int(token_map[t])
+            if t < 0:
+                continue
+        if space is not None and space >= 0 and t == space and (not out or out[-1] == space):
+            continue
+        out.append(t)
+    if space is not None and space >= 0 and out and out[-1] == space:
+        out.pop()
+    return out
+
+
+def edit_units_host(tokens, unit, space):
+    """Steps 4-5: the units of a cleaned row (words as tuples of tokens)."""
+    if unit != 'word':
+        return list(tokens)
+    words, cur = [], []
+    for t in tokens:
+        if t == space:
+            words.append(tuple(cur))
+            cur = []
+        else:
+            cur.append(t)
+    if cur or words:
+        words.append(tuple(cur))
+    return words
+
+
+def edit_counts_host(ref, hyp):
+    """(distance, sub, ins, del) of two unit lists: compute_wer's table and
+    backtrace (utils/evaluation/edit_distance.py:53-126) with the border rule
+    of asr_edit_distance (x == 0: insertions, y == 0: deletions)."""
+    R, H = len(ref), len(hyp)
+    d = [list(range(H + 1))] + [[i] + [0] * H for i in range(1, R + 1)]
+    for i in range(1, R + 1):
+        di, dp, r = d[i], d[i - 1], ref[i - 1]
+        for j in range(1, H + 1):
+            di[j] = dp[j - 1] if r == hyp[j - 1] else 1 + min(dp[j - 1], di[j - 1], dp[j])
+    x, y, sub, ins, dele = R, H, 0, 0, 0
+    while x > 0 or y > 0:
+        if x == 0:
+            ins, y = ins + 1, y - 1
+        elif y == 0:
+            dele, x = dele + 1, x - 1
+        elif ref[x - 1] == hyp[y - 1]:
+            x, y = x - 1, y - 1
+        elif d[x][y] == d[x][y - 1] + 1:
+            ins, y = ins + 1, y - 1
+        elif d[x][y] == d[x - 1][y - 1] + 1:
+            sub, x, y = sub + 1, x - 1, y - 1
+        else:
+            dele, x = dele + 1, x - 1
+    return d[R][H], sub, ins, dele
+
+
+def edit_distance_host(hyp, hyp_lens, ref, ref_lens, unit='token', eos=None, space=None,
+                       token_map=None):
+    """asr_edit_distance restated on host arrays: int32 [B, 5]."""
+    out = np.zeros((len(hyp), 5), np.int32)
+    for b in range(len(hyp)):
+        r = edit_units_host(edit_clean_host(ref[b], ref_lens[b], False, eos, space, token_map),
+                            unit, space)
+        h = edit_units_host(edit_clean_host(hyp[b], hyp_lens[b], True, eos, space, token_map),
+                            unit, space)
+        out[b, :4] = edit_counts_host(r, h)
+        out[b, 4] = len(r)
+    return out
+
+
+def _i32_rows(t, keep_i64=False):
+    if t.dtype != torch.int32 and not (keep_i64 and t.dtype == torch.int64):
+        t = t.to(torch.int32)
+    if t.dim() != 2:
+        raise ValueError('edit_distance: [B, L] token tensors expected, got %r' % (tuple(t.shape),))
+    if t.shape[1] == 0:      # no storage to point at: one column of padding instead
+        return torch.full((t.shape[0], 1), -1, dtype=t.dtype, device=t.device)
+    return t if t.stride(1) == 1 else t.contiguous()
+
+
+@torch.no_grad()
+def edit_distance(hyp, hyp_lens, ref, ref_lens, unit='token', eos=None, space=None,
+                  token_map=None, totals=None):
+    """Edit distance and error counts per utterance on the device
+    (asr_edit_distance): hyp int32 / int64 [B, Lh] and ref [B, Lr] device
+    tensors as the decoders return them, lengths [B].  unit 'token' or 'word'
+    (needs `space`); eos: the hypothesis is cut before it; space: separator
+    (runs collapse, leading / trailing go); token_map: int sequence or device
+    int32 tensor, token -> token or -1 to delete.  Returns int32 [B, 5] =
+    (distance, sub, ins, del, ref units) on the device; totals (int64 [5]
+    device tensor) += its column sums, with no host synchronisation.  A shape
+    the kernel refuses runs edit_distance_host on host copies instead and
+    last_edit_distance_path() says so."""
+    N.require_device(hyp, ref)
+    if unit not in ('token', 'word'):
+        raise ValueError("edit_distance: unit must be 'token' or 'word'")
+    dev = hyp.device
+    hyp, ref = _i32_rows(hyp, keep_i64=True), _i32_rows(ref)
+    B = hyp.shape[0]
+    as_lens = lambda l: (l if torch.is_tensor(l) else torch.as_tensor(   # noqa: E731
+        np.asarray(l).astype(np.int32))).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    hl, rl = as_lens(hyp_lens), as_lens(ref_lens)
+    if ref.shape[0] != B or hl.numel() != B or rl.numel() != B:
+        raise ValueError('edit_distance: batch sizes differ')
+    if totals is not None and (totals.dtype != torch.int64 or totals.numel() != 5 or
+                               not totals.is_cuda or not totals.is_contiguous()):
+        raise ValueError('edit_distance: totals must be a contiguous int64 [5] device tensor')
+    out = torch.zeros(B, 5, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out
+    if token_map is not None and not torch.is_tensor(token_map):
+        token_map = torch.as_tensor(np.asarray(token_map).astype(np.int32))
+    if token_map is not None:
+        token_map = token_map.to(device=dev, dtype=torch.int32).contiguous()
+    max_h, max_r = hyp.shape[1], ref.shape[1]
+    opts = N.EditOpts(N.ASR_ED_WORD if unit == 'word' else N.ASR_ED_TOKEN,
+                      -1 if eos is None else int(eos), -1 if space is None else int(space),
+                      None if token_map is None else token_map.data_ptr(),
+                      0 if token_map is None else token_map.numel(),
+                      int(hyp.dtype == torch.int64))
+    nb = N.query('asr_edit_distance_ws_bytes', B, max_r, max_h)
+    ws = _edit['ws'].get(dev)
+    if ws is None or ws.numel() < nb:
+        ws = _edit['ws'][dev] = _ws(nb, dev)
+    rc = getattr(N.lib(), 'asr_edit_distance')(
+        N.ptr(hyp), max(hyp.stride(0), max_h), N.ptr(hl), N.ptr(ref), max(ref.stride(0), max_r),
+        N.ptr(rl), B, max_r, max_h, ctypes.byref(opts), N.ptr(out), N.ptr(totals), N.ptr(ws),
+        ws.numel(), N.stream_handle(dev))
+    if rc == N.ASR_OK:
+        _edit['path'] = 'device'
+        return out
+    if rc != N.ASR_ERR_UNSUPPORTED:
+        raise N.NativeError('asr_edit_distance failed (rc=%d): %s'
+                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
+    _edit['path'] = 'host'
+    res = edit_distance_host(hyp.cpu().numpy(), hl.cpu().numpy(), ref.cpu().numpy(),
+                             rl.cpu().numpy(), unit, eos, space,
+                             None if token_map is None else token_map.cpu().numpy())
+    out = torch.from_numpy(res).to(dev)
+    if totals is not None:
+        totals += out.sum(dim=0, dtype=torch.int64)
+    return out
+
+
 def row_argmax(x):
     N.require_device(x)
     x = x.contiguous()
