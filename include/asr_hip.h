@@ -1104,6 +1104,83 @@ int asr_vgg_block_forward_given_p(const uint16_t* P, int B, int T, int F, int C,
                                   const float* mpart, const float* qpart, int nblk,
                                   void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------- kf x kt convolutions (pure-CNN encoder)
+ * Replaces the Conv2d of CNNEncoder layers whose kernel is not 3x3
+ * (encoders/cnn.py:68-73: kernel_size = (kf, kt) over [B, C, freq, time],
+ * stride 1, padding 1), kf, kt in {3, 5}; csrc/conv_taps.hip.  Operands use the
+ * VGG front-end's layout: channels-last with a one-pixel zero halo,
+ * x [B][T+2][F+2][Cin].  The output grid is To x Fo = (T + 3 - kt) x (F + 3 - kf)
+ * valid pixels, written to the interior of z [B][To+2][Fo+2][Cout] f32 (the
+ * caller zeroes the halo, asr_vgg_zero_halo): input and output rows have their
+ * own pitches.  Tap index = dt * kf + df (time-major).  compute_dtype
+ * ASR_DT_BF16: bf16 operands, bf16 MFMA, f32 sums; Cin, Cout multiples of 16 up
+ * to 256.  ASR_DT_F32: f32 operands, exact f32 products and sums in k order;
+ * Cout % 8 == 0.  A shape a kernel does not take returns ASR_ERR_UNSUPPORTED
+ * before any launch (asr_last_error says why).
+ * asr_conv_taps_supported: 1 when forward, input gradient and weight gradient
+ *   all take the shape (T, F = the layer input's valid extents).
+ * asr_conv_taps_forward: z(to, fo)[n] = bias[n] + sum_{dt, df, c}
+ *   x_p(to + dt, fo + df)[c] * w[n][(dt kf + df) Cin + c]; w = the mode-0 image
+ *   [Cout][kf kt Cin] of asr_conv_taps_weight_pack, bias f32 [Cout] or NULL.
+ * asr_conv_taps_dgrad (autograd of that Conv2d w.r.t. its input): dx interior
+ *   [B][T+2][F+2][Cin] f32 from dz [B][To+2][Fo+2][Cout] (zero halo) and wt =
+ *   the mode-1 image [Cin][kf kt Cout] (mirrored, transposed): the forward
+ *   kernel with the pitches exchanged, writing a grid k - 3 larger per axis.
+ * asr_conv_taps_wgrad: packed [Cout][kf kt Cin] f32 (overwritten) =
+ *   sum over pixels of dz(to, fo)[n] * x_p(to + dt, fo + df)[c]; bf16 mode sums
+ *   per-chunk partials from the workspace in a fixed order (two runs are
+ *   bitwise equal).  asr_conv_taps_wgrad_workspace_bytes: 0 = shape not taken.
+ * asr_conv_taps_weight_pack: images of the torch weight W [Co][Ci][kf][kt]:
+ *   mode 0 out[co][(dt kf + df) Cip + ci] = W[co][ci][df][dt] (channels ci >= Ci
+ *   of the pitch Cip written 0), mode 1 (Cip == Ci) out[ci][(dt kf + df) Co + co]
+ *   = W[co][ci][kf-1-df][kt-1-dt]; out_dtype f32 / bf16.
+ * asr_conv_taps_weight_unpack_acc: dW [Co][Ci][kf][kt] += the mode-0 image. */
+int asr_conv_taps_supported(int compute_dtype, int B, int T, int F, int Cin, int Cout, int kf,
+                            int kt);
+int asr_conv_taps_forward(int compute_dtype, const void* x, int B, int T, int F, int Cin,
+                          const void* w, int Cout, int kf, int kt, const float* bias, float* z,
+                          void* stream);
+int asr_conv_taps_dgrad(int compute_dtype, const void* dz, int B, int T, int F, int Cin,
+                        const void* wt, int Cout, int kf, int kt, float* dx, void* stream);
+size_t asr_conv_taps_wgrad_workspace_bytes(int compute_dtype, int B, int T, int F, int Cin,
+                                           int Cout, int kf, int kt);
+int asr_conv_taps_wgrad(int compute_dtype, const void* x, const void* dz, int B, int T, int F,
+                        int Cin, int Cout, int kf, int kt, float* packed, void* ws,
+                        size_t ws_bytes, void* stream);
+int asr_conv_taps_weight_pack(const float* w, int Co, int Ci, int Cip, int kf, int kt, int mode,
+                              int out_dtype, void* out, void* stream);
+int asr_conv_taps_weight_unpack_acc(const float* packed, int Co, int Ci, int Cip, int kf, int kt,
+                                    float* dw, void* stream);
+/* Activation -> MaxPool2d -> BatchNorm2d -> Dropout of a CNNEncoder layer
+ * (encoders/cnn.py:78-111) with the activation given: ReLU, PReLU (cnn.py:82,
+ * slope = device pointer to the one learnable slope) or hard-tanh(0, 20)
+ * (cnn.py:84); csrc/cnn_act.hip.  Arguments as asr_vgg_block_forward /
+ * _backward_ex (z, dz haloed f32 [B][T+2][F+2][C]; P f32 [B][To][Fo][C]; out
+ * the next layer's haloed operand f32 / bf16, or flat f32; dnext f32, haloed or
+ * flat).  The pool returns the maximum of the activated values present in its
+ * window (they may be negative).  Backward: PReLU dz = dy where z > 0 else
+ * slope * dy, *dslope += sum of dy * z over z <= 0; hard-tanh dz = dy where
+ * 0 < z < 20; dbias (nullable) += per-channel sum of dz; training = the
+ * forward's flag (eval: BatchNorm used the running statistics).  Every sum is
+ * taken in a fixed order (two runs are bitwise equal). */
+#define ASR_ACT_RELU 0
+#define ASR_ACT_PRELU 1
+#define ASR_ACT_HARDTANH 2
+size_t asr_cnn_act_workspace_bytes(int B, int T, int F, int C);
+int asr_cnn_act_forward(const float* z, int B, int T, int F, int C, int act, const float* slope,
+                        int pt, int pf, int ceil_mode, float* P, uint8_t* slot,
+                        const float* gamma, const float* beta, float* run_mean, float* run_var,
+                        int training, float momentum, float eps, float* bn_mean, float* bn_rstd,
+                        float drop, unsigned long long seed, void* out, int out_dtype, int flat,
+                        void* workspace, size_t ws_bytes, void* stream);
+int asr_cnn_act_backward(const float* dnext, int flat, const float* z, int B, int T, int F, int C,
+                         int act, const float* slope, int pt, int pf, int ceil_mode,
+                         const float* P, const uint8_t* slot, const float* gamma,
+                         const float* bn_mean, const float* bn_rstd, int training, float* dgamma,
+                         float* dbeta, float drop, unsigned long long seed, void* dz, int dz_dtype,
+                         float* dbias, float* dslope, void* workspace, size_t ws_bytes,
+                         void* stream);
+
 /* ----------------------------------------------------------- profiling
  * Sampled HIP-event timing of the recurrence step kernels on their own stream
  * (bench.py's live roofline measurement).  asr_prof_begin(stride): bracket

@@ -211,6 +211,27 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_float, ctypes.c_ulonglong,
                                            c_vp, c_int, c_vp, c_vp, c_size, c_vp]),
+    'asr_conv_taps_supported': (c_int, [c_int] * 8),
+    'asr_conv_taps_forward': (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                      c_int, c_vp, c_vp, c_vp]),
+    'asr_conv_taps_dgrad': (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                    c_int, c_vp, c_vp]),
+    'asr_conv_taps_wgrad_workspace_bytes': (c_size, [c_int] * 8),
+    'asr_conv_taps_wgrad': (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_vp, c_vp, c_size, c_vp]),
+    'asr_conv_taps_weight_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_vp, c_vp]),
+    'asr_conv_taps_weight_unpack_acc': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                c_vp]),
+    'asr_cnn_act_workspace_bytes': (c_size, [c_int, c_int, c_int, c_int]),
+    'asr_cnn_act_forward': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_float,
+                                    c_float, c_vp, c_vp, c_float, ctypes.c_ulonglong, c_vp, c_int,
+                                    c_int, c_vp, c_size, c_vp]),
+    'asr_cnn_act_backward': (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                     c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                     c_vp, c_vp, c_float, ctypes.c_ulonglong, c_vp, c_int, c_vp,
+                                     c_vp, c_vp, c_size, c_vp]),
     'asr_prof_begin': (c_int, [c_int]),
     'asr_prof_end': (c_int, [c_vp, c_vp, c_vp, c_int]),
     'asr_prof_samples': (c_ll, [c_int, c_vp, c_vp, c_vp, c_ll]),

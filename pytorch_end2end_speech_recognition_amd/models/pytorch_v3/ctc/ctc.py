@@ -81,6 +81,16 @@ class CTC(ModelBase):
                 conv_kernel_sizes=conv_kernel_sizes, conv_strides=conv_strides,
                 poolings=poolings, activation=activation, batch_norm=batch_norm,
                 residual=encoder_residual, dense_residual=encoder_dense_residual, nin=0)
+        elif encoder_type == 'cnn':                                  # ctc.py:197-209
+            assert num_stack == 1 and splice == 1
+            self.encoder = load(encoder_type='cnn')(
+                input_size=input_size, input_channel=input_channel, conv_channels=conv_channels,
+                conv_kernel_sizes=conv_kernel_sizes, conv_strides=conv_strides,
+                poolings=poolings, dropout_input=dropout_input, dropout_hidden=dropout_encoder,
+                activation=activation, batch_norm=batch_norm)
+            # the CNN encoder drops its own output (per-layer dropout): nothing is
+            # handed over to the first layer after it
+            self.encoder.pending_output_drop = None
         else:
             raise NotImplementedError('encoder_type=%s' % encoder_type)
 
@@ -90,6 +100,8 @@ class CTC(ModelBase):
         if len(fc_list) > 0:
             for i in range(len(fc_list)):
                 din = self.encoder_num_units if i == 0 else fc_list[i - 1]
+                if i == 0 and encoder_type == 'cnn':                 # ctc.py:219-220
+                    din = self.encoder.output_size
                 setattr(self, 'fc_' + str(i), LinearND(din, fc_list[i], dropout=dropout_encoder))
             self.fc_out = LinearND(fc_list[-1], self.num_classes)
         else:
@@ -99,7 +111,7 @@ class CTC(ModelBase):
         self.init_weights(parameter_init, distribution=parameter_init_distribution,
                           ignore_keys=['bias'])
         self.init_weights(0, distribution='constant', keys=['bias'])
-        if recurrent_weight_orthogonal:
+        if recurrent_weight_orthogonal and encoder_type != 'cnn':    # ctc.py:256
             self.init_weights(parameter_init, distribution='orthogonal',
                               keys=[encoder_type, 'weight'], ignore_keys=['bias'])
         if init_forget_gate_bias_with_one:
@@ -142,7 +154,9 @@ class CTC(ModelBase):
         """ctc.py:344-396.  defer_head: the output layer(s) whose only consumer
         is the CTC loss are returned as _Head(x, fc, drop) for _ctc_term's
         fused LinearND + CTC op instead of being applied here."""
-        if is_multi_task:
+        if self.encoder_type == 'cnn':
+            xs, x_lens, perm_idx = self._encode_cnn(xs, x_lens)
+        elif is_multi_task:
             xs, x_lens, xs_sub, x_lens_sub, perm_idx = self.encoder(
                 xs, x_lens, volatile=not self.training)
         else:
@@ -167,6 +181,19 @@ class CTC(ModelBase):
                 logits_sub = self.fc_out_sub(xs_sub)
             return logits, x_lens, logits_sub, x_lens_sub, perm_idx
         return logits, x_lens, perm_idx
+
+    def _encode_cnn(self, xs, x_lens):
+        """ctc.py:360-363 (encoder_type == 'cnn'): the encoder returns (xs, x_lens),
+        nothing is sorted and perm_idx is None; the identity is kept as
+        ``last_perm_np`` so the label gather and the decoders read rows in place."""
+        enc = self.encoder
+        if torch.is_tensor(x_lens):
+            x_lens = x_lens.detach().cpu().numpy()
+        xs, lens = enc(xs, np.asarray(x_lens).astype(np.int64))
+        enc.last_lens_np = np.asarray(lens).astype(np.int32)
+        enc.last_perm_np = np.arange(len(enc.last_lens_np), dtype=np.int64)
+        enc.pending_output_drop = None
+        return xs, ops.h2d(enc.last_lens_np, xs.device), None
 
     def _ctc_term(self, logits, lens_d, ys, y_lens, perm, B):
         """sum_b cost_b / B on the HIP CTC kernel (+ label smoothing, ctc.py:319-337)."""

@@ -1,12 +1,15 @@
 """CNNEncoder: the reference's VGG front-end (models/pytorch_v3/encoders/cnn.py)
-on the MI355X HIP kernels (csrc/cnn.hip + tap-addressed MFMA GEMMs).
+on the MI355X HIP kernels (csrc/cnn.hip + tap-addressed MFMA GEMMs), and its
+pure-CNN encoder (kf x kt kernels with extents 3 or 5, PReLU / hard-tanh:
+csrc/conv_taps.hip + csrc/cnn_act.hip; ops.vgg_front picks the kernels).
 
-Same constructor arguments and the same ``layers`` nn.Sequential (Conv2d, ReLU,
-MaxPool2d, BatchNorm2d, Dropout modules in the reference's order, cnn.py:74-122),
+Same constructor arguments and the same ``layers`` nn.Sequential (Conv2d, ReLU /
+PReLU / Hardtanh, MaxPool2d, BatchNorm2d, Dropout modules in the reference's
+order, cnn.py:74-122),
 so state_dict keys, the construction-time RNG consumption and
 ``output_size`` are identical; the modules are parameter / running-stat
 holders and their forwards never run.  Forward semantics (cnn.py:124-165):
-input dropout, [B, T, F] viewed as [B, 1, F, T], per layer conv 3x3 ->
+input dropout, [B, T, F] viewed as [B, 1, F, T], per layer conv ->
 activation -> max-pool (first floor mode, later ceil mode) -> batch norm ->
 dropout, output [B, T', F' * C], and x_lens from ConvOutSize (cnn_utils.py:
 34-37) which applies the FLOOR rule to every pool, so a ceil-mode pool over an
@@ -18,6 +21,9 @@ import numpy as np
 import torch.nn as nn
 
 from .... import native_ops as ops
+
+
+_ACTS = {'relu': ops.ACT_RELU, 'prelu': ops.ACT_PRELU, 'hard_tanh': ops.ACT_HARDTANH}
 
 
 class CNNEncoder(nn.Module):
@@ -33,11 +39,17 @@ class CNNEncoder(nn.Module):
         unsupported = []
         if input_channel != 1:
             unsupported.append('input_channel=%d' % input_channel)
-        if activation != 'relu':
+        if activation == 'maxout':
+            # the reference's Maxout(1, 1, 2) (cnn.py:86) is an nn.Linear(1, 2) over
+            # the last (time) axis: it fails on any input whose time extent is not 1
+            unsupported.append('activation=maxout (the reference cannot run it either: its '
+                               'Maxout(1, 1, 2) is a Linear over a time axis of extent 1)')
+        elif activation not in _ACTS:
             unsupported.append('activation=%s' % activation)
         for k, st, pl in zip(conv_kernel_sizes, conv_strides, poolings):
-            if list(k) != [3, 3] or list(st) != [1, 1]:
-                unsupported.append('conv kernel %s stride %s (3x3 / 1x1 only)' % (k, st))
+            if (len(k) != 2 or any(e not in (3, 5) for e in k)) or list(st) != [1, 1]:
+                unsupported.append('conv kernel %s stride %s (extents 3 or 5 / 1x1 only)'
+                                   % (k, st))
             if len(pl) and (len(pl) != 2 or min(pl) < 1):
                 unsupported.append('pooling %s' % (pl,))
         if unsupported:
@@ -47,6 +59,7 @@ class CNNEncoder(nn.Module):
         self.dropout_hidden_p = float(dropout_hidden)
         self.dropout_input = nn.Dropout(p=dropout_input)
         self.batch_norm = batch_norm
+        self.activation = activation
 
         layers, self._plan = [], []
         in_c, in_freq = self.input_channel, self.input_freq
@@ -59,7 +72,13 @@ class CNNEncoder(nn.Module):
             layers.append(conv)
             in_freq = math.floor((in_freq + 2 * conv.padding[0] - conv.kernel_size[0]) /
                                  conv.stride[0] + 1)
-            layers.append(nn.ReLU())
+            if activation == 'relu':                                 # cnn.py:79-84
+                act = nn.ReLU()
+            elif activation == 'prelu':
+                act = nn.PReLU(num_parameters=1, init=0.2)
+            else:
+                act = nn.Hardtanh(min_val=0, max_val=20, inplace=True)
+            layers.append(act)
             pool = None
             if len(poolings[l]) > 0:
                 pool = nn.MaxPool2d(kernel_size=tuple(poolings[l]), stride=tuple(poolings[l]),
@@ -73,7 +92,7 @@ class CNNEncoder(nn.Module):
                 bn = nn.BatchNorm2d(conv_channels[l])
                 layers.append(bn)
             layers.append(nn.Dropout(p=dropout_hidden))
-            self._plan.append((conv, pool, bn))
+            self._plan.append((conv, pool, bn, act))
             in_c = conv_channels[l]
         self.layers = nn.Sequential(*layers)
         self.output_size = conv_channels[-1] * in_freq
@@ -94,7 +113,7 @@ class CNNEncoder(nn.Module):
         if self.training and self.dropout_input_p > 0:
             xs = ops.dropout(xs, self.dropout_input_p)
         specs = []
-        for conv, pool, bn in self._plan:
+        for conv, pool, bn, act in self._plan:
             pt, pf = (pool.kernel_size[1], pool.kernel_size[0]) if pool is not None else (0, 0)
             specs.append(dict(w=conv.weight, b=conv.bias, pt=pt, pf=pf,
                               ceil=int(bool(pool is not None and pool.ceil_mode)),
@@ -103,7 +122,9 @@ class CNNEncoder(nn.Module):
                               run_mean=bn.running_mean if bn is not None else None,
                               run_var=bn.running_var if bn is not None else None,
                               momentum=bn.momentum if bn is not None else 0.1,
-                              eps=bn.eps if bn is not None else 1e-5, bn=bn))
+                              eps=bn.eps if bn is not None else 1e-5, bn=bn,
+                              act=_ACTS[self.activation],
+                              slope=act.weight if isinstance(act, nn.PReLU) else None))
         out = ops.vgg_front(xs, specs, self.training, self.dropout_hidden_p)
         lens = np.array([self.conv_out_len(int(x), 1) for x in np.asarray(x_lens)], np.int32)
         return out, lens

@@ -1,10 +1,12 @@
 """Encoder registry (reference models/pytorch_v3/encoders/load_encoder.py:15-35)."""
+from .cnn import CNNEncoder
 from .rnn import RNNEncoder
 
 ENCODERS = {
     'lstm': RNNEncoder,
     'gru': RNNEncoder,
     'rnn': RNNEncoder,
+    'cnn': CNNEncoder,
 }
 
 

@@ -3432,7 +3432,195 @@ class _nullctx(object):
         return False
 
 
+ACT_RELU, ACT_PRELU, ACT_HARDTANH = 0, 1, 2
+
+
+def _spec_kernel(sp):
+    """(kf, kt) of a layer spec: the Conv2d weight is [Co][Ci][kf][kt]."""
+    return int(sp['w'].shape[2]), int(sp['w'].shape[3])
+
+
+def _needs_taps(specs):
+    """A net the 3x3 / ReLU kernels of VGGFn do not cover."""
+    return any(_spec_kernel(sp) != (3, 3) or sp.get('act', ACT_RELU) != ACT_RELU for sp in specs)
+
+
+def conv_taps_forward(x, B, T, F, cin, w_img, cout, kf, kt, bias, z, cd=None):
+    """z interior = the kf x kt convolution of the haloed operand x (asr_conv_taps_forward)."""
+    N.require_device(x, w_img, z)
+    N.call('asr_conv_taps_forward', compute_dtype() if cd is None else cd, N.ptr(x), int(B), int(T),
+           int(F), int(cin), N.ptr(w_img), int(cout), int(kf), int(kt), N.ptr(bias), N.ptr(z),
+           N.stream_handle(x.device))
+
+
+def conv_taps_dgrad(dz, B, T, F, cin, wt_img, cout, kf, kt, dx, cd=None):
+    """dx interior [B][T+2][F+2][cin] from dz [B][To+2][Fo+2][cout] (asr_conv_taps_dgrad)."""
+    N.require_device(dz, wt_img, dx)
+    N.call('asr_conv_taps_dgrad', compute_dtype() if cd is None else cd, N.ptr(dz), int(B), int(T),
+           int(F), int(cin), N.ptr(wt_img), int(cout), int(kf), int(kt), N.ptr(dx),
+           N.stream_handle(dz.device))
+
+
+def conv_taps_wgrad(x, dz, B, T, F, cin, cout, kf, kt, packed, cd=None):
+    """packed [cout][kf kt cin] f32 = the weight-gradient image (asr_conv_taps_wgrad)."""
+    N.require_device(x, dz, packed)
+    cd = compute_dtype() if cd is None else cd
+    nb = N.query('asr_conv_taps_wgrad_workspace_bytes', cd, int(B), int(T), int(F), int(cin),
+                 int(cout), int(kf), int(kt))
+    ws = _ws(nb, x.device)
+    N.call('asr_conv_taps_wgrad', cd, N.ptr(x), N.ptr(dz), int(B), int(T), int(F), int(cin),
+           int(cout), int(kf), int(kt), N.ptr(packed), N.ptr(ws), nb, N.stream_handle(x.device))
+
+
+def conv_taps_weight_pack(w, cip, mode, cd=None):
+    """The tap image of a Conv2d weight [Co][Ci][kf][kt] in the compute dtype: mode 0
+    [Co][kf kt cip] (forward / weight gradient), mode 1 [Ci][kf kt Co] (input gradient)."""
+    cd = compute_dtype() if cd is None else cd
+    Co, Ci, kf, kt = w.shape
+    dt = torch.bfloat16 if cd == BF16 else torch.float32
+    out = (torch.empty(Co, kf * kt * cip, dtype=dt, device=w.device) if mode == 0 else
+           torch.empty(Ci, kf * kt * Co, dtype=dt, device=w.device))
+    N.call('asr_conv_taps_weight_pack', N.ptr(w), Co, Ci, int(cip), kf, kt, int(mode), cd,
+           N.ptr(out), N.stream_handle(w.device))
+    return out
+
+
+class CNNTapsFn(torch.autograd.Function):
+    """The conv stack of a CNNEncoder whose layers need kf x kt kernels
+    (kf, kt in {3, 5}) or a PReLU / hard-tanh activation (the pure-CNN CTC
+    recipe, encoders/cnn.py:61-122).  Layer l input: zero-haloed channels-last
+    [B][T_l+2][F_l+2][C_in] in the compute dtype (the single input channel of
+    layer 0 padded to 16 zero channels); convolution = asr_conv_taps_* writing
+    the f32 conv output z over its own, smaller grid; activation, pool, batch
+    norm and dropout = asr_cnn_act_*.  Output [B, T', F'*C] f32.  A shape the
+    kernels do not take raises: there is no other path."""
+
+    @staticmethod
+    def forward(ctx, xs, specs, training, p_drop, *params):
+        N.require_device(xs)
+        xs = xs.contiguous()
+        dev = xs.device
+        cd = compute_dtype()
+        B, T, F = xs.shape
+        f32 = dict(dtype=torch.float32, device=dev)
+        opdt = torch.bfloat16 if cd == BF16 else torch.float32
+        cC, cCp = 1, 16
+        x_op = torch.empty(B * (T + 2) * (F + 2), cCp, dtype=opdt, device=dev)
+        N.call('asr_vgg_pad_input_ch', N.ptr(xs), B, T, F, cCp, cd, N.ptr(x_op),
+               N.stream_handle(dev))
+        cT, cF = T, F
+        saved, layers = [], []
+        L = len(specs)
+        for l, sp in enumerate(specs):
+            w = sp['w']
+            Co = w.shape[0]
+            kf, kt = _spec_kernel(sp)
+            if N.query('asr_conv_taps_supported', cd, B, cT, cF, cCp, Co, kf, kt) != 1:
+                raise N.NativeError(
+                    'CNN layer %d (%d -> %d channels, kernel %dx%d, grid %dx%d): %s' %
+                    (l, cC, Co, kf, kt, cT, cF,
+                     N.lib().asr_last_error().decode(errors='replace')))
+            zT, zF = cT + 3 - kt, cF + 3 - kf
+            wg = conv_taps_weight_pack(w, cCp, 0)
+            # the act pass reads only z's interior: no halo to clear
+            z = torch.empty(B * (zT + 2) * (zF + 2), Co, **f32)
+            conv_taps_forward(x_op, B, cT, cF, cCp, wg, Co, kf, kt, sp['b'], z)
+            pt, pf, ceil = sp['pt'], sp['pf'], sp['ceil']
+            To, Fo = _pool_dims(zT, zF, pt, pf, ceil) if pt else (zT, zF)
+            if To < 1 or Fo < 1:
+                raise N.NativeError('CNN layer %d: pool %dx%d leaves nothing of a %dx%d grid'
+                                    % (l, pt, pf, zT, zF))
+            P = torch.empty(B * To * Fo, Co, **f32)
+            slot = torch.empty(B * To * Fo * Co, dtype=torch.uint8, device=dev) if pt else None
+            bn = sp['gamma'] is not None
+            mean = torch.empty(Co, **f32) if bn else None
+            rstd = torch.empty(Co, **f32) if bn else None
+            drop = float(p_drop) if training else 0.0
+            seed = _next_seed() if drop > 0 else 0
+            if l == L - 1:
+                out = torch.empty(B, To, Fo * Co, **f32)
+                out_dt, flat = F32, 1
+            else:
+                out = torch.empty(B * (To + 2) * (Fo + 2), Co, dtype=opdt, device=dev)
+                if _halo_only(Co, opdt):
+                    _zero_halo(out, B, To, Fo, Co)
+                else:
+                    out.zero_()
+                out_dt, flat = cd, 0
+            nb = N.query('asr_cnn_act_workspace_bytes', B, zT, zF, Co)
+            ws = _ws(nb, dev)
+            act = sp.get('act', ACT_RELU)
+            N.call('asr_cnn_act_forward', N.ptr(z), B, zT, zF, Co, act, N.ptr(sp.get('slope')),
+                   pt, pf, ceil, N.ptr(P), N.ptr(slot), N.ptr(sp['gamma']), N.ptr(sp['beta']),
+                   N.ptr(sp['run_mean']), N.ptr(sp['run_var']), int(bool(training)),
+                   float(sp['momentum']), float(sp['eps']), N.ptr(mean), N.ptr(rstd), drop, seed,
+                   N.ptr(out), out_dt, flat, N.ptr(ws), nb, N.stream_handle(dev))
+            saved += [x_op, z, P, slot, mean, rstd]
+            layers.append((cT, cF, cC, cCp, Co, kf, kt, pt, pf, ceil, drop, seed))
+            x_op, cT, cF, cC, cCp = out, To, Fo, Co, Co
+        ctx.save_for_backward(*[t if t is not None else torch.empty(0, device=dev)
+                                for t in saved])
+        ctx.layers = layers
+        ctx.specs = specs
+        ctx.B = B
+        ctx.training = bool(training)
+        ctx.cd = cd
+        return x_op
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = ctx.saved_tensors
+        specs, layers, B, cd = ctx.specs, ctx.layers, ctx.B, ctx.cd
+        dev = dout.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        opdt = torch.bfloat16 if cd == BF16 else torch.float32
+        dnext, flat = dout.contiguous(), 1
+        for l in range(len(layers) - 1, -1, -1):
+            x_op, z, P, slot, mean, rstd = saved[6 * l:6 * l + 6]
+            slot = slot if slot.numel() else None
+            mean = mean if mean.numel() else None
+            rstd = rstd if rstd.numel() else None
+            cT, cF, cC, cCp, Co, kf, kt, pt, pf, ceil, drop, seed = layers[l]
+            sp = specs[l]
+            zT, zF = cT + 3 - kt, cF + 3 - kf
+            # dz: the convolutions' operand (compute dtype); the act pass writes its
+            # whole interior
+            dz = torch.empty(B * (zT + 2) * (zF + 2), Co, dtype=opdt, device=dev)
+            if _halo_only(Co, opdt):
+                _zero_halo(dz, B, zT, zF, Co)
+            else:
+                dz.zero_()
+            bn = sp['gamma'] is not None
+            act = sp.get('act', ACT_RELU)
+            slope = sp.get('slope')
+            nb = N.query('asr_cnn_act_workspace_bytes', B, zT, zF, Co)
+            ws = _ws(nb, dev)
+            N.call('asr_cnn_act_backward', N.ptr(dnext), flat, N.ptr(z), B, zT, zF, Co, act,
+                   N.ptr(slope), pt, pf, ceil, N.ptr(P), N.ptr(slot), N.ptr(sp['gamma']),
+                   N.ptr(mean), N.ptr(rstd), int(ctx.training),
+                   N.ptr(grad_buffer(sp['gamma']) if bn else None),
+                   N.ptr(grad_buffer(sp['beta']) if bn else None), drop, seed, N.ptr(dz), cd,
+                   N.ptr(grad_buffer(sp['b']) if sp['b'] is not None else None),
+                   N.ptr(grad_buffer(slope) if slope is not None else None), N.ptr(ws), nb,
+                   N.stream_handle(dev))
+            w = sp['w']
+            packed = torch.empty(Co, kf * kt * cCp, **f32)
+            conv_taps_wgrad(x_op, dz, B, cT, cF, cCp, Co, kf, kt, packed, cd)
+            N.call('asr_conv_taps_weight_unpack_acc', N.ptr(packed), Co, cC, cCp, kf, kt,
+                   N.ptr(grad_buffer(w)), N.stream_handle(dev))
+            if l == 0:
+                break
+            wt = conv_taps_weight_pack(w, cC, 1, cd)
+            dx = torch.empty(B * (cT + 2) * (cF + 2), cC, **f32)   # interior read only
+            conv_taps_dgrad(dz, B, cT, cF, cC, wt, Co, kf, kt, dx, cd)
+            dnext, flat = dx, 0
+        return (None, None, None, None) + (None,) * len(ctx.needs_input_grad[4:])
+
+
 def vgg_front(xs, specs, training, p_drop):
     params = [t for sp in specs for t in (sp['w'], sp['b'], sp['gamma'], sp['beta'])
               if t is not None]
+    if _needs_taps(specs):
+        params += [sp['slope'] for sp in specs if sp.get('slope') is not None]
+        return CNNTapsFn.apply(xs, specs, training, p_drop, *params)
     return VGGFn.apply(xs, specs, training, p_drop, *params)
