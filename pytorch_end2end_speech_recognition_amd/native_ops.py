@@ -824,6 +824,14 @@ def linear(x, weight, bias=None, drop=None):
     return LinearFn.apply(x, weight, bias, drop)
 
 
+def _bias_pair_grad(dy2d, bias, bias2):
+    """Column sums of dy2d added to the gradient of each bias that is given
+    (one pass for the pair; a second bias without a first gets its own)."""
+    gbs = [grad_buffer(b) for b in (bias, bias2) if b is not None]
+    if gbs:
+        colsum_accumulate(dy2d, *gbs)
+
+
 class LinearExFn(torch.autograd.Function):
     """y = x @ W[:, c0:c0+K]^T + b + b2, with x rows optionally gathered from a
     3-D tensor at a fixed time index (x_src[b, t_index, :]).  Covers the
@@ -874,9 +882,7 @@ class LinearExFn(torch.autograd.Function):
             run_gemm([gemm_problem(operand(dy, 1, rowmap(Nout)), operand(x, 1, amap, offset=a_off),
                                    grad_buffer(weight), rowmap(ldw), Nout, K, M, beta=1.0,
                                    c_offset=c0)], x.device, opts=gemm_opts)
-            if bias is not None:
-                colsum_accumulate(dy.view(M, Nout), grad_buffer(bias),
-                                  grad_buffer(bias2) if bias2 is not None else None)
+            _bias_pair_grad(dy.view(M, Nout), bias, bias2)
 
         if ctx.beside is not None:
             # the weight / bias gradients beside the encoder's top backward
@@ -891,9 +897,7 @@ class LinearExFn(torch.autograd.Function):
                                   grad_buffer(weight), rowmap(ldw), Nout, K, M, beta=1.0,
                                   c_offset=c0))
         run_gemm(probs, x.device)
-        if bias is not None:
-            colsum_accumulate(dy.view(M, Nout), grad_buffer(bias),
-                              grad_buffer(bias2) if bias2 is not None else None)
+        _bias_pair_grad(dy.view(M, Nout), bias, bias2)
         return dx, None, None, None, None, None, None
 
 
@@ -973,9 +977,7 @@ class Linear2Fn(torch.autograd.Function):
                                grad_buffer(w1), rowmap(K1), Nout, K1, M, beta=1.0),
                   gemm_problem(operand(dy, 1, rowmap(Nout)), operand(x2, 1, rowmap(K2)),
                                grad_buffer(w2), rowmap(K2), Nout, K2, M, beta=1.0)], x1.device)
-        if b1 is not None:
-            colsum_accumulate(dy.view(M, Nout), grad_buffer(b1),
-                              grad_buffer(b2) if b2 is not None else None)
+        _bias_pair_grad(dy.view(M, Nout), b1, b2)
         return dx1, None, None, dx2, None, None
 
 
