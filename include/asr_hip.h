@@ -893,6 +893,31 @@ int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t
                         const float* h0, void* workspace, size_t ws_bytes, long long* tokens,
                         int32_t* hyp_lens, double* scores, float* aw, void* stream);
 
+/* Joint CTC/attention beam search: asr_att_beam_decode with every candidate's
+ * attention log-probability joined by its CTC prefix term (csrc/att_beam.hip
+ * states the semantics): score = (parent + (1 - weight) lp_att(c) + weight
+ * delta_ctc(g, c)) + length_penalty.  ctc_logits f32 [B][T][Vc]: the raw logits
+ * of the CTC head over the same frames (read in place, frames t < lens[b]
+ * only); attention class c != eos is CTC class c + label_offset, which must lie
+ * in [0, Vc) and differ from blank (else ASR_ERR_ARG).  weight in (0, 1];
+ * weight == 0 is asr_att_beam_decode itself (same launches).  Launches: 2 once,
+ * then 7 per step (6 at step 0).  The workspace is asr_att_beam_ctc_ws_bytes:
+ * that of asr_att_beam_ws_bytes plus 2 B T floats and (4 B W T + 2 B W +
+ * 2 B W W) doubles.  ASR_ERR_UNSUPPORTED as asr_att_beam_decode: the added
+ * kernels use a fixed 2 KiB of LDS and add no limit. */
+typedef struct {
+  const float* ctc_logits;
+  int Vc, blank, label_offset;
+  double weight;
+} asr_att_beam_ctc_t;
+size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
+                                 int max_len, const int32_t* lens_host);
+int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
+                            const asr_att_beam_ctc_t* ctc, const float* enc, const float* enc_a,
+                            const int32_t* lens, const float* h0, void* workspace,
+                            size_t ws_bytes, long long* tokens, int32_t* hyp_lens, double* scores,
+                            float* aw, void* stream);
+
 /* Test / diagnostics: the attention-step kernel instantiations the last
  * asr_attdec_forward_ex / _backward_ex launched: out4 = {forward conv-channel
  * template (10 or 3; 0 = generic), forward 32-frame chunks per utterance,

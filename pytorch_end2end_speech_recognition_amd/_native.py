@@ -251,6 +251,8 @@ SIGNATURES = {
     'asr_att_heads_backward': (c_int, [c_vp] + [c_vp] * 17 + [c_size, c_vp]),
     'asr_att_beam_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     'asr_att_beam_decode': (c_int, [c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
+    'asr_att_beam_ctc_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    'asr_att_beam_decode_ctc': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
@@ -337,6 +339,12 @@ class AttBeamOpts(ctypes.Structure):
         ('length_penalty', ctypes.c_double), ('ld_ih', c_ll)] + [
         (n, c_vp) for n in ('w_ih', 'w_hh', 'b_ih', 'b_hh', 'w_dec', 'w_conv', 'conv_w', 'v',
                             'w_d', 'b_d', 'w_c', 'b_c', 'w_fc', 'b_fc', 'emb_w')]
+
+
+class AttBeamCtc(ctypes.Structure):
+    """asr_att_beam_ctc_t"""
+    _fields_ = [('ctc_logits', c_vp), ('Vc', c_int), ('blank', c_int), ('label_offset', c_int),
+                ('weight', ctypes.c_double)]
 
 
 ASR_ED_TOKEN = 0

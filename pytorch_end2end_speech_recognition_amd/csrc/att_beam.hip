@@ -44,6 +44,54 @@
 //   beam_backtrack (utt) at the end: best entry, its tokens and aw rows
 // The state is double buffered by step parity and read through the parent
 // index, so no gather pass exists.
+//
+// Joint CTC/attention search (asr_att_beam_decode_ctc, weight = lambda in
+// (0, 1]; the host path of the model follows the same contract; lambda == 0 is
+// the search above, with the launches above):
+//   * label spaces: attention class c (c != <eos>) is CTC class c +
+//     label_offset (1: decode_ctc's h - 1 mapping), blank is its own class,
+//     <eos> has no CTC class.
+//   * lp_t(k): the f32 log-softmax (lg - max) - log(sum(exp(lg - max))) of the
+//     CTC head's logits [b, t], over the utterance's own frames t < L only.
+//     Everything below is double; LOGZERO = -1.0e10 stands for log 0 and
+//     logaddexp is the ordinary one on these finite values.
+//   * prefix state of a hypothesis g (its tokens after <sos>): gn_t(g), gb_t(g),
+//     t < L, the log-probability of the alignments of g over frames 0..t that
+//     end in a non-blank / in a blank.  Empty g: gn_t = LOGZERO, gb_t = the
+//     running sum of lp_tau(blank), psi = 0.
+//   * prefix score of g.c, c != <eos>: with phi_t = logaddexp(gn_t(g), gb_t(g)),
+//     or gb_t(g) alone when c == last(g), and r_n[0] = lp_0(c) if g is empty
+//     else LOGZERO:  psi(g.c) = logaddexp over {r_n[0]} and {phi_{t-1} +
+//     lp_t(c) : 1 <= t < L} -- the parent's state only, a reduction over frames.
+//   * new state of a kept row: gn_t(g.c) = logaddexp(gn_{t-1}(g.c), phi_{t-1}) +
+//     lp_t(c), gb_t(g.c) = logaddexp(gn_{t-1}(g.c), gb_{t-1}(g.c)) + lp_t(blank),
+//     gn_0 = r_n[0], gb_0 = LOGZERO.
+//   * CTC term of a candidate: delta = psi(g.c) - psi(g), or for <eos>
+//     logaddexp(gn_{L-1}(g), gb_{L-1}(g)) - psi(g); psi(g) travels with the row.
+//   * the search is the one above except for the score: the candidates are
+//     still the min(W, V) best ATTENTION classes of each row in (parent, rank)
+//     order, and score = (parent score + (1 - lambda) lp_att(c) + lambda delta)
+//     + length_penalty, in double.
+// What is stored per row is (phi_t, gb_t) = (logaddexp(gn_t, gb_t), gb_t): a
+// child needs nothing else of its parent (gn only inside phi), so the score
+// kernel does no logaddexp per frame.  Added kernels:
+//   beam_ctc_lse   (frame) once: max and log-sum of the head's logits per valid
+//                       frame.  lp_t(k) is formed from them where it is read;
+//                       the logits stay in place.  A candidate's column
+//                       lp_.(c) is strided by Vc floats, and every candidate's
+//                       column is read exactly once per step (the <= W kept
+//                       rows' once more), so gathering the <= W min(W, V)
+//                       columns first would do the same strided reads plus a
+//                       write and a re-read: columns are read in place.
+//   beam_ctc_empty (utt)   once: the empty prefix's state, a wave scan
+//   beam_ctc_advance (row) t >= 1, before beam_ctc_score: the row's (phi, gb)
+//                       from its parent's and its token; 64-frame chunks are
+//                       loaded by the wave, scanned by one lane, stored by
+//                       the wave (the only part sequential in the frames)
+//   beam_ctc_score (row)   between beam_expand and beam_select: one wave per
+//                       candidate, lanes over frames, a wave log-sum-exp:
+//                       psi(g.c) and delta of the row's min(W, V) candidates
+//   beam_select_ctc (utt)  beam_select with the joint score; hands psi on
 #include <limits.h>
 
 #include "common.h"
@@ -78,6 +126,19 @@ struct BeamP {
   int *comp_t, *comp_par;  // [B][W]: completed at step t from parent row
   int *rows;               // [B][max_len]: the best hypothesis' row per step
 };
+
+// the joint search's additions (asr_att_beam_decode_ctc)
+struct CtcP {
+  const float* lg;         // [B][T][Vc] logits of the CTC head
+  int Vc, blank, off;
+  double weight;
+  // workspace
+  float *mx, *lse;         // [B][T] per valid frame
+  double *phi, *gb;        // [2][R][T] by step parity: logaddexp(gn_t, gb_t), gb_t of the row's prefix
+  double *psi;             // [2][R]
+  double *delta, *psic;    // [R][W] per candidate: CTC term, psi(g.c)
+};
+constexpr double kLogZero = -1.0e10;
 
 __device__ __forceinline__ int utt_len(const BeamP& p, int b) {
   return max(0, min(p.lens[b], p.T));
@@ -334,7 +395,9 @@ __global__ void __launch_bounds__(EXP_THREADS) beam_expand(int t, BeamP p) {
 }
 
 // ----------------------------------------------------------------- select
-__global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
+// CTC: the joint score, and psi(g.c) of a kept candidate goes on with its row
+template <bool CTC>
+__device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q) {
   __shared__ double s_score[kMaxBeam * kMaxBeam];
   __shared__ int s_tok[kMaxBeam * kMaxBeam];
   __shared__ double s_selv[kMaxBeam];
@@ -350,7 +413,13 @@ __global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
     const int tok = p.topc[(r0 + i) * p.W + k];
     const bool drop = tok < 0 || (tok == p.eos && t + 1 < p.min_len);
     s_tok[e] = drop ? -1 : tok;
-    s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k]) + p.penalty;
+    if constexpr (CTC) {
+      const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[(r0 + i) * p.W + k];
+      s_score[e] = (p.sc[r0 + i] + (1.0 - lam) * (double)p.topv[(r0 + i) * p.W + k] + lam * d) +
+                   p.penalty;
+    } else {
+      s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k]) + p.penalty;
+    }
   }
   __syncthreads();
   // W rounds of (score descending, generation index ascending)
@@ -396,6 +465,10 @@ __global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
         p.tok_tab[tab] = tok;
         p.par_tab[tab] = i;
         p.sc[r0 + nb] = s_selv[rd];
+        if constexpr (CTC) {
+          const long long R = (long long)p.B * p.W;
+          q->psi[((t + 1) & 1) * R + r0 + nb] = q->psic[(r0 + i) * p.W + (e - i * ktop)];
+        }
         ++nb;
       }
     }
@@ -407,6 +480,172 @@ __global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
       p.n_live[b] = nb;
       p.last_t[b] = t;
       if (nb == 0) p.done[b] = 1;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) beam_select(int t, BeamP p) { select_body<false>(t, p, nullptr); }
+
+__global__ void __launch_bounds__(64) beam_select_ctc(int t, BeamP p, CtcP q) {
+  select_body<true>(t, p, &q);
+}
+
+// ------------------------------------------------------ CTC prefix scoring
+constexpr int LSE_THREADS = 256, SCORE_THREADS = 256;
+
+__device__ __forceinline__ double logaddexp_(double a, double b) {
+  return fmax(a, b) + log1p(exp(-fabs(a - b)));
+}
+
+// lp_t(k) of utterance b, t < L
+__device__ __forceinline__ double ctc_lp(const BeamP& p, const CtcP& q, int b, int t, int k) {
+  const long long f = (long long)b * p.T + t;
+  return (double)((q.lg[f * q.Vc + k] - q.mx[f]) - q.lse[f]);
+}
+
+__global__ void __launch_bounds__(LSE_THREADS) beam_ctc_lse(BeamP p, CtcP q) {
+  __shared__ float red[LSE_THREADS / 64];
+  const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= utt_len(p, b)) return;
+  const long long f = (long long)b * p.T + t;
+  const float* lg = q.lg + f * q.Vc;
+  float mx = neg_inf();
+  for (int v = threadIdx.x; v < q.Vc; v += LSE_THREADS) mx = fmaxf(mx, lg[v]);
+  mx = block_red(mx, red, true);
+  float se = 0.f;
+  for (int v = threadIdx.x; v < q.Vc; v += LSE_THREADS) se += expf(lg[v] - mx);
+  se = block_red(se, red, false);
+  if (threadIdx.x == 0) {
+    q.mx[f] = mx;
+    q.lse[f] = logf(se);
+  }
+}
+
+// the empty prefix: gb_t = sum_{tau <= t} lp_tau(blank), gn_t = LOGZERO, psi = 0 (row 0, parity 0)
+__global__ void __launch_bounds__(64) beam_ctc_empty(BeamP p, CtcP q) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int L = utt_len(p, b);
+  const long long r0 = (long long)b * p.W;
+  double carry = 0.0;
+  for (int base = 0; base < L; base += 64) {
+    const int t = base + lane;
+    double v = t < L ? ctc_lp(p, q, b, t, q.blank) : 0.0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double u = __shfl_up(v, o, 64);
+      if (lane >= o) v += u;
+    }
+    v += carry;
+    if (t < L) {
+      q.gb[r0 * p.T + t] = v;
+      q.phi[r0 * p.T + t] = logaddexp_(kLogZero, v);
+    }
+    carry = __shfl(v, 63, 64);
+  }
+  if (lane == 0) q.psi[r0] = 0.0;
+}
+
+__global__ void __launch_bounds__(64) beam_ctc_advance(int t, BeamP p, CtcP q) {
+  __shared__ double s_a[64], s_phi[64], s_gb[64];
+  __shared__ float s_lc[64], s_lb[64];
+  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int L = utt_len(p, b);
+  const long long R = (long long)p.B * p.W;
+  const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
+  const int par = p.par_tab[tab], tok = p.tok_tab[tab];
+  const int cur = t & 1, prev = cur ^ 1;
+  const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
+  // the parent's own last token: it has one from step 2 on
+  bool rep = false;
+  if (t >= 2) rep = p.tok_tab[((long long)(t - 2) * p.B + b) * p.W + par] == tok;
+  const double* pa = (rep ? q.gb : q.phi) + (prev * R + pr) * p.T;   // phi'_t of the parent
+  double* ophi = q.phi + (cur * R + r) * p.T;
+  double* ogb = q.gb + (cur * R + r) * p.T;
+  const int k = tok + q.off;
+  double gn = 0.0, gb = 0.0, ph = 0.0;   // lane 0's carry: gn_{t-1}, gb_{t-1}, their logaddexp
+  for (int base = 0; base < L; base += 64) {
+    const int f = base + lane;
+    if (f < L) {
+      const long long fr = (long long)b * p.T + f;
+      const float m = q.mx[fr], ls = q.lse[fr];
+      s_lc[lane] = (q.lg[fr * q.Vc + k] - m) - ls;
+      s_lb[lane] = (q.lg[fr * q.Vc + q.blank] - m) - ls;
+      s_a[lane] = f > 0 ? pa[f - 1] : 0.0;
+    }
+    __syncthreads();
+    if (lane == 0) {
+      const int n = min(64, L - base);
+      for (int j = 0; j < n; ++j) {
+        double ngn, ngb;
+        if (base + j == 0) {   // gn_0 = r_n[0]: lp_0(c) only if the parent is the empty prefix
+          ngn = t == 1 ? (double)s_lc[0] : kLogZero;
+          ngb = kLogZero;
+        } else {
+          ngn = logaddexp_(gn, s_a[j]) + (double)s_lc[j];
+          ngb = ph + (double)s_lb[j];   // ph = logaddexp(gn_{t-1}, gb_{t-1}), formed for the store
+        }
+        gn = ngn;
+        gb = ngb;
+        ph = logaddexp_(gn, gb);
+        s_phi[j] = ph;
+        s_gb[j] = gb;
+      }
+    }
+    __syncthreads();
+    if (f < L) {
+      ophi[f] = s_phi[lane];
+      ogb[f] = s_gb[lane];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(SCORE_THREADS) beam_ctc_score(int t, BeamP p, CtcP q) {
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = SCORE_THREADS / 64;
+  const int L = utt_len(p, b), ktop = min(p.W, p.V);
+  const long long R = (long long)p.B * p.W;
+  const long long r = (long long)b * p.W + i;
+  const int cur = t & 1;
+  const double* phi = q.phi + (cur * R + r) * p.T;
+  const double* gb = q.gb + (cur * R + r) * p.T;
+  const double psi_g = q.psi[cur * R + r];
+  const int last = t > 0 ? p.tok_tab[((long long)(t - 1) * p.B + b) * p.W + i] : -1;
+  for (int kk = w; kk < ktop; kk += nw) {   // one wave per candidate
+    const int c = p.topc[r * p.W + kk];
+    double psi_c = kLogZero, d = 0.0;
+    if (c == p.eos) {
+      d = phi[L - 1] - psi_g;
+    } else if (c >= 0) {
+      const double* pa = c == last ? gb : phi;
+      const int k = c + q.off;
+      // per lane a running (max, sum of exp(x - max)) over its frames
+      double m = -__builtin_huge_val(), s = 0.0;
+      for (int f = lane; f < L; f += 64) {
+        double x;
+        if (f == 0) x = t == 0 ? ctc_lp(p, q, b, 0, k) : kLogZero;
+        else x = pa[f - 1] + ctc_lp(p, q, b, f, k);
+        if (x > m) {
+          s = s * exp(m - x) + 1.0;
+          m = x;
+        } else {
+          s += exp(x - m);
+        }
+      }
+      double M = m;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o, 64));
+      s = s > 0.0 ? s * exp(m - M) : 0.0;   // M is finite: lane 0 holds frame 0
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      psi_c = M + log(s);
+      d = psi_c - psi_g;
+    }
+    if (lane == 0) {
+      q.delta[r * p.W + kk] = d;
+      q.psic[r * p.W + kk] = psi_c;
     }
   }
 }
@@ -501,6 +740,26 @@ BeamWs beam_ws(int B, int T, int E, int D, int W, int V, int max_len) {
   return w;
 }
 
+// the joint search's part of the workspace, laid after the plain search's
+struct CtcWs {
+  size_t mx, lse, phi, gb, psi, delta, psic, total;
+};
+
+CtcWs ctc_ws(size_t base, int B, int T, int W) {
+  CtcWs w;
+  const size_t R = (size_t)B * W;
+  size_t o = base;
+  w.mx = o; o += al256((size_t)B * T * 4);
+  w.lse = o; o += al256((size_t)B * T * 4);
+  w.phi = o; o += al256(2 * R * T * 8);
+  w.gb = o; o += al256(2 * R * T * 8);
+  w.psi = o; o += al256(2 * R * 8);
+  w.delta = o; o += al256(R * W * 8);
+  w.psic = o; o += al256(R * W * 8);
+  w.total = o;
+  return w;
+}
+
 // ASR_OK, or the refusal with its reason in the error text
 int beam_check(const asr_attdec_dims_t& d, int W, int V, int Y, int Dz, int max_len) {
   ASR_REQUIRE(d.B > 0 && d.T > 0 && d.E > 0 && d.A > 0 && d.C > 0 && d.K > 0 && d.D > 0 && V >= 2 &&
@@ -532,11 +791,18 @@ extern "C" size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, in
   return beam_ws(dims->B, dims->T, dims->E, dims->D, W, V, max_len).total;
 }
 
-extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                                   const float* enc, const float* enc_a, const int32_t* lens,
-                                   const float* h0, void* workspace, size_t ws_bytes,
-                                   long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
-                                   void* stream) {
+extern "C" size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y,
+                                            int Dz, int max_len, const int32_t* lens_host) {
+  const size_t base = asr_att_beam_ws_bytes(dims, W, V, Y, Dz, max_len, lens_host);
+  return base ? ctc_ws(base, dims->B, dims->T, W).total : 0;
+}
+
+// ctc == nullptr: the attention-only search, its launches unchanged
+static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                            const asr_att_beam_ctc_t* ctc, const float* enc, const float* enc_a,
+                            const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
+                            long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
+                            void* stream) {
   ASR_REQUIRE(dims && o, ASR_ERR_ARG, "att_beam_decode: dims / opts is null");
   const int rc = beam_check(*dims, o->W, o->V, o->Y, o->Dz, o->max_len);
   if (rc) return rc;
@@ -550,8 +816,22 @@ extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_
               "att_beam_decode: ld_ih = %lld < Y + E", o->ld_ih);
   ASR_REQUIRE(o->max_len > 0, ASR_ERR_ARG, "att_beam_decode: max_len = %d", o->max_len);
   const BeamWs w = beam_ws(dims->B, dims->T, dims->E, dims->D, o->W, o->V, o->max_len);
-  ASR_REQUIRE(ws_bytes >= w.total, ASR_ERR_WORKSPACE, "att_beam_decode: workspace %zu < %zu bytes",
-              ws_bytes, w.total);
+  const CtcWs cw = ctc_ws(w.total, dims->B, dims->T, o->W);
+  if (ctc) {
+    ASR_REQUIRE(ctc->ctc_logits, ASR_ERR_ARG, "att_beam_decode_ctc: ctc_logits is null");
+    ASR_REQUIRE(ctc->weight > 0.0 && ctc->weight <= 1.0, ASR_ERR_ARG,
+                "att_beam_decode_ctc: weight = %g outside (0, 1]", ctc->weight);
+    // every class but <eos> maps into [0, Vc) and not onto blank
+    const int hi = (o->eos == o->V - 1 ? o->V - 2 : o->V - 1) + ctc->label_offset;
+    const int bl = ctc->blank - ctc->label_offset;   // the attention class that would hit blank
+    ASR_REQUIRE(ctc->Vc >= 2 && ctc->label_offset >= 0 && hi < ctc->Vc && ctc->blank >= 0 &&
+                    ctc->blank < ctc->Vc && (bl < 0 || bl >= o->V || bl == o->eos),
+                ASR_ERR_ARG, "att_beam_decode_ctc: Vc = %d, blank = %d, label_offset = %d do not "
+                "fit V = %d, eos = %d", ctc->Vc, ctc->blank, ctc->label_offset, o->V, o->eos);
+  }
+  const size_t need = ctc ? cw.total : w.total;
+  ASR_REQUIRE(ws_bytes >= need, ASR_ERR_WORKSPACE, "att_beam_decode: workspace %zu < %zu bytes",
+              ws_bytes, need);
   ASR_REQUIRE(((uintptr_t)workspace & 255) == 0, ASR_ERR_ARG,
               "att_beam_decode: workspace not 256-B aligned");
   char* base = (char*)workspace;
@@ -579,8 +859,23 @@ extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_
   const size_t lds_att = attend_lds_floats(p.D, p.A, p.C, p.K, p.T) * 4;
   const size_t lds_exp = ((size_t)p.D + p.E + p.Dz + 8) * 4;
   const dim3 rows(p.W, p.B);
+  CtcP q = {};
+  if (ctc) {
+    q.lg = ctc->ctc_logits; q.Vc = ctc->Vc; q.blank = ctc->blank; q.off = ctc->label_offset;
+    q.weight = ctc->weight;
+    q.mx = (float*)(base + cw.mx); q.lse = (float*)(base + cw.lse);
+    q.phi = (double*)(base + cw.phi); q.gb = (double*)(base + cw.gb);
+    q.psi = (double*)(base + cw.psi); q.delta = (double*)(base + cw.delta);
+    q.psic = (double*)(base + cw.psic);
+  }
   hipLaunchKernelGGL(beam_init, dim3(p.B), dim3(256), 0, s, p);
   ASR_LAUNCH_CHECK();
+  if (ctc) {
+    hipLaunchKernelGGL(beam_ctc_lse, dim3(p.T, p.B), dim3(LSE_THREADS), 0, s, p, q);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_ctc_empty, dim3(p.B), dim3(64), 0, s, p, q);
+    ASR_LAUNCH_CHECK();
+  }
   for (int t = 0; t < p.max_len; ++t) {
     if (t > 0) {
       hipLaunchKernelGGL(beam_cell, rows, dim3(CELL_THREADS), lds_cell, s, t, p);
@@ -590,11 +885,42 @@ extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_
     ASR_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_expand, rows, dim3(EXP_THREADS), lds_exp, s, t, p);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_select, dim3(p.B), dim3(64), 0, s, t, p);
-    ASR_LAUNCH_CHECK();
+    if (ctc) {
+      if (t > 0) {
+        hipLaunchKernelGGL(beam_ctc_advance, rows, dim3(64), 0, s, t, p, q);
+        ASR_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL(beam_ctc_score, rows, dim3(SCORE_THREADS), 0, s, t, p, q);
+      ASR_LAUNCH_CHECK();
+      hipLaunchKernelGGL(beam_select_ctc, dim3(p.B), dim3(64), 0, s, t, p, q);
+      ASR_LAUNCH_CHECK();
+    } else {
+      hipLaunchKernelGGL(beam_select, dim3(p.B), dim3(64), 0, s, t, p);
+      ASR_LAUNCH_CHECK();
+    }
   }
   hipLaunchKernelGGL(beam_backtrack, dim3(p.B), dim3(BT_THREADS), 0, s, p, tokens, hyp_lens,
                      scores, aw);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
+}
+
+extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                   const float* enc, const float* enc_a, const int32_t* lens,
+                                   const float* h0, void* workspace, size_t ws_bytes,
+                                   long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
+                                   void* stream) {
+  return beam_decode_impl(dims, o, nullptr, enc, enc_a, lens, h0, workspace, ws_bytes, tokens,
+                          hyp_lens, scores, aw, stream);
+}
+
+extern "C" int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                       const asr_att_beam_ctc_t* ctc, const float* enc,
+                                       const float* enc_a, const int32_t* lens, const float* h0,
+                                       void* workspace, size_t ws_bytes, long long* tokens,
+                                       int32_t* hyp_lens, double* scores, float* aw, void* stream) {
+  ASR_REQUIRE(ctc, ASR_ERR_ARG, "att_beam_decode_ctc: ctc is null");
+  // weight 0 is the attention-only search itself
+  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, enc, enc_a, lens, h0,
+                          workspace, ws_bytes, tokens, hyp_lens, scores, aw, stream);
 }

@@ -29,6 +29,7 @@ from ..linear import LinearND, Embedding, Embedding_LS
 from ..encoders.load_encoder import load
 from .rnn_decoder import RNNDecoder
 from .attention_layer import AttentionMechanism
+from .ctc_prefix_score import CtcPrefixScorer, log_softmax_f32
 from ..ctc.ctc import _concatenate_labels_np
 from ..ctc.decoders.greedy_decoder import GreedyDecoder
 
@@ -512,22 +513,54 @@ class AttentionSeq2seq(ModelBase):
     @eval_retry
     @torch.no_grad()
     def decode(self, xs, x_lens, beam_width, max_decode_len, min_decode_len=0,
-               length_penalty=0, coverage_penalty=0, task_index=0, resolving_unk=False):
+               length_penalty=0, coverage_penalty=0, task_index=0, resolving_unk=False,
+               ctc_weight=0):
         """:866-915.  Returns (best_hyps int64 [B, T_out], aw [B, T_out, T_in],
-        perm_idx), rows in the encoder's length-sorted order like the reference."""
+        perm_idx), rows in the encoder's length-sorted order like the reference.
+        ctc_weight in (0, 1]: one-pass joint CTC/attention beam search, every
+        candidate's score (1 - ctc_weight) * attention + ctc_weight * CTC prefix
+        term of fc_ctc_0 (csrc/att_beam.hip states the semantics); 0: the
+        attention decoder alone."""
+        dir = 'fwd' if self.fwd_weight_0 >= self.bwd_weight_0 else 'bwd'   # :893
+        self._check_ctc_weight(ctc_weight, beam_width, 0, dir)
         self.eval()
         xs_d = self.np2var(xs, dtype='float')
         enc_out, enc_lens_d, _ = self._encode(xs_d, x_lens)
-        dir = 'fwd' if self.fwd_weight_0 >= self.bwd_weight_0 else 'bwd'   # :893
         if beam_width == 1:
             best_hyps, aw = self._decode_infer_greedy(enc_out, enc_lens_d, max_decode_len,
                                                       dir=dir)
         else:
             best_hyps, aw = self._decode_infer_beam(enc_out, self.encoder.last_lens_np, beam_width,
                                                     max_decode_len, min_decode_len,
-                                                    length_penalty, coverage_penalty, dir=dir)
+                                                    length_penalty, coverage_penalty, dir=dir,
+                                                    ctc_weight=ctc_weight)
         check_recurrences(self)
         return best_hyps, aw, self.encoder.last_perm_np.copy()
+
+    def _check_ctc_weight(self, ctc_weight, beam_width, task, dir):
+        """The joint decode's preconditions, checked before the encoder runs."""
+        if not 0 <= ctc_weight <= 1:
+            raise ValueError('ctc_weight = %r outside [0, 1]' % (ctc_weight,))
+        if ctc_weight == 0:
+            return
+        if dir != 'fwd':
+            raise NotImplementedError('ctc_weight > 0 with the backward decoder: its hypotheses '
+                                      'are reversed, the CTC prefix score reads left to right')
+        if getattr(self, 'fc_ctc_%d' % task, None) is None:
+            raise ValueError('ctc_weight > 0 needs the CTC head fc_ctc_%d (a model built with a '
+                             'CTC loss weight > 0 for task %d)' % (task, task))
+        if beam_width <= 1:
+            raise ValueError('ctc_weight > 0 needs beam_width > 1: the CTC prefix term rescores '
+                             'a beam')
+
+    def _ctc_logits_f32(self, enc_out, task):
+        """fc_ctc_<task>'s logits with the GEMM forced to f32, as W_enc's is for the search."""
+        bf16 = ops.compute_dtype() == ops.BF16
+        ops.set_compute_dtype('fp32')
+        try:
+            return getattr(self, 'fc_ctc_%d' % task)(enc_out)
+        finally:
+            ops.set_compute_dtype('bf16' if bf16 else 'fp32')
 
     # error_rate() sets a list here for the length of one decode(): the device
     # decode paths append their (tokens, lengths) device tensors to it and
@@ -617,32 +650,36 @@ class AttentionSeq2seq(ModelBase):
 
     def _decode_infer_beam(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
                            length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
-                           _scores=None):
+                           _scores=None, ctc_weight=0):
         """:1038-1237.  Decoders the fused pass covers (_fused_ok) search on the
         device (native_ops.att_decode_beam, csrc/att_beam.hip: no host read
         inside the step loop); the others, a shape the kernels refuse, and
         ASR_ATT_BEAM=host run _decode_infer_beam_host.  Same results either
         way; native_ops.last_att_beam_path() says which ran.  _gaps: a list
         that receives the host path's decision margins (filled by that path
-        only); _scores: a list that receives each best hypothesis' score."""
+        only); _scores: a list that receives each best hypothesis' score.
+        ctc_weight > 0: the joint CTC/attention search on fc_ctc_<task>'s
+        logits, on the same two paths (margins and scores are then those of
+        the joint score)."""
         if coverage_penalty > 0:
             raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
+        self._check_ctc_weight(ctc_weight, beam_width, task, dir)
         if (self._fused_ok(task, dir) and max_decode_len >= 1
                 and os.environ.get('ASR_ATT_BEAM', 'device') != 'host'):
             out = self._decode_infer_beam_device(enc_out, x_lens, beam_width, max_decode_len,
                                                  min_decode_len, length_penalty, task, dir,
-                                                 _scores)
+                                                 _scores, ctc_weight)
             if out is not None:
                 ops._set_att_beam_path('device')
                 return out
         ops._set_att_beam_path('host')
         return self._decode_infer_beam_host(enc_out, x_lens, beam_width, max_decode_len,
                                             min_decode_len, length_penalty, coverage_penalty,
-                                            task, dir, _gaps, _scores)
+                                            task, dir, _gaps, _scores, ctc_weight)
 
     def _decode_infer_beam_device(self, enc_out, x_lens, beam_width, max_decode_len,
                                   min_decode_len, length_penalty, task=0, dir='fwd',
-                                  _scores=None):
+                                  _scores=None, ctc_weight=0):
         """The whole search as one op; None when the kernels refuse the shape.
         One device-to-host copy of the compact results at the end."""
         att = getattr(self, 'attend_%d_%s' % (task, dir))
@@ -663,12 +700,15 @@ class AttentionSeq2seq(ModelBase):
         gen = dict(w_d=W_d.fc.weight, b_d=W_d.fc.bias, w_c=W_c.fc.weight, b_c=W_c.fc.bias,
                    w_fc=fc.fc.weight, b_fc=fc.fc.bias, emb_w=emb_w,
                    emb_trans=int(emb_ls), b_ih=cell.bias_ih, b_hh=cell.bias_hh)
+        joint = {}
+        if ctc_weight > 0:
+            joint = dict(ctc_logits=self._ctc_logits_f32(enc_out, task), ctc_weight=ctc_weight)
         out = ops.att_decode_beam(enc_out, enc_a, lens.astype(np.int32), h0, self._emb_dims[task],
                                   self.sharpening_factor, self.sigmoid_smoothing,
                                   cell.weight_ih, cell.weight_hh, att.W_dec_head0.fc.weight,
                                   *att.conv_weights(), att.V_head0.fc.weight, gen, beam_width,
                                   max_decode_len, min_decode_len, length_penalty,
-                                  getattr(self, 'eos_%d' % task))
+                                  getattr(self, 'eos_%d' % task), **joint)
         if out is None:
             return None
         if self._hyp_capture is not None and dir == 'fwd':
@@ -687,7 +727,7 @@ class AttentionSeq2seq(ModelBase):
 
     def _decode_infer_beam_host(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
                                 length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
-                                _scores=None):
+                                _scores=None, ctc_weight=0):
         """:1038-1237 (any decoding order / decoder depth).  Utterance by utterance like the
         reference, each over its own frames (enc_out[b, :x_len]); the live
         hypotheses of an utterance advance as ONE batch per step on the HIP ops
@@ -698,9 +738,18 @@ class AttentionSeq2seq(ModelBase):
         reference does with its per-step reads.  Returns (best_hyps: an int64
         [B, L] array when every hypothesis has the same length, else an object
         array of int64 rows, each ending with <eos> when it completed; aw: list
-        of [L_b, x_len_b] float32 arrays)."""
+        of [L_b, x_len_b] float32 arrays).  ctc_weight > 0: the candidates'
+        scores are joint, (1 - ctc_weight) * log-prob + ctc_weight * CTC prefix
+        term (ctc_prefix_score.CtcPrefixScorer, numpy doubles on the f32
+        log-softmax of fc_ctc_<task>); every hypothesis carries its prefix
+        state."""
         if coverage_penalty > 0:
             raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
+        self._check_ctc_weight(ctc_weight, beam_width, task, dir)
+        lam = float(ctc_weight)
+        ctc_lp = None
+        if lam > 0:
+            ctc_lp = log_softmax_f32(self._ctc_logits_f32(enc_out, task).float().cpu().numpy())
         att = getattr(self, 'attend_%d_%s' % (task, dir))
         embed = getattr(self, 'embed_%d' % task)
         sos, eos = getattr(self, 'sos_%d' % task), getattr(self, 'eos_%d' % task)
@@ -730,6 +779,9 @@ class AttentionSeq2seq(ModelBase):
                          dec=init['dec'][b:b + 1], ctx=init['ctx'][b:b + 1],
                          aw=init['aw'][b:b + 1, :L])
             beam = [dict(hyp=[sos], score=0.0, row=0, hist=[])]
+            if lam > 0:
+                scorer = CtcPrefixScorer(ctc_lp[b, :L])
+                beam[0]['ctc'] = scorer.empty()
             complete, step_aw = [], []
             gap = float('inf')
             for t in range(max_decode_len):
@@ -768,6 +820,15 @@ class AttentionSeq2seq(ModelBase):
                         tok = int(order[i, k])
                         if tok == eos and len(beam[i]['hyp']) < min_decode_len:
                             continue
+                        if lam > 0:
+                            st, g = beam[i]['ctc'], beam[i]['hyp'][1:]
+                            psi = None if tok == eos else scorer.psi(st, g, tok)
+                            delta = (scorer.eos(st) if tok == eos else psi) - st['psi']
+                            new.append(dict(hyp=beam[i]['hyp'] + [tok],
+                                            score=beam[i]['score'] + (1.0 - lam) * float(lp[i, tok])
+                                            + lam * delta + length_penalty,
+                                            row=i, hist=beam[i]['hist'] + [(t, i)], psi=psi))
+                            continue
                         new.append(dict(hyp=beam[i]['hyp'] + [tok],
                                         score=beam[i]['score'] + float(lp[i, tok]) + length_penalty,
                                         row=i, hist=beam[i]['hist'] + [(t, i)]))
@@ -790,6 +851,11 @@ class AttentionSeq2seq(ModelBase):
                 if len(complete) >= beam_width:
                     complete = complete[:beam_width]
                     break
+                if lam > 0:                     # the kept rows' prefix states, from their parents'
+                    for cand in not_complete[:beam_width]:
+                        par = beam[cand['row']]
+                        cand['ctc'] = scorer.advance(par['ctc'], par['hyp'][1:], cand['hyp'][-1],
+                                                     cand['psi'])
                 beam = not_complete[:beam_width]
             if len(complete) == 0:
                 complete = beam

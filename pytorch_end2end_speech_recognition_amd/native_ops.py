@@ -1075,11 +1075,15 @@ def _set_att_beam_path(path):
 
 @torch.no_grad()
 def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh, w_dec, w_conv,
-                    conv_w, v, gen, beam_width, max_len, min_len, length_penalty, eos):
+                    conv_w, v, gen, beam_width, max_len, min_len, length_penalty, eos,
+                    ctc_logits=None, ctc_weight=0):
     """Attention beam search on the device (asr_att_beam_decode, csrc/att_beam.hip;
     attention_seq2seq.py:1038-1237, bahdanau order): every utterance over its
     own lens[b] frames, f32 in both compute modes, no host read inside the
-    step loop.  gen as att_decode_greedy.  Returns (tokens int64 [B, max_len],
+    step loop.  gen as att_decode_greedy.  ctc_weight > 0: the joint
+    CTC/attention search (asr_att_beam_decode_ctc) on ctc_logits [B, T, Vc],
+    the raw f32 logits of the CTC head (blank 0, attention class c is CTC class
+    c + 1); ctc_weight == 0 is the plain search.  Returns (tokens int64 [B, max_len],
     lengths int32 [B], scores float64 [B], aw float32 [B, max_len, T]) on the
     device, or None when the kernels do not cover the shape
     (ASR_ERR_UNSUPPORTED; the reason is asr_last_error's)."""
@@ -1097,8 +1101,19 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     else:
         lens_d = h2d(np.asarray(lens, np.int32).reshape(-1), dev)
     W, max_len = int(beam_width), int(max_len)
-    nb = N.query('asr_att_beam_ws_bytes', ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz),
-                 max_len, None)
+    lam = float(ctc_weight)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError('att_decode_beam: ctc_weight = %r outside [0, 1]' % (ctc_weight,))
+    if lam > 0:
+        if ctc_logits is None:
+            raise ValueError('att_decode_beam: ctc_weight > 0 needs ctc_logits')
+        ctc_logits = ctc_logits.contiguous().float()
+        if ctc_logits.dim() != 3 or tuple(ctc_logits.shape[:2]) != (B, T):
+            raise ValueError('att_decode_beam: ctc_logits %s is not [%d, %d, Vc]'
+                             % (tuple(ctc_logits.shape), B, T))
+        N.require_device(ctc_logits)
+    nb = N.query('asr_att_beam_ctc_ws_bytes' if lam > 0 else 'asr_att_beam_ws_bytes',
+                 ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz), max_len, None)
     if nb == 0:
         return None
     ws = _att_beam['ws'].get(dev)
@@ -1118,15 +1133,20 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     scores = torch.empty(B, dtype=torch.float64, device=dev)
     aw = torch.empty(B, max_len, T, dtype=torch.float32, device=dev)
     h0c = h0.contiguous().float() if h0 is not None else None
-    rc = getattr(N.lib(), 'asr_att_beam_decode')(
-        ctypes.byref(dims), ctypes.byref(opts), N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d),
-        N.ptr(h0c), N.ptr(ws), ws.numel(), N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw),
-        N.stream_handle(dev))
+    tail = (N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d), N.ptr(h0c), N.ptr(ws), ws.numel(),
+            N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw), N.stream_handle(dev))
+    if lam > 0:
+        fn = 'asr_att_beam_decode_ctc'
+        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam)
+        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ctc), *tail)
+    else:
+        fn = 'asr_att_beam_decode'
+        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), *tail)
     if rc == N.ASR_ERR_UNSUPPORTED:
         return None
     if rc != N.ASR_OK:
-        raise N.NativeError('asr_att_beam_decode failed (rc=%d): %s'
-                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
+        raise N.NativeError('%s failed (rc=%d): %s'
+                            % (fn, rc, N.lib().asr_last_error().decode(errors='replace')))
     return tokens, hl, scores, aw
 
 

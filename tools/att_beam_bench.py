@@ -8,8 +8,10 @@ Shapes: B 32, 250 padded frames (lengths 150 .. 250), max_decode_len 100,
 encoder width 640, decoder 320, attention 128, bottleneck 256, embedding 64,
 10 x 201 location convolution; (W 4, V 29), (W 10, V 29), (W 10, V 10001).
 Random weights with the <eos> logit pushed down, so every search runs its 100
-steps on both paths.  One process; per shape and path: warm-up calls, then
-wall time around each call with a device synchronisation on both sides (the
+steps on both paths.  --ctc-weight L > 0: the joint CTC/attention search
+(decode(..., ctc_weight=L)) on a model with a CTC head; 0 (the default): the
+attention-only search on the model without one.  One process; per shape
+and path: warm-up calls, then wall time around each call with a device synchronisation on both sides (the
 host path synchronises by itself at every step), median (min .. max).
 
 Writes profiles/att_beam_bench.txt (or --out).
@@ -46,6 +48,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--host_repeats', type=int, default=3)
     ap.add_argument('--max_decode_len', type=int, default=100)
+    ap.add_argument('--ctc-weight', type=float, default=0.0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('att_beam_bench: needs an MI355X; a CPU run gives no time')
@@ -63,8 +66,10 @@ def main():
     enc = torch.from_numpy(enc_np).cuda()
     lines = ['# attention beam search, device path beside host path, MI355X; B %d, T %d (lengths '
              '%d .. %d), max_decode_len %d; wall ms per call, median (min .. max) of %d device / '
-             '%d host calls after %d warm-up' % (B, T, lens.min(), lens.max(), S, args.repeats,
-                                                 args.host_repeats, args.warmup)]
+             '%d host calls after %d warm-up; ctc_weight %g'
+             % (B, T, lens.min(), lens.max(), S, args.repeats, args.host_repeats, args.warmup,
+                args.ctc_weight)]
+    joint = dict(ctc_loss_weight=0.2) if args.ctc_weight > 0 else {}
     for W, V in ((4, 29), (10, 29), (10, 10001)):
         torch.manual_seed(V + W)
         model = AttentionSeq2seq(
@@ -73,7 +78,7 @@ def main():
             attention_dim=128, decoder_type='lstm', decoder_num_units=320, decoder_num_layers=1,
             embedding_dim=64, dropout_input=0, dropout_encoder=0, dropout_decoder=0,
             dropout_embedding=0, num_classes=V - 1, subsample_list=[False],
-            init_dec_state='first', bottleneck_dim=256)
+            init_dec_state='first', bottleneck_dim=256, **joint)
         with torch.no_grad():
             model.fc_0_fwd.fc.bias[V - 1] -= 30.0
         model.set_cuda()
@@ -82,7 +87,8 @@ def main():
         def run(mode):
             os.environ['ASR_ATT_BEAM'] = mode
             with torch.no_grad():
-                out = model._decode_infer_beam(enc, lens, W, S, 0, 0, 0)
+                out = model._decode_infer_beam(enc, lens, W, S, 0, 0, 0,
+                                               ctc_weight=args.ctc_weight)
             assert ops.last_att_beam_path() == mode
             return out
 
