@@ -843,8 +843,9 @@ int asr_att_heads_backward(const asr_att_heads_t* p, const float* enc, const flo
 
 /* Attention beam search on the device (AttentionSeq2seq._decode_infer_beam,
  * attention_seq2seq.py:1038-1237; csrc/att_beam.hip states the semantics) for
- * bahdanau order, a one-layer LSTMCell decoder without residual, location or
- * content attention.  f32 arithmetic whatever the compute mode.  dims as above
+ * bahdanau order, a one-layer LSTMCell decoder without residual (a GRUCell one:
+ * asr_att_beam_decode_ex below), location or content attention.  f32
+ * arithmetic whatever the compute mode.  dims as above
  * (T = the padded frame count, S ignored); every utterance decodes over its
  * own lens[b] frames (clipped to [0, T]; 0 frames: empty hypothesis).
  * opts: W beam width, V classes, Y embedding width, Dz bottleneck width,
@@ -917,6 +918,30 @@ int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_op
                             const int32_t* lens, const float* h0, void* workspace,
                             size_t ws_bytes, long long* tokens, int32_t* hyp_lens, double* scores,
                             float* aw, void* stream);
+
+/* The search with the decoder's cell type chosen: the two entry points above
+ * are cell == ASR_ATT_BEAM_CELL_LSTM (ctc null: asr_att_beam_decode; non-null:
+ * asr_att_beam_decode_ctc, weight 0 again the attention-only search), with
+ * exactly their launches.  ASR_ATT_BEAM_CELL_GRU: a one-layer GRUCell decoder
+ * (torch's gate rows r, z, n; r scales the hidden part of n, bias included);
+ * opts' w_ih [3D][ld_ih], w_hh [3D][D], b_ih / b_hh [3D] then hold the 3-gate
+ * tensors.  Only the cell kernel differs (beam_cell_gru for beam_cell): the
+ * launch counts, the limits (the cell's LDS need is the same Y + E + D floats)
+ * and the outputs' layout are those above.  The workspace is sized by the same
+ * asr_att_beam_ws_bytes / asr_att_beam_ctc_ws_bytes: the GRU search needs no
+ * more than the LSTM one (it leaves the c rows unused).  Any other cell is
+ * ASR_ERR_ARG, before any launch. */
+#define ASR_ATT_BEAM_CELL_LSTM 0
+#define ASR_ATT_BEAM_CELL_GRU 1
+typedef struct {
+  int cell;
+  const asr_att_beam_ctc_t* ctc; /* nullable */
+} asr_att_beam_ex_t;
+int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
+                           const asr_att_beam_ex_t* ex, const float* enc, const float* enc_a,
+                           const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
+                           long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
+                           void* stream);
 
 /* Test / diagnostics: the attention-step kernel instantiations the last
  * asr_attdec_forward_ex / _backward_ex launched: out4 = {forward conv-channel

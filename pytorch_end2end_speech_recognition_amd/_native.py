@@ -253,6 +253,7 @@ SIGNATURES = {
     'asr_att_beam_decode': (c_int, [c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_att_beam_ctc_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     'asr_att_beam_decode_ctc': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
+    'asr_att_beam_decode_ex': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
@@ -345,6 +346,15 @@ class AttBeamCtc(ctypes.Structure):
     """asr_att_beam_ctc_t"""
     _fields_ = [('ctc_logits', c_vp), ('Vc', c_int), ('blank', c_int), ('label_offset', c_int),
                 ('weight', ctypes.c_double)]
+
+
+ATT_BEAM_CELL_LSTM = 0
+ATT_BEAM_CELL_GRU = 1
+
+
+class AttBeamEx(ctypes.Structure):
+    """asr_att_beam_ex_t"""
+    _fields_ = [('cell', c_int), ('ctc', c_vp)]
 
 
 ASR_ED_TOKEN = 0

@@ -1,9 +1,10 @@
 // Attention beam search on gfx950 (AttentionSeq2seq._decode_infer_beam,
-// attention_seq2seq.py:1038-1237 of the reference) for the decoders the fused
-// pass covers: bahdanau order, one LSTMCell layer, no residual, location or
-// content attention.  f32 arithmetic in both compute modes: a beam of at most
-// W rows needs no MFMA throughput, and a bf16 near-tie flip changes whole
-// hypotheses.
+// attention_seq2seq.py:1038-1237 of the reference) for bahdanau order, one
+// decoder layer without residual -- an LSTMCell (the decoders the fused pass
+// covers) or a GRUCell (asr_att_beam_decode_ex; the TIMIT attention recipes) --
+// and one head of location or content attention.  f32 arithmetic in both
+// compute modes: a beam of at most W rows needs no MFMA throughput, and a bf16
+// near-tie flip changes whole hypotheses.
 //
 // Semantics (those of the host path, which the recorded fixtures pin):
 //   * each utterance decodes over its own frames: T = lens[b], enc[b, :L].
@@ -33,6 +34,10 @@
 // work-group reads its utterance's done word first and leaves uniformly):
 //   beam_cell    (row)  t >= 1: embedding of the row's token, LSTMCell on
 //                       [e; ctx; h] of the parent row -> h, c
+//   beam_cell_gru (row) in beam_cell's place for a GRU decoder: GRUCell (gate
+//                       rows r, z, n) on the same [e; ctx; h] -> h; c is unused.
+//                       Only the cell kernel knows the cell type: every kernel
+//                       below, the joint search's included, is shared
 //   beam_attend  (row)  W_dec h, conv(aw of the parent row), energies,
 //                       sharpening, softmax / sigmoid over L, context; aw goes
 //                       to the per-step record [step][row][T]
@@ -208,6 +213,47 @@ __global__ void __launch_bounds__(CELL_THREADS) beam_cell(int t, BeamP p) {
       const float cn = fg * p.c[(prev * R + pr) * p.D + u] + ig * gg;
       p.c[(cur * R + r) * p.D + u] = cn;
       p.h[(cur * R + r) * p.D + u] = og * tanhf_(cn);
+    }
+  }
+}
+
+// GRUCell (gate rows r, z, n): the same row, tables and LDS staging as
+// beam_cell.  r scales the hidden part of the n gate only, its bias included,
+// so that gate's two parts are summed apart.  No c state.
+__global__ void __launch_bounds__(CELL_THREADS) beam_cell_gru(int t, BeamP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = CELL_THREADS / 64;
+  const long long R = (long long)p.B * p.W;
+  const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
+  const int par = p.par_tab[tab], tok = p.tok_tab[tab];
+  const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
+  const int cur = t & 1, prev = cur ^ 1;
+  const int YE = p.Y + p.E;
+  float* x = sm;   // [Y + E + D] = [e; ctx; h] of the parent row
+  for (int y = tid; y < p.Y; y += CELL_THREADS)
+    x[y] = p.emb_trans ? p.emb_w[(long long)y * p.V + tok] : p.emb_w[(long long)tok * p.Y + y];
+  for (int e = tid; e < p.E; e += CELL_THREADS) x[p.Y + e] = p.ctx[(prev * R + pr) * p.E + e];
+  for (int j = tid; j < p.D; j += CELL_THREADS) x[YE + j] = p.h[(prev * R + pr) * p.D + j];
+  __syncthreads();
+  for (int u = w; u < p.D; u += nw) {   // one wave per hidden unit, lanes over K
+    float si[3], sh[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+      const long long row = (long long)g * p.D + u;
+      const float* wi = p.w_ih + row * p.ld_ih;
+      const float* wh = p.w_hh + row * p.D;
+      float a = 0.f, c = 0.f;
+      for (int k = lane; k < YE; k += 64) a += wi[k] * x[k];
+      for (int k = lane; k < p.D; k += 64) c += wh[k] * x[YE + k];
+      si[g] = wave_sum(a) + p.b_ih[row];
+      sh[g] = wave_sum(c) + p.b_hh[row];
+    }
+    if (lane == 0) {
+      const float rg = sigmoidf_(si[0] + sh[0]), zg = sigmoidf_(si[1] + sh[1]);
+      const float ng = tanhf_(si[2] + rg * sh[2]);
+      p.h[(cur * R + r) * p.D + u] = (1.f - zg) * ng + zg * x[YE + u];
     }
   }
 }
@@ -797,13 +843,17 @@ extern "C" size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W
   return base ? ctc_ws(base, dims->B, dims->T, W).total : 0;
 }
 
-// ctc == nullptr: the attention-only search, its launches unchanged
+// ctc == nullptr: the attention-only search, its launches unchanged; cell: which
+// cell kernel steps the rows (ASR_ATT_BEAM_CELL_*), the only difference it makes
 static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                            const asr_att_beam_ctc_t* ctc, const float* enc, const float* enc_a,
+                            const asr_att_beam_ctc_t* ctc, int cell, const float* enc,
+                            const float* enc_a,
                             const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
                             long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
                             void* stream) {
   ASR_REQUIRE(dims && o, ASR_ERR_ARG, "att_beam_decode: dims / opts is null");
+  ASR_REQUIRE(cell == ASR_ATT_BEAM_CELL_LSTM || cell == ASR_ATT_BEAM_CELL_GRU, ASR_ERR_ARG,
+              "att_beam_decode: unknown cell %d", cell);
   const int rc = beam_check(*dims, o->W, o->V, o->Y, o->Dz, o->max_len);
   if (rc) return rc;
   ASR_REQUIRE(enc && enc_a && lens && workspace && tokens && hyp_lens && scores && aw &&
@@ -878,7 +928,10 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
   }
   for (int t = 0; t < p.max_len; ++t) {
     if (t > 0) {
-      hipLaunchKernelGGL(beam_cell, rows, dim3(CELL_THREADS), lds_cell, s, t, p);
+      if (cell == ASR_ATT_BEAM_CELL_GRU)
+        hipLaunchKernelGGL(beam_cell_gru, rows, dim3(CELL_THREADS), lds_cell, s, t, p);
+      else
+        hipLaunchKernelGGL(beam_cell, rows, dim3(CELL_THREADS), lds_cell, s, t, p);
       ASR_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(beam_attend, rows, dim3(ATT_THREADS), lds_att, s, t, p);
@@ -910,8 +963,8 @@ extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_
                                    const float* h0, void* workspace, size_t ws_bytes,
                                    long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
                                    void* stream) {
-  return beam_decode_impl(dims, o, nullptr, enc, enc_a, lens, h0, workspace, ws_bytes, tokens,
-                          hyp_lens, scores, aw, stream);
+  return beam_decode_impl(dims, o, nullptr, ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace,
+                          ws_bytes, tokens, hyp_lens, scores, aw, stream);
 }
 
 extern "C" int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
@@ -921,6 +974,19 @@ extern "C" int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_
                                        int32_t* hyp_lens, double* scores, float* aw, void* stream) {
   ASR_REQUIRE(ctc, ASR_ERR_ARG, "att_beam_decode_ctc: ctc is null");
   // weight 0 is the attention-only search itself
-  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, enc, enc_a, lens, h0,
-                          workspace, ws_bytes, tokens, hyp_lens, scores, aw, stream);
+  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, ASR_ATT_BEAM_CELL_LSTM, enc,
+                          enc_a, lens, h0, workspace, ws_bytes, tokens, hyp_lens, scores, aw,
+                          stream);
+}
+
+// the search with the cell type chosen: cell == LSTM is the two entry points above
+extern "C" int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                      const asr_att_beam_ex_t* ex, const float* enc,
+                                      const float* enc_a, const int32_t* lens, const float* h0,
+                                      void* workspace, size_t ws_bytes, long long* tokens,
+                                      int32_t* hyp_lens, double* scores, float* aw, void* stream) {
+  ASR_REQUIRE(ex, ASR_ERR_ARG, "att_beam_decode_ex: ex is null");
+  const asr_att_beam_ctc_t* ctc = (ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
+  return beam_decode_impl(dims, o, ctc, ex->cell, enc, enc_a, lens, h0, workspace, ws_bytes, tokens,
+                          hyp_lens, scores, aw, stream);
 }

@@ -330,6 +330,17 @@ class AttentionSeq2seq(ModelBase):
                 and dec.rnn_type == 'lstm' and not dec.residual and not dec.dense_residual
                 and att is not None and att.single_additive)
 
+    def _beam_device_ok(self, task, dir):
+        """The device beam search (csrc/att_beam.hip) covers what _fused_ok
+        covers and the same decoder with a GRUCell in the LSTMCell's place: only
+        its cell kernel knows the cell type.  Training and the greedy pass of a
+        GRU decoder stay on the per-step paths (_fused_ok)."""
+        dec = getattr(self, 'decoder_%d_%s' % (task, dir), None)
+        att = getattr(self, 'attend_%d_%s' % (task, dir), None)
+        return (self.decoding_order == 'bahdanau' and dec is not None and dec.num_layers == 1
+                and dec.rnn_type in ('lstm', 'gru') and not dec.residual
+                and not dec.dense_residual and att is not None and att.single_additive)
+
     @staticmethod
     def _run_dec(mod, inp, hx, cx):
         """RNNDecoder.forward with the (hx, cx) pair of either cell type (GRU
@@ -651,9 +662,10 @@ class AttentionSeq2seq(ModelBase):
     def _decode_infer_beam(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
                            length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
                            _scores=None, ctc_weight=0):
-        """:1038-1237.  Decoders the fused pass covers (_fused_ok) search on the
-        device (native_ops.att_decode_beam, csrc/att_beam.hip: no host read
-        inside the step loop); the others, a shape the kernels refuse, and
+        """:1038-1237.  Decoders the fused pass covers and their GRU twins
+        (_beam_device_ok) search on the device (native_ops.att_decode_beam,
+        csrc/att_beam.hip: no host read inside the step loop); the others,
+        a shape the kernels refuse, and
         ASR_ATT_BEAM=host run _decode_infer_beam_host.  Same results either
         way; native_ops.last_att_beam_path() says which ran.  _gaps: a list
         that receives the host path's decision margins (filled by that path
@@ -664,7 +676,7 @@ class AttentionSeq2seq(ModelBase):
         if coverage_penalty > 0:
             raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
         self._check_ctc_weight(ctc_weight, beam_width, task, dir)
-        if (self._fused_ok(task, dir) and max_decode_len >= 1
+        if (self._beam_device_ok(task, dir) and max_decode_len >= 1
                 and os.environ.get('ASR_ATT_BEAM', 'device') != 'host'):
             out = self._decode_infer_beam_device(enc_out, x_lens, beam_width, max_decode_len,
                                                  min_decode_len, length_penalty, task, dir,
@@ -683,7 +695,8 @@ class AttentionSeq2seq(ModelBase):
         """The whole search as one op; None when the kernels refuse the shape.
         One device-to-host copy of the compact results at the end."""
         att = getattr(self, 'attend_%d_%s' % (task, dir))
-        cell = getattr(self, 'decoder_%d_%s' % (task, dir)).lstm_l0
+        dec = getattr(self, 'decoder_%d_%s' % (task, dir))
+        cell = getattr(dec, '%s_l0' % dec.rnn_type)          # lstm_l0 / gru_l0
         W_d, W_c = getattr(self, 'W_d_%d_%s' % (task, dir)), getattr(self, 'W_c_%d_%s' % (task, dir))
         fc = getattr(self, 'fc_%d_%s' % (task, dir))
         embed = getattr(self, 'embed_%d' % task)
@@ -703,6 +716,8 @@ class AttentionSeq2seq(ModelBase):
         joint = {}
         if ctc_weight > 0:
             joint = dict(ctc_logits=self._ctc_logits_f32(enc_out, task), ctc_weight=ctc_weight)
+        if dec.rnn_type == 'gru':
+            joint['cell'] = 'gru'
         out = ops.att_decode_beam(enc_out, enc_a, lens.astype(np.int32), h0, self._emb_dims[task],
                                   self.sharpening_factor, self.sigmoid_smoothing,
                                   cell.weight_ih, cell.weight_hh, att.W_dec_head0.fc.weight,

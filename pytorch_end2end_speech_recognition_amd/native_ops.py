@@ -1076,22 +1076,30 @@ def _set_att_beam_path(path):
 @torch.no_grad()
 def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh, w_dec, w_conv,
                     conv_w, v, gen, beam_width, max_len, min_len, length_penalty, eos,
-                    ctc_logits=None, ctc_weight=0):
+                    ctc_logits=None, ctc_weight=0, cell='lstm'):
     """Attention beam search on the device (asr_att_beam_decode, csrc/att_beam.hip;
     attention_seq2seq.py:1038-1237, bahdanau order): every utterance over its
     own lens[b] frames, f32 in both compute modes, no host read inside the
     step loop.  gen as att_decode_greedy.  ctc_weight > 0: the joint
     CTC/attention search (asr_att_beam_decode_ctc) on ctc_logits [B, T, Vc],
     the raw f32 logits of the CTC head (blank 0, attention class c is CTC class
-    c + 1); ctc_weight == 0 is the plain search.  Returns (tokens int64 [B, max_len],
+    c + 1); ctc_weight == 0 is the plain search.  cell: 'lstm' (w_ih [4D, .],
+    the calls above), or 'gru' for a GRUCell decoder (w_ih [3D, .], gate rows r,
+    z, n; asr_att_beam_decode_ex, plain or joint).  Returns (tokens int64 [B, max_len],
     lengths int32 [B], scores float64 [B], aw float32 [B, max_len, T]) on the
     device, or None when the kernels do not cover the shape
     (ASR_ERR_UNSUPPORTED; the reason is asr_last_error's)."""
     N.require_device(enc, enc_a, w_ih)
+    if cell not in ('lstm', 'gru'):
+        raise ValueError("att_decode_beam: cell = %r is not 'lstm' or 'gru'" % (cell,))
     enc, enc_a = enc.contiguous().float(), enc_a.contiguous().float()
     B, T, E = enc.shape
     A = enc_a.shape[-1]
     D = w_hh.shape[1]
+    gates = 4 if cell == 'lstm' else 3
+    if w_ih.shape[0] != gates * D or w_hh.shape[0] != gates * D:
+        raise ValueError('att_decode_beam: a %s cell needs w_ih / w_hh of %d x D rows, got %s, %s'
+                         % (cell, gates, tuple(w_ih.shape), tuple(w_hh.shape)))
     C, K = conv_w.shape[0], conv_w.shape[-1]
     dev = enc.device
     V, Dz = gen['w_fc'].shape
@@ -1135,7 +1143,13 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     h0c = h0.contiguous().float() if h0 is not None else None
     tail = (N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d), N.ptr(h0c), N.ptr(ws), ws.numel(),
             N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw), N.stream_handle(dev))
-    if lam > 0:
+    if cell == 'gru':
+        fn = 'asr_att_beam_decode_ex'
+        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) \
+            if lam > 0 else None
+        ex = N.AttBeamEx(N.ATT_BEAM_CELL_GRU, ctypes.addressof(ctc) if ctc is not None else None)
+        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ex), *tail)
+    elif lam > 0:
         fn = 'asr_att_beam_decode_ctc'
         ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam)
         rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ctc), *tail)

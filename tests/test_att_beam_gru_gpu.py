@@ -1,0 +1,308 @@
+"""Attention beam search on the device for GRU decoders (beam_cell_gru in
+csrc/att_beam.hip, asr_att_beam_decode_ex, native_ops.att_decode_beam(cell='gru'))
+against the host path (ASR_ATT_BEAM=host) on small random models, against a
+fixture recorded from the reference, through error_rate, the hierarchical model
+and both compute modes, and the new C entry point against the old ones.
+
+Cases, seeds, lengths and the margin rule are tests/test_att_beam_gru_cpu.py's:
+an utterance whose host-side decision margin (_gaps) is below GAP = 1e-3 is left
+out of the equality check, at most one in ten per case.  Scores: within 16 x the
+largest f32-against-f64 best-score difference of the CPU restatement
+(tests/att_beam_gru_ref.py) over these cases, computed and printed here; as in
+tests/test_att_beam_ctc_gpu.py a best score below -1e9 (a dead CTC prefix won:
+weight * LOGZERO, where a double's spacing exceeds the bound) is neither counted
+nor asserted."""
+import ctypes
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import edit_distance_ref
+import test_att_beam_gru_cpu as C
+from conftest import golden, golden_params
+
+pytestmark = pytest.mark.gpu
+
+GAP, LENS, CASES, SEEDS = C.GAP, C.LENS, C.CASES, C.SEEDS
+
+
+def _model(kw_over, eos_bias, seed, cls=None, dir='fwd'):
+    model, kw, sd = C.model_cpu(kw_over, eos_bias, seed, cls, dir)
+    model.set_cuda()
+    model.eval()
+    return model, kw, sd
+
+
+def _decode(model, enc, mode, W, max_len, min_len=0, penalty=0, lam=0.0, dir='fwd', gaps=None):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    old = os.environ.get('ASR_ATT_BEAM')
+    os.environ['ASR_ATT_BEAM'] = mode
+    try:
+        scores = []
+        with torch.no_grad():
+            hyps, aws = model._decode_infer_beam(
+                torch.from_numpy(enc).cuda(), np.array(LENS), W, max_len, min_len, penalty, 0,
+                dir=dir, _gaps=gaps, _scores=scores, ctc_weight=lam)
+        torch.cuda.synchronize()
+    finally:
+        if old is None:
+            del os.environ['ASR_ATT_BEAM']
+        else:
+            os.environ['ASR_ATT_BEAM'] = old
+    return [np.asarray(h) for h in hyps], aws, scores, native_ops.last_att_beam_path()
+
+
+@functools.lru_cache(maxsize=None)
+def _score_bound():
+    """16 x the largest |f32 - f64| best-hypothesis score of the CPU restatement
+    over the GRU cases (utterances whose hypotheses agree in both dtypes)."""
+    worst = 0.0
+    for name in CASES:
+        a, r = C.ref(name, False), C.ref(name, True)
+        for h32, h64, s32, s64 in zip(a[0], r[0], a[1], r[1]):
+            if np.array_equal(h32, h64) and s64 > -1e9:
+                worst = max(worst, abs(s32 - s64))
+    print('att_beam_gru: restatement f32-vs-f64 score error %.3e, bound %.3e'
+          % (worst, 16 * worst))
+    return 16 * worst
+
+
+# ------------------------------------------------------- 1. device vs host
+@pytest.mark.parametrize('name', list(CASES))
+def test_device_matches_host(name, cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.set_compute_dtype('fp32')
+    kw_over, bias, o = CASES[name]
+    model, _, _ = _model(kw_over, bias, SEEDS[name], dir=o.get('dir', 'fwd'))
+    enc = C.enc_out()
+    gaps = []
+    ref_h, ref_aw, ref_s, path = _decode(model, enc, 'host', gaps=gaps, **o)
+    assert path == 'host' and len(gaps) == len(LENS)
+    got_h, got_aw, got_s, path = _decode(model, enc, 'device', **o)
+    assert path == 'device'
+    left_out = [b for b, g in enumerate(gaps) if g < GAP]
+    print('att_beam_gru %s: left out %d of %d (smallest gap %.3e)'
+          % (name, len(left_out), len(LENS), min(gaps)))
+    assert len(left_out) * 10 <= len(LENS)
+    bound = _score_bound()
+    r_h = C.ref(name)[0]
+    for b in range(len(LENS)):
+        if b in left_out:
+            continue
+        np.testing.assert_array_equal(got_h[b], ref_h[b], err_msg='utterance %d' % b)
+        np.testing.assert_array_equal(got_h[b], r_h[b], err_msg='utterance %d (restatement)' % b)
+        assert got_aw[b].shape == ref_aw[b].shape == (len(ref_h[b]), LENS[b])
+        np.testing.assert_allclose(got_aw[b], ref_aw[b], rtol=1e-3, atol=1e-5)
+        print('att_beam_gru %s utt %d: score device %.9f host %.9f' % (name, b, got_s[b], ref_s[b]))
+        if ref_s[b] > -1e9:
+            assert abs(got_s[b] - ref_s[b]) <= bound
+
+
+# ------------------------------------------------- 2. the reference's fixture
+def test_fixture_on_device_path(cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    from pytorch_end2end_speech_recognition_amd.models.pytorch_v3.attention.attention_seq2seq \
+        import AttentionSeq2seq
+    d = golden('beam_att_gru')
+    kw = json.loads(str(d['kwargs']))
+    opts = json.loads(str(d['opts']))
+    assert kw['encoder_type'] == 'gru' and kw['decoder_type'] == 'gru' and opts['beam_width'] == 4
+    sd, _ = golden_params(d)
+    torch.manual_seed(int(d['seed'][0]))
+    model = AttentionSeq2seq(**kw)
+    model.load_state_dict(sd)
+    model.set_cuda()
+    native_ops.set_compute_dtype('fp32')
+    hyps, aw, perm = model.decode(d['xs'], d['x_lens'], **opts)
+    assert native_ops.last_att_beam_path() == 'device'
+    np.testing.assert_array_equal(perm, d['perm'])
+    np.testing.assert_array_equal([len(h) for h in hyps], d['hyp_lens'])
+    np.testing.assert_array_equal(np.concatenate([np.asarray(h) for h in hyps]), d['hyp_flat'])
+    got = np.concatenate([np.asarray(a, np.float32).reshape(-1) for a in aw])
+    np.testing.assert_allclose(got, d['aw_flat'], rtol=1e-3, atol=1e-5)
+
+
+# ------------------------------------------------------- 3. hierarchical
+def test_hierarchical_both_tasks(cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    from pytorch_end2end_speech_recognition_amd.models.pytorch_v3.attention.\
+        hierarchical_attention_seq2seq import HierarchicalAttentionSeq2seq
+    native_ops.set_compute_dtype('fp32')
+    kw = {k: v for k, v in C.BASE.items() if k != 'ctc_loss_weight'}
+    kw.update(encoder_num_layers=2, encoder_num_layers_sub=1, decoder_num_units_sub=7,
+              decoder_num_layers_sub=1, embedding_dim_sub=3, num_classes_sub=5,
+              main_loss_weight=0.5, sub_loss_weight=0.5, ctc_loss_weight_sub=0,
+              subsample_list=[False, False], bottleneck_dim_sub=8)
+    torch.manual_seed(1623)
+    model = HierarchicalAttentionSeq2seq(**kw)
+    with torch.no_grad():
+        for p in model.parameters():
+            torch.nn.init.uniform_(p, -0.6, 0.6)
+        model.fc_0_fwd.fc.bias[6] -= 1.5
+        model.fc_1_fwd.fc.bias[5] -= 1.5
+    model.set_cuda()
+    model.eval()
+    assert model.decoder_0_fwd.rnn_type == model.decoder_1_fwd.rnn_type == 'gru'
+    rng = np.random.RandomState(11)
+    x_lens = np.array([40, 33, 31, 27, 20, 16, 9, 5, 2, 1])
+    B = len(x_lens)
+    xs = rng.uniform(-1, 1, (B, 40, 8)).astype(np.float32)
+    for b in range(B):
+        xs[b, x_lens[b]:] = 0
+    with torch.no_grad():
+        enc, _, enc_sub, _, _ = model._encode(model.np2var(xs, dtype='float'), x_lens,
+                                              is_multi_task=True)
+    lens = {0: model.encoder.last_lens_np, 1: model.encoder.last_lens_sub_np}
+    for task in (0, 1):
+        # the host path's margins of this task, then decode() itself on both paths
+        gaps = []
+        os.environ['ASR_ATT_BEAM'] = 'host'
+        try:
+            with torch.no_grad():
+                model._decode_infer_beam(enc if task == 0 else enc_sub, lens[task], 3, 5, 0, 0.3,
+                                         0, task=task, _gaps=gaps)
+            ref_h, ref_aw, _ = model.decode(xs, x_lens, 3, 5, length_penalty=0.3,
+                                            task_index=task)
+            assert native_ops.last_att_beam_path() == 'host'
+        finally:
+            del os.environ['ASR_ATT_BEAM']
+        got_h, got_aw, _ = model.decode(xs, x_lens, 3, 5, length_penalty=0.3, task_index=task)
+        assert native_ops.last_att_beam_path() == 'device'
+        left_out = [b for b, g in enumerate(gaps) if g < GAP]
+        print('att_beam_gru hierarchical task %d: left out %d of %d (smallest gap %.3e)'
+              % (task, len(left_out), B, min(gaps)))
+        assert len(left_out) * 10 <= B
+        for b in range(B):
+            if b in left_out:
+                continue
+            np.testing.assert_array_equal(np.asarray(got_h[b]), np.asarray(ref_h[b]),
+                                          err_msg='task %d utterance %d' % (task, b))
+            np.testing.assert_allclose(got_aw[b], ref_aw[b], rtol=1e-3, atol=1e-5)
+
+
+# ------------------------------------------------------------ 4. error_rate
+@pytest.mark.parametrize('lam', C.ER_LAMS)
+def test_error_rate_scores_the_host_hypotheses(lam, cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.set_compute_dtype('fp32')
+    model, kw, _ = _model(C.ER_KW, C.ER_BIAS, C.ER_SEED)
+    xs, x_lens, ys, y_lens = C.error_rate_batch()
+    B, W, max_len = len(x_lens), C.ER_OPTS['W'], C.ER_OPTS['max_len']
+    extra = dict(ctc_weight=lam) if lam > 0 else {}
+    out = model.error_rate(xs, x_lens, ys, y_lens, W, max_decode_len=max_len, **extra)
+    assert native_ops.last_att_beam_path() == 'device'
+    os.environ['ASR_ATT_BEAM'] = 'host'
+    try:
+        with torch.no_grad():        # the margins of the host decode, on its own encoder output
+            enc, _, _ = model._encode(model.np2var(xs, dtype='float'), x_lens)
+            gaps = []
+            model._decode_infer_beam(enc, model.encoder.last_lens_np, W, max_len, 0, 0, 0,
+                                     _gaps=gaps, ctc_weight=lam)
+        hyps, _, perm = model.decode(xs, x_lens, W, max_len, **extra)
+        assert native_ops.last_att_beam_path() == 'host'
+    finally:
+        del os.environ['ASR_ATT_BEAM']
+    hyps = [np.asarray(h) for h in hyps]
+    assert sum(len(h) for h in hyps) > 0
+    want = edit_distance_ref.score(hyps, [len(h) for h in hyps], ys[perm], y_lens[perm],
+                                   eos=model.eos_0)
+    left_out = [b for b, g in enumerate(gaps) if g < GAP]
+    print('att_beam_gru error_rate lam %g: left out %d of %d (smallest gap %.3e)'
+          % (lam, len(left_out), B, min(gaps)))
+    assert len(left_out) * 10 <= B
+    keep = [b for b in range(B) if b not in left_out]
+    np.testing.assert_array_equal(out.cpu().numpy()[keep], want[keep])
+
+
+# ---------------------------------------------------- 5. both compute modes
+def test_bf16_mode_equals_fp32_mode(cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    kw_over, bias, _ = CASES['first']
+    model, _, _ = _model(kw_over, bias, SEEDS['first'])
+    assert model.init_dec_state_0_fwd == 'first'
+    enc = C.enc_out()
+    o = dict(W=4, max_len=8)
+    native_ops.set_compute_dtype('fp32')
+    h32, aw32, s32, _ = _decode(model, enc, 'device', **o)
+    native_ops.set_compute_dtype('bf16')
+    try:
+        h16, aw16, s16, path = _decode(model, enc, 'device', **o)
+    finally:
+        native_ops.set_compute_dtype('fp32')
+    assert path == 'device'
+    assert s16 == s32
+    for b in range(len(LENS)):
+        np.testing.assert_array_equal(h16[b], h32[b])
+        np.testing.assert_array_equal(aw16[b], aw32[b])
+
+
+# ------------------------------------------ 6. what stays on the host path
+@pytest.mark.parametrize('kw_over', [dict(decoder_num_layers=2), dict(num_heads=2)],
+                         ids=['dec2', 'heads2'])
+def test_other_gru_decoders_stay_on_the_host_path(kw_over, cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.set_compute_dtype('fp32')
+    model, _, _ = _model(kw_over, 0.0, 1623)
+    native_ops._set_att_beam_path(None)
+    hyps, _, _, path = _decode(model, C.enc_out(), 'device', W=3, max_len=3)
+    assert path == 'host'
+    assert len(hyps) == len(LENS) and all(1 <= len(h) <= 3 for h in hyps)
+
+
+# ----------------------------------------------------------------- 7. C ABI
+def _lstm_w2():
+    """The w2 case of tests/test_att_beam_gpu.py (an LSTM decoder) and its options."""
+    import test_att_beam_gpu as L
+    kw_over, bias, o = L.CASES['w2']
+    model, _, _ = L._model(kw_over, bias, L.SEEDS['w2'])
+    return L, model, o
+
+
+def _through_ex(monkeypatch, cell):
+    """Route native_ops' asr_att_beam_decode calls through asr_att_beam_decode_ex
+    with `cell` and a null ctc: the same arguments otherwise, bit for bit."""
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    lib = N.lib()
+    real_ex = lib.asr_att_beam_decode_ex
+    calls = []
+
+    def shim(dims, opts, *tail):
+        ex = N.AttBeamEx(cell, None)
+        calls.append(cell)
+        return real_ex(dims, opts, ctypes.byref(ex), *tail)
+    monkeypatch.setattr(lib, 'asr_att_beam_decode', shim, raising=False)
+    return calls
+
+
+def test_ex_entry_with_lstm_cell_is_bitwise_the_old_entry(monkeypatch, cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.set_compute_dtype('fp32')
+    L, model, o = _lstm_w2()
+    enc = L._enc()
+    h0, aw0, s0, path = L._decode(model, enc, 'device', **o)
+    assert path == 'device'
+    calls = _through_ex(monkeypatch, N.ATT_BEAM_CELL_LSTM)
+    h1, aw1, s1, path = L._decode(model, enc, 'device', **o)
+    assert path == 'device' and calls == [N.ATT_BEAM_CELL_LSTM]
+    assert s0 == s1
+    for b in range(len(L.LENS)):
+        np.testing.assert_array_equal(h0[b], h1[b])
+        np.testing.assert_array_equal(aw0[b], aw1[b])
+
+
+def test_ex_entry_refuses_an_unknown_cell(monkeypatch, cuda_dev):
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    from pytorch_end2end_speech_recognition_amd import native_ops
+    native_ops.set_compute_dtype('fp32')
+    L, model, o = _lstm_w2()
+    calls = _through_ex(monkeypatch, 7)
+    # rc = ASR_ERR_ARG (-1) from the cell check, which precedes every launch
+    with pytest.raises(N.NativeError, match=r'rc=-1\): .*unknown cell 7'):
+        L._decode(model, L._enc(), 'device', **o)
+    assert calls == [7]
+    torch.cuda.synchronize()

@@ -14,6 +14,13 @@ attention-only search on the model without one.  One process; per shape
 and path: warm-up calls, then wall time around each call with a device synchronisation on both sides (the
 host path synchronises by itself at every step), median (min .. max).
 
+--timit: the TIMIT attention recipe's decoder instead (bgru_att_phone61: GRU
+encoder with a bridge layer, so encoder width 256 at the decoder; one-layer GRU
+decoder 256, attention 128, bottleneck 256, embedding 32, 10 x 201 location
+convolution, init_dec_state zero, 61 phones + <eos>); (W 4, V 62), (W 10, V 62);
+B, T and max_decode_len as above.  Without it the shapes, the models and the
+output are the ones above.
+
 Writes profiles/att_beam_bench.txt (or --out).
 """
 import argparse
@@ -49,6 +56,7 @@ def main():
     ap.add_argument('--host_repeats', type=int, default=3)
     ap.add_argument('--max_decode_len', type=int, default=100)
     ap.add_argument('--ctc-weight', type=float, default=0.0)
+    ap.add_argument('--timit', action='store_true')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('att_beam_bench: needs an MI355X; a CPU run gives no time')
@@ -60,7 +68,8 @@ def main():
     rng = np.random.RandomState(0)
     lens = np.sort(rng.randint(150, T + 1, B))[::-1].copy()
     lens[0] = T
-    enc_np = rng.uniform(-1, 1, (B, T, 640)).astype(np.float32)
+    width = 256 if args.timit else 640
+    enc_np = rng.uniform(-1, 1, (B, T, width)).astype(np.float32)
     for b in range(B):
         enc_np[b, lens[b]:] = 0
     enc = torch.from_numpy(enc_np).cuda()
@@ -70,15 +79,24 @@ def main():
              % (B, T, lens.min(), lens.max(), S, args.repeats, args.host_repeats, args.warmup,
                 args.ctc_weight)]
     joint = dict(ctc_loss_weight=0.2) if args.ctc_weight > 0 else {}
-    for W, V in ((4, 29), (10, 29), (10, 10001)):
+    sizes = dict(encoder_type='lstm', encoder_num_units=320, decoder_type='lstm',
+                 decoder_num_units=320, embedding_dim=64, init_dec_state='first')
+    shapes = ((4, 29), (10, 29), (10, 10001))
+    if args.timit:
+        lines[0] += '; TIMIT recipe decoder: GRU 256, encoder width 256 (bridge), embedding 32'
+        sizes = dict(encoder_type='gru', encoder_num_units=256, decoder_type='gru',
+                     decoder_num_units=256, embedding_dim=32, init_dec_state='zero',
+                     bridge_layer=True)
+        shapes = ((4, 62), (10, 62))
+    for W, V in shapes:
         torch.manual_seed(V + W)
         model = AttentionSeq2seq(
-            input_size=40, encoder_type='lstm', encoder_bidirectional=True, encoder_num_units=320,
+            input_size=40, encoder_bidirectional=True,
             encoder_num_proj=0, encoder_num_layers=1, attention_type='location',
-            attention_dim=128, decoder_type='lstm', decoder_num_units=320, decoder_num_layers=1,
-            embedding_dim=64, dropout_input=0, dropout_encoder=0, dropout_decoder=0,
+            attention_dim=128, decoder_num_layers=1,
+            dropout_input=0, dropout_encoder=0, dropout_decoder=0,
             dropout_embedding=0, num_classes=V - 1, subsample_list=[False],
-            init_dec_state='first', bottleneck_dim=256, **joint)
+            bottleneck_dim=256, **sizes, **joint)
         with torch.no_grad():
             model.fc_0_fwd.fc.bias[V - 1] -= 30.0
         model.set_cuda()
