@@ -111,7 +111,14 @@ int asr_ctc_backward_bf16(const float* acts, long long stride_t, long long strid
  * gradient of the fused CTC head: the reference's LinearND bias gradient,
  * linear.py:32-47, summed from dY = ctc.py:30-52's gradient).  Deterministic
  * (fixed-order per-block partials); bias_ws holds
- * asr_ctc_bias_workspace_bytes(T, B, V, gld) bytes.  V <= 16384. */
+ * asr_ctc_bias_workspace_bytes(T, B, V, gld) bytes.  Supported where
+ * asr_ctc_bias_supported(V, gld, max_label_len) returns 1 (gld <= 16384, and
+ * for V > 256 the class table beside the lattice-state arrays within a
+ * work-group's 64 KiB of LDS: V <= 16256 for labels up to 31, V <= 14336 for
+ * labels up to 511); ASR_ERR_UNSUPPORTED otherwise, with nothing written --
+ * the caller then runs asr_ctc_backward_bf16 and sums the bias gradient from
+ * dY. */
+int asr_ctc_bias_supported(int V, int gld, int max_label_len);
 size_t asr_ctc_bias_workspace_bytes(int T, int B, int V, int gld);
 int asr_ctc_backward_bf16_db(const float* acts, long long stride_t, long long stride_b, int T,
                              int B, int V, const int32_t* labels_flat, const int32_t* label_lens,

@@ -1942,6 +1942,29 @@ static void ctc_bias_grid(int T, int B, int V, int* rpb, int* nblk) {
   *nblk = (int)((rows + r - 1) / r);
 }
 
+// 8-column chunks per thread of the gradient pass that also sums the bias
+// gradient (the NCH of ctc_grad_bf16 / ctc_grad_bf16_pipe), or 0 where
+// asr_ctc_backward_bf16_db refuses: more than 8 chunks per thread (gld >
+// 16384), or a wide head whose class table [V] beside the two [Spad] state
+// arrays exceeds the 64 KiB of LDS a work-group gets -- V > 16256 at Spad 64,
+// V > 14336 at Spad 1024.  (Every width the streamed pass takes, gld <=
+// 12288, passes: that pass keeps no [V] table, and 2 * 1024 + 12288 fits.)
+static int ctc_bias_nch(int V, int gld, int max_label_len) {
+  if (V <= 1 || gld < V || max_label_len < 0 || 2 * max_label_len + 1 > 64 * kMaxK) return 0;
+  const bool table = V <= 256;
+  const int threads = table ? 64 : 256;
+  const int n8 = gld >> 3;
+  int nch = (n8 + threads - 1) / threads;
+  nch = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 5 ? 5 : nch <= 8 ? 8 : 0;
+  const int Spad = 64 * pick_k(max_label_len);
+  if (!table && (size_t)(2 * Spad + V) * 4 > 64 * 1024) nch = 0;
+  return nch;
+}
+
+extern "C" int asr_ctc_bias_supported(int V, int gld, int max_label_len) {
+  return ctc_bias_nch(V, gld, max_label_len) > 0;
+}
+
 extern "C" size_t asr_ctc_bias_workspace_bytes(int T, int B, int V, int gld) {
   if (T <= 0 || B <= 0 || V <= 1 || gld < V) return 0;
   int rpb, nblk;
@@ -1994,11 +2017,11 @@ static int ctc_backward_bf16_impl(const float* acts, long long stride_t, long lo
     ASR_REQUIRE(bws && bws_bytes >= asr_ctc_bias_workspace_bytes(T, B, V, gld), ASR_ERR_WORKSPACE,
                 "ctc_bf16_db: bias workspace %zu < %zu", bws_bytes,
                 asr_ctc_bias_workspace_bytes(T, B, V, gld));
-    const int n8 = gld >> 3;
-    nch = (n8 + threads - 1) / threads;
-    nch = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 5 ? 5 : nch <= 8 ? 8 : 0;
-    ASR_REQUIRE(nch > 0 && (table || (size_t)(2 * Spad + V) * 4 <= 64 * 1024), ASR_ERR_UNSUPPORTED,
-                "ctc_bf16_db: V %d too wide for the in-kernel bias sums", V);
+    nch = ctc_bias_nch(V, gld, max_label_len);
+    ASR_REQUIRE(nch > 0, ASR_ERR_UNSUPPORTED,
+                "ctc_bf16_db: V %d (gld %d, max_label_len %d) too wide for the in-kernel bias "
+                "sums; asr_ctc_bias_supported says so beforehand",
+                V, gld, max_label_len);
     ctc_bias_grid(T, B, V, &rpb, &nblk);
     colpart = (float*)bws;
   }

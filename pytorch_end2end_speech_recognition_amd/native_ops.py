@@ -676,9 +676,11 @@ class LinearCTCFn(torch.autograd.Function):
                 N.ptr(act_lens), max_label_len, blank, N.ptr(g),
                 loss_scale if g is not None else 0.0, N.ptr(dyo), Np, T * Np, Np, N.ptr(ws), nbytes)
         # the bias gradient: f32 column sums formed inside the gradient pass before
-        # the bf16 rounding (ASR_CTC_HEAD_DB=0: column sums of the rounded dY)
+        # the bf16 rounding (ASR_CTC_HEAD_DB=0, or a head too wide for that pass's
+        # class table by the library's own condition: column sums of the rounded dY)
         bws = None
-        if bias is not None and V <= 16384 and os.environ.get('ASR_CTC_HEAD_DB', '1') != '0':
+        if (bias is not None and os.environ.get('ASR_CTC_HEAD_DB', '1') != '0'
+                and N.query('asr_ctc_bias_supported', V, Np, max_label_len)):
             bnb = N.query('asr_ctc_bias_workspace_bytes', T, B, V, Np)
             bws = _ws(bnb, dev)
             N.call('asr_ctc_backward_bf16_db', *args, N.ptr(grad_buffer(bias)), N.ptr(bws), bnb,

@@ -1,0 +1,307 @@
+"""The CTC gradient pass (csrc/ctc.hip behind asr_ctc_backward_bf16 /
+asr_ctc_backward_bf16_db) against the float64 reference of
+tests/ctc_width_ref.py at every vocabulary width where the dispatch changes
+its kernel or the kernel's chunks-per-thread template argument, through the C
+entry points alone (no GEMM):
+
+    V      pitch  default            ASR_CTC_GRAD_STREAM=0  + ASR_CTC_GRAD_PIPE=0
+    2051   2052   4 stream<1>        3 pipe<2>              1 bf16<false,2,true>
+    2051   2051   1 bf16<false,2,false> (rows not 16-B aligned)
+    4099   4100   4 stream<2>        3 pipe<4>              1 bf16<false,4>
+    6151   6152   4 stream<2>        3 pipe<4>, 4th live    1
+    10243  10244  4 stream<3>        3 pipe<8>              1 bf16<false,8>
+    14339  14340  3 pipe<8>, all eight chunks live          1   (ASR_CTC_GRAD_PIPE=0)
+    16389  16392  no bias: 1 bf16<false,0>; with bias ASR_ERR_UNSUPPORTED
+
+(the number is asr_ctc_last_path()[1]).  Each row runs with
+ASR_CTC_BIAS_BLOCKS unset (one row per block at 42 rows) and = 2 (21 rows per
+block: a block's chain of rows crosses utterance boundaries and dead rows).
+B 3 x T 14, lengths (14, 11, 6), labels (5, 3, 1) with an adjacent repeat, two
+classes of one 8-column chunk and class V - 1; scale 1/3 x a device scalar 2.
+dY rows have pitch gld = V rounded up to 8 and are prefilled with bf16 NaN,
+dbias with 0.25, and the logits' padding columns V .. P-1 hold NaN (the fused
+heads allocate them with torch.empty).
+
+Per case: costs at rtol 1e-4; dY and db within ctc_width_ref.bound (MARGIN 16 x
+the float32-evaluation constant x max |ref|, + one bf16 ulp for dY); columns
+V .. gld-1 and every row t >= act_len exactly 0; no NaN; two runs bitwise
+equal; pipe vs plain dY bitwise, stream vs plain bitwise outside the blank
+column and within one bf16 ulp in it.  The error-to-bound ratios are printed.
+
+Last: the fused head (native_ops.linear_ctc_loss, bf16) at V = 16301 and
+16384, where asr_ctc_backward_bf16_db refuses (class table beyond 64 KiB of
+LDS) and LinearCTCFn.backward must sum the bias gradient from dY instead."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import ctc_width_ref as R
+from oracle import ctc_ref
+
+pytestmark = pytest.mark.gpu
+
+ENVS = ('ASR_CTC_GRAD_STREAM', 'ASR_CTC_GRAD_PIPE', 'ASR_CTC_BIAS_BLOCKS')
+STREAM = ('stream', {}, 4)
+PIPE = ('pipe', {'ASR_CTC_GRAD_STREAM': '0'}, 3)
+PLAIN = ('plain', {'ASR_CTC_GRAD_STREAM': '0', 'ASR_CTC_GRAD_PIPE': '0'}, 1)
+ROWS = {
+    (2051, 2052): (STREAM, PIPE, PLAIN),
+    (2051, 2051): (('plain', {}, 1),),
+    (4099, 4100): (STREAM, PIPE, PLAIN),
+    (6151, 6152): (STREAM, PIPE, PLAIN),
+    (10243, 10244): (STREAM, PIPE, PLAIN),
+    (14339, 14340): (('pipe', {}, 3), ('plain', {'ASR_CTC_GRAD_PIPE': '0'}, 1)),
+}
+assert set(ROWS) | {(16389, 16392)} == set(R.WIDTHS)
+BF16_NAN = 0x7FC0
+
+
+def _N():
+    from pytorch_end2end_speech_recognition_amd import _native
+    return _native
+
+
+def _last_path():
+    N = _N()
+    path = (ctypes.c_int * 2)()
+    N.call('asr_ctc_last_path', ctypes.cast(path, ctypes.c_void_p))
+    return path[1]
+
+
+def _bf16_to_f64(bits):
+    return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32).astype(np.float64)
+
+
+def _bf16_order(bits):
+    """bf16 bit patterns as integers ordered like the values (an ulp apart: 1)."""
+    b = bits.astype(np.int32)
+    return np.where(b & 0x8000, -(b & 0x7FFF), b & 0x7FFF)
+
+
+def _run(c, P, dev, with_bias=True, expect_refusal=False):
+    """asr_ctc_forward then the bf16 gradient entry point on logits of pitch P.
+    Returns costs, loss, the dY bit patterns [B, T, gld], dbias and the
+    gradient path record."""
+    N = _N()
+    B, T, V = c['B'], c['T'], c['V']
+    gld = R.gld_of(V)
+    logits = torch.full((B, T, P), float('nan'), dtype=torch.float32, device=dev)
+    logits[:, :, :V] = torch.from_numpy(c['logits'].copy()).to(dev)   # (the case's array is read-only)
+    lab = torch.from_numpy(c['labels']).to(dev)
+    ll = torch.from_numpy(c['label_lens']).to(dev)
+    al = torch.from_numpy(c['act_lens']).to(dev)
+    mll, blank = int(c['max_label_len']), int(c['blank'])
+    nbytes = N.query('asr_ctc_workspace_bytes', T, B, V, mll)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    costs = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    st = N.stream_handle(dev)
+    N.call('asr_ctc_forward', N.ptr(logits), P, T * P, T, B, V, N.ptr(lab), N.ptr(ll), N.ptr(al),
+           mll, blank, 1, N.ptr(costs), N.ptr(loss), float(c['loss_scale']), N.ptr(ws), nbytes, st)
+    dy = torch.full((B, T, gld), BF16_NAN, dtype=torch.int16, device=dev)
+    dbias = torch.full((V,), 0.25, dtype=torch.float32, device=dev)
+    gs = torch.full((1,), float(c['grad_scale']), dtype=torch.float32, device=dev)
+    args = (N.ptr(logits), P, T * P, T, B, V, N.ptr(lab), N.ptr(ll), N.ptr(al), mll, blank,
+            N.ptr(gs), float(c['loss_scale']), N.ptr(dy), gld, T * gld, gld, N.ptr(ws), nbytes)
+    if with_bias:
+        bnb = N.query('asr_ctc_bias_workspace_bytes', T, B, V, gld)
+        bws = torch.empty(max(bnb, 1), dtype=torch.uint8, device=dev)
+        if expect_refusal:
+            with pytest.raises(N.NativeError) as ei:
+                N.call('asr_ctc_backward_bf16_db', *args, N.ptr(dbias), N.ptr(bws), bnb, st)
+            msg = str(ei.value)
+            assert 'rc=%d' % N.ASR_ERR_UNSUPPORTED in msg and 'too wide' in msg, msg
+        else:
+            N.call('asr_ctc_backward_bf16_db', *args, N.ptr(dbias), N.ptr(bws), bnb, st)
+    else:
+        N.call('asr_ctc_backward_bf16', *args, st)
+    path = _last_path()
+    torch.cuda.synchronize()
+    return dict(costs=costs.cpu().numpy(), loss=float(loss.item()),
+                dy=dy.cpu().numpy().view(np.uint16), dbias=dbias.cpu().numpy(), path=path)
+
+
+def _assert_case(c, out, what, with_bias, fails):
+    """One run against the float64 reference; appends (what, tensor, ratio) to
+    fails where a bound is exceeded (so every figure of a test prints first)."""
+    B, T, V = c['B'], c['T'], c['V']
+    costs64 = R.costs_ref(c)
+    dy64, db64 = R.dy_ref(c)
+    tol_dy, tol_db, k = R.bound(c)
+    np.testing.assert_allclose(out['costs'], costs64, rtol=1e-4)
+    np.testing.assert_allclose(out['loss'], c['loss_scale'] * costs64.sum(), rtol=1e-4)
+    bits = out['dy']
+    assert bits.shape == (B, T, R.gld_of(V))
+    got = _bf16_to_f64(bits)
+    assert not np.isnan(got).any(), (what, int(np.isnan(got).sum()))
+    assert not got[:, :, V:].any(), what                      # padding columns
+    for b in range(B):
+        assert not got[b, c['act_lens'][b]:].any(), (what, b)  # dead rows, all gld columns
+    r_dy = float(np.max(np.abs(got[:, :, :V] - dy64) / tol_dy))
+    msg = '  %-22s dY err/bound %.3f (max err %.2e, const %.2e)' % (
+        what, r_dy, float(np.abs(got[:, :, :V] - dy64).max()), k['dy'])
+    if not np.isfinite(r_dy) or r_dy > 1.0:
+        fails.append((what, 'dY', r_dy))
+    if with_bias:
+        assert not np.isnan(out['dbias']).any(), what
+        db = out['dbias'].astype(np.float64) - 0.25
+        r_db = float(np.max(np.abs(db - db64)) / tol_db)
+        msg += '  db err/bound %.3f (max err %.2e, const %.2e)' % (
+            r_db, float(np.abs(db - db64).max()), k['db'])
+        if not np.isfinite(r_db) or r_db > 1.0:
+            fails.append((what, 'db', r_db))
+    print(msg)
+
+
+def _run_paths(c, P, paths, bias_blocks, dev, monkeypatch):
+    """Every path of one width twice; the per-case assertions, then the
+    cross-path ones."""
+    fails, outs = [], {}
+    for name, env, expect in paths:
+        for e in ENVS:
+            monkeypatch.delenv(e, raising=False)
+        for e, v in env.items():
+            monkeypatch.setenv(e, v)
+        if bias_blocks:
+            monkeypatch.setenv('ASR_CTC_BIAS_BLOCKS', bias_blocks)
+        what = '%s P%d %s%s' % (c['id'], P, name, ' bb' + bias_blocks if bias_blocks else '')
+        a = _run(c, P, dev)
+        b = _run(c, P, dev)
+        assert a['path'] == expect and b['path'] == expect, (what, a['path'], expect)
+        _assert_case(c, a, what, True, fails)
+        assert np.array_equal(a['dy'], b['dy']), what                       # bitwise, two runs
+        assert np.array_equal(a['dbias'].view(np.uint32), b['dbias'].view(np.uint32)), what
+        assert np.array_equal(a['costs'].view(np.uint32), b['costs'].view(np.uint32)), what
+        outs[name] = a
+    if 'pipe' in outs and 'plain' in outs:
+        assert np.array_equal(outs['pipe']['dy'], outs['plain']['dy'])
+    if 'stream' in outs and 'plain' in outs:
+        s, p = outs['stream']['dy'], outs['plain']['dy']
+        other = np.ones(c['V'], bool)
+        other[c['blank']] = False
+        assert np.array_equal(s[:, :, :c['V']][:, :, other], p[:, :, :c['V']][:, :, other])
+        assert np.array_equal(s[:, :, c['V']:], p[:, :, c['V']:])
+        d = np.abs(_bf16_order(s[:, :, c['blank']]) - _bf16_order(p[:, :, c['blank']]))
+        assert int(d.max()) <= 1, int(d.max())
+    assert not fails, fails
+
+
+@pytest.mark.parametrize('bias_blocks', [None, '2'], ids=['bb_default', 'bb2'])
+@pytest.mark.parametrize('V,P', sorted(ROWS), ids=['V%d_P%d' % vp for vp in sorted(ROWS)])
+def test_gradient_width_vs_float64(V, P, bias_blocks, cuda_dev, monkeypatch):
+    print()
+    _run_paths(R.case(V), P, ROWS[(V, P)], bias_blocks, cuda_dev, monkeypatch)
+
+
+def test_gradient_blank_last_class(cuda_dev, monkeypatch):
+    """blank = V - 1 at V = 4099: the blank column sits in the last, partial
+    8-column chunk."""
+    print()
+    _run_paths(R.case(4099, blank=4098), 4100, ROWS[(4099, 4100)], None, cuda_dev, monkeypatch)
+
+
+def test_gradient_long_labels_spad_1024(cuda_dev, monkeypatch):
+    """max_label_len 300 at V = 4099: 1024 padded lattice states (four states
+    per thread in the 256-thread passes, two in the streamed one), B = 2 with
+    T = 608 for the long utterance only."""
+    print()
+    _run_paths(R.case(4099, long_labels=True), 4100, ROWS[(4099, 4100)], None, cuda_dev,
+               monkeypatch)
+
+
+@pytest.mark.parametrize('bias_blocks', [None, '2'], ids=['bb_default', 'bb2'])
+def test_gradient_v16389_no_bias_and_refusal(bias_blocks, cuda_dev, monkeypatch):
+    """V = 16389 (gld 16392: nine chunks per thread): without a bias the wide
+    form bf16<false,0> runs; asr_ctc_backward_bf16_db returns
+    ASR_ERR_UNSUPPORTED with a message and writes nothing, as
+    asr_ctc_bias_supported says beforehand."""
+    N = _N()
+    for e in ENVS:
+        monkeypatch.delenv(e, raising=False)
+    if bias_blocks:
+        monkeypatch.setenv('ASR_CTC_BIAS_BLOCKS', bias_blocks)
+    c, P = R.case(16389), 16392
+    print()
+    fails = []
+    a = _run(c, P, cuda_dev, with_bias=False)
+    b = _run(c, P, cuda_dev, with_bias=False)
+    assert a['path'] == 1 and b['path'] == 1
+    _assert_case(c, a, '%s P%d no bias' % (c['id'], P), False, fails)
+    assert np.array_equal(a['dy'], b['dy'])
+    assert np.all(a['dbias'] == 0.25)
+    assert not fails, fails
+    assert N.query('asr_ctc_bias_supported', 16389, 16392, 5) == 0
+    r = _run(c, P, cuda_dev, with_bias=True, expect_refusal=True)
+    assert np.all(r['dy'] == BF16_NAN) and np.all(r['dbias'] == 0.25)
+
+
+def test_bias_supported_states_the_lds_condition():
+    """asr_ctc_bias_supported: at most 8 chunks of 8 columns per thread, and
+    for V > 256 (2 Spad + V) x 4 bytes within 64 KiB (Spad 64 for labels up to
+    31, 1024 for labels above 255)."""
+    q = lambda V, mll: _N().query('asr_ctc_bias_supported', V, R.gld_of(V), mll)
+    assert [q(V, 5) for V in (29, 2051, 14339, 16256, 16257, 16301, 16384, 16389)] == [
+        1, 1, 1, 1, 0, 0, 0, 0]
+    assert [q(V, 300) for V in (4099, 14336, 14337)] == [1, 1, 0]
+    assert q(15360, 255) == 1 and q(15361, 255) == 0      # Spad 512
+    assert q(4099, 512) == 0                               # beyond the lattice's 1024 states
+
+
+@pytest.mark.parametrize('V,K', [(16301, 32), (16384, 1472)])
+def test_fused_head_beyond_bias_table_vs_oracle(V, K, cuda_dev):
+    """native_ops.linear_ctc_loss in bf16 mode on x [3, 14, K] with a bias at
+    widths where asr_ctc_backward_bf16_db refuses ((2 x 64 + V) x 4 bytes > 64
+    KiB): forward and backward complete (the bias gradient summed from dY),
+    loss within 2e-3 and dX / dW / db within 2e-2 relative L2 of the float64
+    oracle on float64 logits -- the bounds of
+    test_wide_fused_head_v10001_vs_oracle.  Both heads are staged (V = 16301:
+    V % 8 != 0 at 4.4e7 flops; V = 16384: K chosen for 2e9 flops), which the
+    bf16 gradient's path record proves."""
+    from pytorch_end2end_speech_recognition_amd import native_ops as ops
+    rng = np.random.RandomState(V)
+    B, T = 3, 14
+    act_lens = np.array([14, 11, 6], np.int32)
+    label_lens = np.array([5, 3, 1], np.int32)
+    labels = rng.randint(1, V, 9).astype(np.int32)
+    labels[1] = labels[0]
+    labels[4] = V - 1
+    x = (rng.randn(B, T, K) * 0.5).astype(np.float32)
+    for b in range(B):
+        x[b, act_lens[b]:] = 0
+    w = (rng.randn(V, K) * (0.05 if K == 32 else 0.02)).astype(np.float32)
+    bias = (rng.randn(V) * 0.1).astype(np.float32)
+    logits = x.astype(np.float64) @ w.T.astype(np.float64) + bias.astype(np.float64)
+    c_ref, g_ref = ctc_ref.ctc_batch(logits, labels, label_lens, act_lens, time_major=False)
+    assert np.all(np.isfinite(c_ref)) and np.all(c_ref > 0)
+    g_ref = g_ref / B
+    loss_ref = c_ref.sum() / B
+    refs = [g_ref @ w.astype(np.float64),
+            np.tensordot(g_ref, x.astype(np.float64), axes=([0, 1], [0, 1])),
+            g_ref.sum(axis=(0, 1))]
+    assert _N().query('asr_ctc_bias_supported', V, R.gld_of(V), 5) == 0
+    ops.set_compute_dtype('bf16')
+    try:
+        xd = torch.from_numpy(x).to(cuda_dev).requires_grad_(True)
+        wd = torch.from_numpy(w).to(cuda_dev).requires_grad_(True)
+        bd = torch.from_numpy(bias).to(cuda_dev).requires_grad_(True)
+        wd.grad = torch.zeros_like(wd)
+        bd.grad = torch.zeros_like(bd)
+        loss, _ = ops.linear_ctc_loss(xd, wd, bd, torch.from_numpy(labels).to(cuda_dev),
+                                      torch.from_numpy(label_lens).to(cuda_dev),
+                                      torch.from_numpy(act_lens).to(cuda_dev), 5,
+                                      loss_scale=1.0 / B)
+        loss.backward()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_compute_dtype('fp32')
+    assert _last_path() == 1                       # the fused head's bf16 gradient, wide form
+    lerr = abs(float(loss.item()) - loss_ref) / abs(loss_ref)
+    got = [xd.grad.cpu().numpy(), wd.grad.cpu().numpy(), bd.grad.cpu().numpy()]
+    errs = [float(np.linalg.norm(g - r) / np.linalg.norm(r)) for g, r in zip(got, refs)]
+    print('\nV=%d fused head bf16 vs float64: loss %.2e, dX %.2e, dW %.2e, db %.2e'
+          % ((V, lerr) + tuple(errs)))
+    assert lerr <= 2e-3, lerr
+    for n, e in zip(('dX', 'dW', 'db'), errs):
+        assert e <= 2e-2, (n, e)
