@@ -138,6 +138,27 @@ int asr_ctc_fwd_bwd(const float* acts, long long stride_t, long long stride_b, i
  * epilogue's partials; gradient: 0 f32 ctc_grad, 1 ctc_grad_bf16, 2 narrow
  * (V <= 256), 3 pipelined, 4 streamed}. */
 int asr_ctc_last_path(int* out2);
+/* Which kernel asr_ctc_backward_bf16 (with_bias 0) or asr_ctc_backward_bf16_db
+ * (with_bias 1) would run for these shapes, and on which grid, under the
+ * current ASR_CTC_* environment switches: the library's own plan, answered on
+ * the host with nothing launched.  acts is looked at for its 16-B alignment
+ * only, never dereferenced.  cus: the CU count to plan for, 0 = the current
+ * device's (only then is a GPU needed).  path is numbered as
+ * asr_ctc_last_path's gradient entry (1 .. 4); nch and aligned are the
+ * kernel's chunks-per-thread and aligned-rows template arguments (nch 0:
+ * the form without bias sums); threads, rpb, nblk: work-group size, rows per
+ * work-group, work-groups; lds_bytes: dynamic LDS per work-group; rev: rows
+ * descending (ASR_CTC_ORDER bit 1); acts_bytes: the activations' extent for
+ * buffer loads (0: plain loads); part_bytes: the nblk column partials at the
+ * head of bias_ws (0 without bias sums).  ASR_ERR_UNSUPPORTED, with the reason
+ * in the error text, where the gradient entry point would refuse. */
+typedef struct {
+  int path, nch, aligned, threads, rpb, nblk, rev, acts_bytes;
+  size_t lds_bytes, part_bytes;
+} asr_ctc_grad_plan_t;
+int asr_ctc_grad_plan(int T, int B, int V, int gld, int max_label_len, const void* acts,
+                      long long stride_t, long long stride_b, int with_bias, int cus,
+                      asr_ctc_grad_plan_t* out);
 /* Waves per direction of the last CTC forward's lattice (round 6): 1 = the
  * one-wave ctc_lattice, 2 / 4 = ctc_lattice_w (ASR_CTC_LATTICE_W=1 forces 1). */
 int asr_ctc_last_lattice_waves(void);

@@ -258,6 +258,8 @@ SIGNATURES = {
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
+    'asr_ctc_grad_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_ll, c_int, c_int,
+                                  c_vp]),
     'asr_ctc_last_lattice_waves': (c_int, []),
     'asr_gemm_last_family': (c_int, []),
     'asr_attdec_conv_feat_bytes': (c_size, [c_vp]),
@@ -332,6 +334,21 @@ class LstmOpts(ctypes.Structure):
 class GemmOpts(ctypes.Structure):
     """asr_gemm_opts_t (one GEMM call's settings; all zero: the defaults)"""
     _fields_ = [('small_tiles', c_int), ('nosplit', c_int), ('n64_kmode', c_int)]
+
+
+class CtcGradPlan(ctypes.Structure):
+    """asr_ctc_grad_plan_t"""
+    _fields_ = [(n, c_int) for n in ('path', 'nch', 'aligned', 'threads', 'rpb', 'nblk', 'rev',
+                                     'acts_bytes')] + [('lds_bytes', c_size), ('part_bytes', c_size)]
+
+
+def ctc_grad_plan(T, B, V, gld, max_label_len, acts_addr, stride_t, stride_b, with_bias, cus=0):
+    """asr_ctc_grad_plan: the gradient pass's plan for these shapes (host only;
+    cus = 0 asks the current device).  Raises NativeError where the pass refuses."""
+    plan = CtcGradPlan()
+    call('asr_ctc_grad_plan', T, B, V, gld, max_label_len, ctypes.c_void_p(acts_addr), stride_t,
+         stride_b, int(bool(with_bias)), cus, ctypes.byref(plan))
+    return plan
 
 
 class AttBeamOpts(ctypes.Structure):

@@ -1740,6 +1740,189 @@ int check_common(const float* acts, int T, int B, int V, const int32_t* labels,
   return ASR_OK;
 }
 
+// The environment A/B switches of this file, read once per
+// call by every public entry point: a test may switch any of them.
+struct CtcSwitches {
+  // ASR_CTC_ORDER (default 2): bit 0 the emission pass, bit 1 the gradient
+  // pass over descending rows.  At V = 10001 the [B][T][V] activations (320
+  // MB) exceed the 256 MB Infinity Cache by little: the gradient pass reading
+  // first the rows the emission pass read last finds part of them still cached.
+  int order;
+  // ASR_CTC_LATTICE_W (default 1) = 2 / 4: the lattice over at most two / four
+  // waves (ctc_lattice_w) -- measured SLOWER at ctc5x512 (B 32 x T 1000, K 4:
+  // forward 195 us one wave, 265 two, 262 four; tools/ctc_lattice_bench.py),
+  // kept as a tested alternative
+  int lattice_w;
+  long long bias_blocks;      // ASR_CTC_BIAS_BLOCKS (<= 0: ctc_bias_rpb's own target)
+  bool narrow, pipe, stream;  // ASR_CTC_GRAD_NARROW / _PIPE / _STREAM: off at "0"
+};
+
+CtcSwitches ctc_switches() {
+  auto num = [](const char* name, long long dflt) {
+    const char* e = getenv(name);
+    return e ? atoll(e) : dflt;
+  };
+  auto on = [](const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+  };
+  return {(int)num("ASR_CTC_ORDER", 2) & 3, (int)num("ASR_CTC_LATTICE_W", 1),
+          num("ASR_CTC_BIAS_BLOCKS", 0), on("ASR_CTC_GRAD_NARROW"), on("ASR_CTC_GRAD_PIPE"),
+          on("ASR_CTC_GRAD_STREAM")};
+}
+
+// Waves per direction of the forward's lattice of K states per lane.
+int ctc_lattice_waves(int K, const CtcSwitches& sw) {
+  return K < 2 || sw.lattice_w <= 1 ? 1 : (sw.lattice_w == 2 || K == 2 ? 2 : 4);
+}
+
+int ctc_cus() {   // CUs of the current device (256 where it cannot be asked)
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+      cus = 256;
+  }
+  return cus;
+}
+
+// Rows per block of a gradient pass that also sums the bias gradient; a
+// block's rows share one partial row of gld f32.  They run one after another,
+// so fewer rows per block hide more latency at the price of partial traffic:
+// at V = 10001, 534 / 1067 / 2134 blocks measured 265 + 13 / 202 + 20 / 185 +
+// 33 us (gradient + column sums).  Narrow heads (V <= 256,
+// ctc_grad_bf16_narrow): 4 rows per work-group, one per wave (a row is a chain
+// of ~3 dependent memory round trips, so rows in parallel, not in sequence: 16
+// rows per work-group measured 54 us at 32000 rows).
+int ctc_bias_rpb(long long rows, int V, const CtcSwitches& sw) {
+  const long long target =
+      sw.bias_blocks > 0 ? sw.bias_blocks : V <= 256 ? (rows + 3) / 4 : 1024;
+  return (int)std::min<long long>(std::max<long long>(rows / target, 1), 64);
+}
+
+inline size_t ctc_part_bytes(int nblk, int gld) {   // the column partials, padded
+  return align256((size_t)nblk * gld * sizeof(float));
+}
+
+// Which bf16 gradient kernel runs, on which grid (asr_hip.h describes the
+// fields): a pure function of the shapes, the activations' alignment, the
+// switches and the CU count.  path 0: refused, for the reason named.
+struct CtcGradPlan : asr_ctc_grad_plan_t {
+  const char* refused;
+};
+
+CtcGradPlan ctc_grad_plan(int T, int B, int V, int gld, int max_label_len, const void* acts,
+                          long long stride_t, long long stride_b, bool bias,
+                          const CtcSwitches& sw, int cus) {
+  CtcGradPlan p = {};
+  auto refuse = [&p](const char* why) {
+    p.refused = why;
+    return p;
+  };
+  if (V <= 1 || gld < V) return refuse("gld below V");
+  if (max_label_len < 0 || 2 * max_label_len + 1 > 64 * kMaxK)
+    return refuse("labels beyond the lattice's 64 * kMaxK states");
+  const long long rows = (long long)B * T;
+  const int Spad = 64 * pick_k(max_label_len);
+  const int n8 = gld >> 3;
+  const bool table = V <= 256;
+  p.threads = table ? 64 : 256;  // compact mode: Spad <= 1024 = 4 * threads
+  p.rev = (sw.order >> 1) & 1;
+  // aligned 16-B buffer loads of the activation rows (compact form) when the
+  // activations are one dense [B][T][V] or [T][B][V] block below 2 GiB
+  // (or [B][T] rows of a padded pitch >= V: the fused heads' logits); the
+  // buffer's extent ends with the last row.  aligned: every row 16-B aligned
+  const long long nb =
+      stride_t >= 0 && stride_b >= 0
+          ? 4LL * ((long long)(B - 1) * stride_b + (long long)(T - 1) * stride_t + V)
+          : 0;
+  const bool dense = (stride_t == V && stride_b == (long long)T * V) ||
+                     (stride_b == V && stride_t == (long long)B * V) ||
+                     (stride_t >= V && stride_b == (long long)T * stride_t);
+  p.acts_bytes =
+      !table && dense && nb > 0 && nb < 0x7fffff00LL && ((uintptr_t)acts & 15) == 0 ? (int)nb : 0;
+  p.aligned = p.acts_bytes && stride_t % 4 == 0 && stride_b % 4 == 0;
+  p.rpb = 1;
+  if (bias) {
+    // chunks per thread of the passes that sum the bias gradient (ctc_grad_bf16
+    // / _pipe; the one-wave table form is built with 1 only); a wide head keeps
+    // its class table [V] beside the two [Spad] state arrays in the 64 KiB of
+    // LDS a work-group gets -- V <= 16256 at Spad 64, V <= 14336 at Spad 1024.
+    // (Every width the streamed pass takes, gld <= 12288, passes: no [V] table.)
+    const int nch = (n8 + p.threads - 1) / p.threads;
+    if (nch > 8)
+      return refuse("too wide for the in-kernel bias sums: more than 8 chunks per thread");
+    if (!table && (size_t)(2 * Spad + V) * 4 > 64 * 1024)
+      return refuse("too wide for the in-kernel bias sums: the class table beyond 64 KiB of LDS");
+    p.nch = table || nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 5 ? 5 : 8;
+    p.rpb = ctc_bias_rpb(rows, V, sw);
+  }
+  p.nblk = ceil_div(rows, p.rpb);
+  p.lds_bytes = (size_t)(table ? V : 2 * Spad + (bias ? V : 0)) * sizeof(float);
+  p.path = 1;
+  const int nchs = (n8 + 511) / 512;
+  if (table && sw.narrow) {
+    // narrow heads: four waves per work-group on rows of their own
+    p.path = 2;
+    p.nch = 1;
+    p.threads = 256;
+    if (!bias) p.rpb = 4;
+    p.nblk = ceil_div(rows, p.rpb);
+    p.lds_bytes = (size_t)(4 * V + (bias ? 4 * gld : 0)) * sizeof(float);
+  } else if (p.aligned && !table && nchs <= 3 && sw.stream) {   // NCH 4 spills at 128 VGPRs
+    // the streamed pass: 512 threads, 2 work-groups per CU, each on a run of rows
+    p.path = 4;
+    p.nch = nchs;
+    p.threads = 512;
+    long long nb2 = std::min<long long>(rows, 2LL * cus);
+    if (bias) nb2 = std::min<long long>(nb2, p.nblk);   // the bias workspace holds nblk partials
+    p.rpb = ceil_div(rows, nb2);
+    p.nblk = ceil_div(rows, p.rpb);
+    p.lds_bytes = (size_t)(5 * Spad + n8 + 8) * sizeof(float);
+  } else if (p.aligned && !table && p.nch > 0 && sw.pipe) {
+    p.path = 3;
+  }
+  if (bias) p.part_bytes = ctc_part_bytes(p.nblk, gld);
+  return p;
+}
+
+int ctc_refused(const char* who, const CtcGradPlan& p, int V, int gld, int max_label_len) {
+  set_error("%s: V %d (gld %d, max_label_len %d) refused: %s", who, V, gld, max_label_len,
+            p.refused);
+  return ASR_ERR_UNSUPPORTED;
+}
+
+// What every gradient kernel takes first, and the stream.
+struct CtcGradArgs {
+  const float* acts;
+  long long st, sb;
+  int T, V;
+  const int32_t *labels, *label_lens, *act_lens;
+  int blank, Spad;
+  CtcWs ws;
+  const float* grad_scale;
+  float scale;
+  hipStream_t s;
+};
+
+// Launches one gradient kernel instantiation: the shared arguments, then the
+// kernel family's own, from the gradient pointer on.
+template <typename K, typename... Tail>
+void ctc_launch_grad(K kernel, const CtcGradArgs& a, int nblk, int threads, size_t lds,
+                     Tail... tail) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(threads), lds, a.s, a.acts, a.st, a.sb,
+                     a.T, a.V, a.labels, a.label_lens, a.act_lens, a.ws.offs, a.blank, a.Spad,
+                     a.ws.lse, a.ws.emit, a.ws.alpha, a.ws.beta, a.ws.logp, a.grad_scale, a.scale,
+                     tail...);
+}
+
+template <int NCH>
+auto ctc_grad_wide(bool al) {   // ctc_grad_bf16 for V > 256
+  return al ? ctc_grad_bf16<false, NCH, true> : ctc_grad_bf16<false, NCH, false>;
+}
+
 }  // namespace
 }  // namespace asr
 
@@ -1749,20 +1932,6 @@ extern "C" size_t asr_ctc_workspace_bytes(int T, int B, int V, int max_label_len
   (void)V;
   if (T <= 0 || B <= 0 || max_label_len < 0) return 0;
   return ws_layout(T, B, max_label_len, nullptr, nullptr);
-}
-
-// Row order of the two passes that stream the activations (ASR_CTC_ORDER: bit
-// 0 the emission pass descending, bit 1 the gradient pass descending).  At
-// V = 10001 the [B][T][V] activations (320 MB) exceed the 256 MB Infinity
-// Cache by little: the gradient pass reading first the rows the emission pass
-// read last finds part of them still cached.
-static int ctc_row_order() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ASR_CTC_ORDER");
-    v = e ? (atoi(e) & 3) : 2;
-  }
-  return v;
 }
 
 // Which kernels the last CTC forward / gradient ran (host-side record;
@@ -1795,6 +1964,7 @@ static int ctc_forward_impl(const float* acts, long long stride_t, long long str
   ASR_REQUIRE(!lse_part || nslab == (V + 63) / 64, ASR_ERR_ARG,
               "ctc: %d log-sum-exp slabs for V=%d (need %d)", nslab, V, (V + 63) / 64);
   hipStream_t s = (hipStream_t)stream;
+  const CtcSwitches sw = ctc_switches();
   CtcWs ws;
   ws_layout(T, B, max_label_len, &ws, (char*)workspace);
   const int K = pick_k(max_label_len);
@@ -1818,38 +1988,27 @@ static int ctc_forward_impl(const float* acts, long long stride_t, long long str
   } else if (V > 1024)
     hipLaunchKernelGGL(ctc_emit_wide, dim3((unsigned)rows), dim3(256), 0, s, acts, stride_t,
                        stride_b, T, V, labels_flat, label_lens, act_lens, ws.offs, blank, Spad,
-                       ws.lse, ws.emit, ctc_row_order() & 1);
+                       ws.lse, ws.emit, sw.order & 1);
   else
     hipLaunchKernelGGL(ctc_emit, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, acts, stride_t,
                        stride_b, T, B, V, labels_flat, label_lens, act_lens, ws.offs, blank, Spad,
                        ws.lse, ws.emit);
   ASR_LAUNCH_CHECK();
-#define ASR_CTC_LAT(KK)                                                                        \
-  hipLaunchKernelGGL(ctc_lattice<KK>, dim3(B, 2), dim3(128), 0, s, T, labels_flat, label_lens,  \
-                     act_lens, ws.offs, blank, zero_infinity, ws.emit, ws.alpha, ws.beta,      \
-                     ws.logp, costs)
-#define ASR_CTC_LATW(KK, WW)                                                                   \
-  hipLaunchKernelGGL((ctc_lattice_w<KK, WW>), dim3(B, 2), dim3(64 * (WW + 1)), 0, s, T,         \
-                     labels_flat, label_lens, act_lens, ws.offs, blank, zero_infinity, ws.emit,  \
-                     ws.alpha, ws.beta, ws.logp, costs)
-  // the one-wave kernel by default; ASR_CTC_LATTICE_W=2 / 4: the lattice over
-  // at most two / four waves (ctc_lattice_w) -- measured SLOWER at ctc5x512
-  // (B 32 x T 1000, K 4: forward 195 us one wave, 265 two, 262 four;
-  // tools/ctc_lattice_bench.py), kept as a tested alternative
-  const char* lw = getenv("ASR_CTC_LATTICE_W");
-  const int wmax = lw ? atoi(lw) : 1;
-  const int W = K < 2 || wmax <= 1 ? 1 : (wmax == 2 || K == 2 ? 2 : 4);
+  const int W = ctc_lattice_waves(K, sw);
   g_ctc_last_path[2] = W;
+  auto lattice = [&](auto kernel) {   // ctc_lattice<K>: two waves; ctc_lattice_w<K, W>: W + 1
+    hipLaunchKernelGGL(kernel, dim3(B, 2), dim3(W == 1 ? 128 : 64 * (W + 1)), 0, s, T, labels_flat,
+                       label_lens, act_lens, ws.offs, blank, zero_infinity, ws.emit, ws.alpha,
+                       ws.beta, ws.logp, costs);
+  };
   switch (K) {
-    case 1: ASR_CTC_LAT(1); break;
-    case 2: if (W > 1) ASR_CTC_LATW(2, 2); else ASR_CTC_LAT(2); break;
-    case 4: if (W == 4) ASR_CTC_LATW(4, 4); else if (W == 2) ASR_CTC_LATW(4, 2); else ASR_CTC_LAT(4); break;
-    case 8: if (W == 4) ASR_CTC_LATW(8, 4); else if (W == 2) ASR_CTC_LATW(8, 2); else ASR_CTC_LAT(8); break;
-    case 16: if (W == 4) ASR_CTC_LATW(16, 4); else if (W == 2) ASR_CTC_LATW(16, 2); else ASR_CTC_LAT(16); break;
+    case 1: lattice(ctc_lattice<1>); break;
+    case 2: W > 1 ? lattice(ctc_lattice_w<2, 2>) : lattice(ctc_lattice<2>); break;
+    case 4: W == 4 ? lattice(ctc_lattice_w<4, 4>) : W == 2 ? lattice(ctc_lattice_w<4, 2>) : lattice(ctc_lattice<4>); break;
+    case 8: W == 4 ? lattice(ctc_lattice_w<8, 4>) : W == 2 ? lattice(ctc_lattice_w<8, 2>) : lattice(ctc_lattice<8>); break;
+    case 16: W == 4 ? lattice(ctc_lattice_w<16, 4>) : W == 2 ? lattice(ctc_lattice_w<16, 2>) : lattice(ctc_lattice<16>); break;
     default: set_error("ctc: unsupported K=%d", K); return ASR_ERR_UNSUPPORTED;
   }
-#undef ASR_CTC_LATW
-#undef ASR_CTC_LAT
   ASR_LAUNCH_CHECK();
   prof_end_launch(ASR_PROF_CTC_FWD, pslot, s);
   if (loss_out) {
@@ -1898,79 +2057,52 @@ extern "C" int asr_ctc_backward(const float* acts, long long stride_t, long long
   CtcWs ws;
   ws_layout(T, B, max_label_len, &ws, (char*)workspace);
   const int Spad = 64 * pick_k(max_label_len);
-  const bool table = V <= 256;
-  const int threads = table ? 64 : 256;  // compact mode: Spad <= 1024 = 4 * threads
+  const CtcGradArgs a = {acts,     stride_t,   stride_b, T,    V,  labels_flat, label_lens,
+                         act_lens, blank,      Spad,     ws,   grad_scale, scale, s};
+  const int rows = (int)((long long)B * T), rev = (ctc_switches().order >> 1) & 1;
   // algorithmic HBM bytes: activations read + gradient written
   const int pslot = prof_begin_launch(ASR_PROF_CTC_GRAD, s, 8.0 * (double)V * B * T, V);
   g_ctc_last_path[1] = 0;
-  if (table)
-    hipLaunchKernelGGL(ctc_grad<true>, dim3((unsigned)((long long)B * T)), dim3(threads),
-                       V * sizeof(float), s, acts, stride_t, stride_b, T, V, labels_flat,
-                       label_lens, act_lens, ws.offs, blank, Spad, ws.lse, ws.emit, ws.alpha,
-                       ws.beta, ws.logp, grad_scale, scale, grads, gstride_t, gstride_b,
-                       (ctc_row_order() >> 1) & 1);
-  else
-    hipLaunchKernelGGL(ctc_grad<false>, dim3((unsigned)((long long)B * T)), dim3(threads),
-                       2 * Spad * sizeof(float), s, acts, stride_t, stride_b, T, V, labels_flat,
-                       label_lens, act_lens, ws.offs, blank, Spad, ws.lse, ws.emit, ws.alpha,
-                       ws.beta, ws.logp, grad_scale, scale, grads, gstride_t, gstride_b,
-                       (ctc_row_order() >> 1) & 1);
+  if (V <= 256)   // the class table [V] in LDS, one wave
+    ctc_launch_grad(ctc_grad<true>, a, rows, 64, V * sizeof(float), grads, gstride_t, gstride_b,
+                    rev);
+  else            // compact mode: Spad <= 1024 = 4 * threads
+    ctc_launch_grad(ctc_grad<false>, a, rows, 256, 2 * Spad * sizeof(float), grads, gstride_t,
+                    gstride_b, rev);
   ASR_LAUNCH_CHECK();
   prof_end_launch(ASR_PROF_CTC_GRAD, pslot, s);
   return ASR_OK;
 }
 
-// Output-layer bias gradient of the fused head (asr_ctc_backward_bf16_db):
-// rows per block and blocks of the column-partial pass.
-static void ctc_bias_grid(int T, int B, int V, int* rpb, int* nblk) {
-  const long long rows = (long long)B * T;
-  // partial rows: nblk x gld f32.  A block's rows run one after another, so
-  // fewer rows per block hide more latency at the price of partial traffic:
-  // at V = 10001, 534 / 1067 / 2134 blocks measured 265 + 13 / 202 + 20 /
-  // 185 + 33 us (gradient + column sums).  ASR_CTC_BIAS_BLOCKS: the target (A/B)
-  const char* bb_env = getenv("ASR_CTC_BIAS_BLOCKS");   // per call: the tests switch it
-  const long long env_target = bb_env ? atoll(bb_env) : 0;
-  // narrow heads (V <= 256, ctc_grad_bf16_narrow): 4 rows per work-group, one
-  // per wave (the partials are gld <= 256 columns; a row is a chain of ~3
-  // dependent memory round trips, so rows in parallel, not in sequence: 16
-  // rows per work-group measured 54 us at 32000 rows)
-  const long long target = env_target > 0 ? env_target : V <= 256 ? (rows + 3) / 4 : 1024;
-  long long r = rows / target;
-  if (r < 1) r = 1;
-  if (r > 64) r = 64;
-  *rpb = (int)r;
-  *nblk = (int)((rows + r - 1) / r);
-}
-
-// 8-column chunks per thread of the gradient pass that also sums the bias
-// gradient (the NCH of ctc_grad_bf16 / ctc_grad_bf16_pipe), or 0 where
-// asr_ctc_backward_bf16_db refuses: more than 8 chunks per thread (gld >
-// 16384), or a wide head whose class table [V] beside the two [Spad] state
-// arrays exceeds the 64 KiB of LDS a work-group gets -- V > 16256 at Spad 64,
-// V > 14336 at Spad 1024.  (Every width the streamed pass takes, gld <=
-// 12288, passes: that pass keeps no [V] table, and 2 * 1024 + 12288 fits.)
-static int ctc_bias_nch(int V, int gld, int max_label_len) {
-  if (V <= 1 || gld < V || max_label_len < 0 || 2 * max_label_len + 1 > 64 * kMaxK) return 0;
-  const bool table = V <= 256;
-  const int threads = table ? 64 : 256;
-  const int n8 = gld >> 3;
-  int nch = (n8 + threads - 1) / threads;
-  nch = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 5 ? 5 : nch <= 8 ? 8 : 0;
-  const int Spad = 64 * pick_k(max_label_len);
-  if (!table && (size_t)(2 * Spad + V) * 4 > 64 * 1024) nch = 0;
-  return nch;
-}
-
 extern "C" int asr_ctc_bias_supported(int V, int gld, int max_label_len) {
-  return ctc_bias_nch(V, gld, max_label_len) > 0;
+  return ctc_grad_plan(1, 1, V, gld, max_label_len, nullptr, 0, 0, true, ctc_switches(), 1).path != 0;
+}
+
+// The partials of the largest grid any path takes for these shapes -- the bias
+// grid's: the streamed pass only shrinks it -- and the column sums' own.
+static size_t ctc_bias_ws_bytes(int T, int B, int V, int gld, const CtcSwitches& sw) {
+  const long long rows = (long long)B * T;
+  const int nblk = ceil_div(rows, ctc_bias_rpb(rows, V, sw));
+  return ctc_part_bytes(nblk, gld) + asr_colsum_workspace_bytes(nblk, V);
 }
 
 extern "C" size_t asr_ctc_bias_workspace_bytes(int T, int B, int V, int gld) {
   if (T <= 0 || B <= 0 || V <= 1 || gld < V) return 0;
-  int rpb, nblk;
-  ctc_bias_grid(T, B, V, &rpb, &nblk);
-  const size_t part = ((size_t)nblk * gld * sizeof(float) + 255) & ~(size_t)255;
-  return part + asr_colsum_workspace_bytes(nblk, V);
+  return ctc_bias_ws_bytes(T, B, V, gld, ctc_switches());
+}
+
+extern "C" int asr_ctc_grad_plan(int T, int B, int V, int gld, int max_label_len,
+                                 const void* acts, long long stride_t, long long stride_b,
+                                 int with_bias, int cus, asr_ctc_grad_plan_t* out) {
+  ASR_REQUIRE(out, ASR_ERR_ARG, "ctc_grad_plan: null pointer");
+  ASR_REQUIRE(T > 0 && B > 0 && V > 1 && cus >= 0, ASR_ERR_ARG,
+              "ctc_grad_plan: bad shape T=%d B=%d V=%d or CU count %d", T, B, V, cus);
+  ASR_REQUIRE(gld >= V && gld % 8 == 0, ASR_ERR_ARG, "ctc_grad_plan: gld %d for V %d", gld, V);
+  const CtcGradPlan p = ctc_grad_plan(T, B, V, gld, max_label_len, acts, stride_t, stride_b,
+                                      with_bias != 0, ctc_switches(), cus ? cus : ctc_cus());
+  if (!p.path) return ctc_refused("ctc_grad_plan", p, V, gld, max_label_len);
+  *out = p;
+  return ASR_OK;
 }
 
 static int ctc_backward_bf16_impl(const float* acts, long long stride_t, long long stride_b, int T,
@@ -1989,153 +2121,66 @@ static int ctc_backward_bf16_impl(const float* acts, long long stride_t, long lo
                   ((uintptr_t)grads & 15) == 0,
               ASR_ERR_ARG, "ctc_bf16: gradient rows must be 16-B aligned with gld %d >= V %d", gld,
               V);
+  const CtcSwitches sw = ctc_switches();
+  if (dbias) {
+    const size_t need = ctc_bias_ws_bytes(T, B, V, gld, sw);
+    ASR_REQUIRE(bws && bws_bytes >= need, ASR_ERR_WORKSPACE,
+                "ctc_bf16_db: bias workspace %zu < %zu", bws_bytes, need);
+  }
+  const CtcGradPlan p = ctc_grad_plan(T, B, V, gld, max_label_len, acts, stride_t, stride_b,
+                                      dbias != nullptr, sw, ctc_cus());
+  if (!p.path) return ctc_refused("ctc_bf16_db", p, V, gld, max_label_len);
+  ASR_REQUIRE(p.part_bytes <= bws_bytes, ASR_ERR_WORKSPACE,
+              "ctc_bf16_db: %d partial rows (%zu bytes) beyond the bias workspace %zu", p.nblk,
+              p.part_bytes, bws_bytes);
   hipStream_t s = (hipStream_t)stream;
   CtcWs ws;
   ws_layout(T, B, max_label_len, &ws, (char*)workspace);
-  const int Spad = 64 * pick_k(max_label_len);
-  const bool table = V <= 256;
-  const int threads = table ? 64 : 256;
-  // aligned 16-B buffer loads of the activation rows (compact form) when the
-  // activations are one dense [B][T][V] or [T][B][V] block below 2 GiB
-  // (or [B][T] rows of a padded pitch >= V: the fused heads' logits); the
-  // buffer's extent ends with the last row.  al: every row 16-B aligned
-  const long long nb =
-      stride_t >= 0 && stride_b >= 0
-          ? 4LL * ((long long)(B - 1) * stride_b + (long long)(T - 1) * stride_t + V)
-          : 0;
-  const bool dense = (stride_t == V && stride_b == (long long)T * V) ||
-                     (stride_b == V && stride_t == (long long)B * V) ||
-                     (stride_t >= V && stride_b == (long long)T * stride_t);
-  const int abytes = (!table && dense && nb > 0 && nb < 0x7fffff00LL && ((uintptr_t)acts & 15) == 0)
-                         ? (int)nb : 0;
-  const bool al = abytes && stride_t % 4 == 0 && stride_b % 4 == 0;
+  const CtcGradArgs a = {acts,     stride_t, stride_b, T,  V,          labels_flat, label_lens,
+                         act_lens, blank,    64 * pick_k(max_label_len), ws, grad_scale, scale, s};
+  float* colpart = dbias ? (float*)bws : nullptr;
   const long long rows = (long long)B * T;
-  const int rev = (ctc_row_order() >> 1) & 1;
-  int rpb = 1, nblk = (int)rows, nch = 0;
-  float* colpart = nullptr;
-  if (dbias) {
-    ASR_REQUIRE(bws && bws_bytes >= asr_ctc_bias_workspace_bytes(T, B, V, gld), ASR_ERR_WORKSPACE,
-                "ctc_bf16_db: bias workspace %zu < %zu", bws_bytes,
-                asr_ctc_bias_workspace_bytes(T, B, V, gld));
-    nch = ctc_bias_nch(V, gld, max_label_len);
-    ASR_REQUIRE(nch > 0, ASR_ERR_UNSUPPORTED,
-                "ctc_bf16_db: V %d (gld %d, max_label_len %d) too wide for the in-kernel bias "
-                "sums; asr_ctc_bias_supported says so beforehand",
-                V, gld, max_label_len);
-    ctc_bias_grid(T, B, V, &rpb, &nblk);
-    colpart = (float*)bws;
-  }
   // algorithmic HBM bytes: activations read (4 V) + bf16 gradient written (2 gld) per row
   const int pslot = prof_begin_launch(ASR_PROF_CTC_GRAD, s, (4.0 * V + 2.0 * gld) * B * T, V);
-  const size_t lds = (table ? V : 2 * Spad + (dbias ? V : 0)) * sizeof(float);
-#define ASR_CTC_G16A(TB, NC, A)                                                                  \
-  hipLaunchKernelGGL((ctc_grad_bf16<TB, NC, A>), dim3((unsigned)nblk), dim3(threads), lds, s,     \
-                     acts, stride_t, stride_b, T, V, labels_flat, label_lens, act_lens, ws.offs,  \
-                     blank, Spad, ws.lse, ws.emit, ws.alpha, ws.beta, ws.logp, grad_scale, scale, \
-                     grads, gstride_t, gstride_b, gld, rev, abytes, colpart, rpb, rows)
-#define ASR_CTC_G16(TB, NC)                  \
-  do {                                       \
-    if (al) ASR_CTC_G16A(TB, NC, true);      \
-    else ASR_CTC_G16A(TB, NC, false);        \
-  } while (0)
-  // narrow heads: four waves per work-group on rows of their own
-  // (ASR_CTC_GRAD_NARROW=0: ctc_grad_bf16<true>, one wave per work-group)
-  const char* en = getenv("ASR_CTC_GRAD_NARROW");
-  if (table && !(en && en[0] == '0')) {
-    if (!dbias) {
-      rpb = 4;
-      nblk = (int)((rows + 3) / 4);
+  g_ctc_last_path[1] = p.path;
+  auto full = [&](auto kernel) {
+    ctc_launch_grad(kernel, a, p.nblk, p.threads, p.lds_bytes, grads, gstride_t, gstride_b, gld,
+                    p.rev, p.acts_bytes, colpart, p.rpb, rows);
+  };
+  // one case per instantiation the library is built with
+  if (p.path == 2)   // (the narrow kernel takes no acts_bytes)
+    ctc_launch_grad(ctc_grad_bf16_narrow<1>, a, p.nblk, p.threads, p.lds_bytes, grads, gstride_t,
+                    gstride_b, gld, p.rev, colpart, p.rpb, rows);
+  else if (p.path == 4)
+    switch (p.nch) {
+      case 1: full(ctc_grad_bf16_stream<1>); break;
+      case 2: full(ctc_grad_bf16_stream<2>); break;
+      default: full(ctc_grad_bf16_stream<3>); break;
     }
-    const size_t ldsn = (size_t)(4 * V + (dbias ? 4 * gld : 0)) * sizeof(float);
-    g_ctc_last_path[1] = 2;
-    hipLaunchKernelGGL((ctc_grad_bf16_narrow<1>), dim3((unsigned)nblk), dim3(256), ldsn, s, acts,
-                       stride_t, stride_b, T, V, labels_flat, label_lens, act_lens, ws.offs, blank,
-                       Spad, ws.lse, ws.emit, ws.alpha, ws.beta, ws.logp, grad_scale, scale, grads,
-                       gstride_t, gstride_b, gld, rev, colpart, rpb, rows);
-    ASR_LAUNCH_CHECK();
-    prof_end_launch(ASR_PROF_CTC_GRAD, pslot, s);
-    if (dbias) {
-      const size_t part = ((size_t)nblk * gld * sizeof(float) + 255) & ~(size_t)255;
-      rc = asr_colsum_accumulate(colpart, gld, nblk, V, 1.0f, dbias, nullptr, (char*)bws + part,
-                                 bws_bytes - part, stream);
-      if (rc) return rc;
+  else if (p.path == 3)
+    switch (p.nch) {
+      case 1: full(ctc_grad_bf16_pipe<1>); break;
+      case 2: full(ctc_grad_bf16_pipe<2>); break;
+      case 4: full(ctc_grad_bf16_pipe<4>); break;
+      case 5: full(ctc_grad_bf16_pipe<5>); break;
+      default: full(ctc_grad_bf16_pipe<8>); break;
     }
-    return ASR_OK;
-  }
-  const char* ep = getenv("ASR_CTC_GRAD_PIPE");   // 0: the unpipelined pass (A/B)
-  const bool pipe = al && !table && nch > 0 && !(ep && ep[0] == '0');
-  // the streamed pass (512 threads, 2 work-groups per CU): ASR_CTC_GRAD_STREAM=0 (A/B)
-  const char* es = getenv("ASR_CTC_GRAD_STREAM");
-  const int n8s = gld >> 3;
-  const int nchs = (n8s + 511) / 512;
-  if (al && !table && nchs <= 3 && !(es && es[0] == '0')) {   // NCH 4 spills at 128 VGPRs
-    static int cus = 0;
-    if (cus == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus <= 0)
-        cus = 256;
+  else if (V <= 256)
+    p.nch ? full(ctc_grad_bf16<true, 1, false>) : full(ctc_grad_bf16<true, 0, false>);
+  else
+    switch (p.nch) {
+      case 0: full(ctc_grad_wide<0>(p.aligned)); break;
+      case 1: full(ctc_grad_wide<1>(p.aligned)); break;
+      case 2: full(ctc_grad_wide<2>(p.aligned)); break;
+      case 4: full(ctc_grad_wide<4>(p.aligned)); break;
+      case 5: full(ctc_grad_wide<5>(p.aligned)); break;
+      default: full(ctc_grad_wide<8>(p.aligned)); break;
     }
-    long long nb2 = std::min<long long>(rows, 2LL * cus);
-    if (dbias) nb2 = std::min<long long>(nb2, nblk);   // the bias workspace holds nblk partials
-    const long long rp2 = (rows + nb2 - 1) / nb2;
-    rpb = (int)rp2;
-    nblk = (int)((rows + rp2 - 1) / rp2);
-    const size_t lds2 = (size_t)(5 * Spad + n8s + 8) * sizeof(float);
-    g_ctc_last_path[1] = 4;
-#define ASR_CTC_GS(NC)                                                                           \
-  hipLaunchKernelGGL((ctc_grad_bf16_stream<NC>), dim3((unsigned)nblk), dim3(512), lds2, s, acts, \
-                     stride_t, stride_b, T, V, labels_flat, label_lens, act_lens, ws.offs, blank, \
-                     Spad, ws.lse, ws.emit, ws.alpha, ws.beta, ws.logp, grad_scale, scale, grads, \
-                     gstride_t, gstride_b, gld, rev, abytes, colpart, rpb, rows)
-    switch (nchs) {
-      case 1: ASR_CTC_GS(1); break;
-      case 2: ASR_CTC_GS(2); break;
-      default: ASR_CTC_GS(3); break;
-    }
-#undef ASR_CTC_GS
-  } else
-#define ASR_CTC_GP(NC)                                                                           \
-  hipLaunchKernelGGL((ctc_grad_bf16_pipe<NC>), dim3((unsigned)nblk), dim3(threads), lds, s, acts, \
-                     stride_t, stride_b, T, V, labels_flat, label_lens, act_lens, ws.offs, blank, \
-                     Spad, ws.lse, ws.emit, ws.alpha, ws.beta, ws.logp, grad_scale, scale, grads, \
-                     gstride_t, gstride_b, gld, rev, abytes, colpart, rpb, rows)
-  if (pipe) {
-    g_ctc_last_path[1] = 3;
-    switch (nch) {
-      case 1: ASR_CTC_GP(1); break;
-      case 2: ASR_CTC_GP(2); break;
-      case 4: ASR_CTC_GP(4); break;
-      case 5: ASR_CTC_GP(5); break;
-      default: ASR_CTC_GP(8); break;
-    }
-  } else if (table) {
-    g_ctc_last_path[1] = 1;
-    if (nch) ASR_CTC_G16A(true, 1, false);
-    else ASR_CTC_G16A(true, 0, false);
-  } else {
-    g_ctc_last_path[1] = 1;
-    switch (nch) {
-      case 0: ASR_CTC_G16(false, 0); break;
-      case 1: ASR_CTC_G16(false, 1); break;
-      case 2: ASR_CTC_G16(false, 2); break;
-      case 4: ASR_CTC_G16(false, 4); break;
-      case 5: ASR_CTC_G16(false, 5); break;
-      default: ASR_CTC_G16(false, 8); break;
-    }
-  }
-#undef ASR_CTC_G16A
-#undef ASR_CTC_GP
-#undef ASR_CTC_G16
   ASR_LAUNCH_CHECK();
   prof_end_launch(ASR_PROF_CTC_GRAD, pslot, s);
-  if (dbias) {   // fixed-order column sums of the per-block partials, added into dbias
-    const size_t part = ((size_t)nblk * gld * sizeof(float) + 255) & ~(size_t)255;
-    rc = asr_colsum_accumulate(colpart, gld, nblk, V, 1.0f, dbias, nullptr, (char*)bws + part,
-                               bws_bytes - part, stream);
-    if (rc) return rc;
-  }
+  if (dbias)   // fixed-order column sums of the per-block partials, added into dbias
+    return asr_colsum_accumulate(colpart, gld, p.nblk, V, 1.0f, dbias, nullptr,
+                                 (char*)bws + p.part_bytes, bws_bytes - p.part_bytes, stream);
   return ASR_OK;
 }
 

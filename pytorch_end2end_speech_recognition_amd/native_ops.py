@@ -601,16 +601,23 @@ class LinearFn(torch.autograd.Function):
 
 
 def _ctc_forward(logits, st, sb, T, B, V, lse, labels_flat, label_lens, act_lens, max_label_len,
-                 blank, zero_infinity, costs, loss, loss_scale, ws, nbytes):
-    """asr_ctc_forward, or asr_ctc_forward_lse from the head GEMM's partials."""
+                 blank, zero_infinity, loss_scale):
+    """asr_ctc_forward, or asr_ctc_forward_lse from the head GEMM's partials;
+    returns (costs [B], loss [1], ws, nbytes), ws the state the backward reads."""
+    dev = logits.device
+    nbytes = N.query('asr_ctc_workspace_bytes', T, B, V, max_label_len)
+    ws = _ws(nbytes, dev)
+    costs = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
     common = (N.ptr(labels_flat), N.ptr(label_lens), N.ptr(act_lens), int(max_label_len),
               int(blank), int(bool(zero_infinity)), N.ptr(costs), N.ptr(loss), float(loss_scale),
-              N.ptr(ws), nbytes, N.stream_handle(logits.device))
+              N.ptr(ws), nbytes, N.stream_handle(dev))
     if lse is not None:
         N.call('asr_ctc_forward_lse', N.ptr(logits), st, sb, T, B, V, N.ptr(lse), lse.shape[0],
                *common)
     else:
         N.call('asr_ctc_forward', N.ptr(logits), st, sb, T, B, V, *common)
+    return costs, loss, ws, nbytes
 
 
 class LinearCTCFn(torch.autograd.Function):
@@ -645,13 +652,9 @@ class LinearCTCFn(torch.autograd.Function):
                                                 ld=(V + 3) // 4 * 4 if V > 1024 else V)
         assert stage, 'LinearCTCFn needs a staged (bf16) output layer'
         B, T, V = logits.shape
-        nbytes = N.query('asr_ctc_workspace_bytes', T, B, V, max_label_len)
-        ws = _ws(nbytes, logits.device)
-        costs = torch.empty(B, dtype=torch.float32, device=logits.device)
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        _ctc_forward(logits, logits.stride(1), logits.stride(0), T, B, V, lse, labels_flat,
-                     label_lens, act_lens, max_label_len, blank, zero_infinity, costs, loss,
-                     loss_scale, ws, nbytes)
+        costs, loss, ws, nbytes = _ctc_forward(
+            logits, logits.stride(1), logits.stride(0), T, B, V, lse, labels_flat, label_lens,
+            act_lens, max_label_len, blank, zero_infinity, loss_scale)
         ctx.save_for_backward(xo, wo, logits, labels_flat, label_lens, act_lens, ws)
         ctx.meta = (bias, tuple(x.shape), weight, int(max_label_len), int(blank),
                     float(loss_scale), nbytes)
@@ -738,12 +741,9 @@ class LinearCTC32Fn(torch.autograd.Function):
         if B * T > 0:
             run_gemm([gemm_problem(operand(x, 0, rowmap(K)), operand(weight, 0, rowmap(K)),
                                    logits, rowmap(Vp), B * T, V, K, bias=bias)], dev, lse=lse)
-        nbytes = N.query('asr_ctc_workspace_bytes', T, B, V, max_label_len)
-        ws = _ws(nbytes, dev)
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _ctc_forward(logits, Vp, T * Vp, T, B, V, lse, labels_flat, label_lens, act_lens,
-                     max_label_len, blank, zero_infinity, costs, loss, loss_scale, ws, nbytes)
+        costs, loss, ws, nbytes = _ctc_forward(logits, Vp, T * Vp, T, B, V, lse, labels_flat,
+                                               label_lens, act_lens, max_label_len, blank,
+                                               zero_infinity, loss_scale)
         ctx.save_for_backward(x, logits, labels_flat, label_lens, act_lens, ws)
         ctx.meta = (bias, weight, B, T, V, Vp, int(max_label_len), int(blank), float(loss_scale),
                     nbytes)
@@ -2806,14 +2806,9 @@ class CTCLossFn(torch.autograd.Function):
         N.require_device(logits, labels_flat, label_lens, act_lens)
         logits = logits.contiguous()
         B, T, V = logits.shape
-        nbytes = N.query('asr_ctc_workspace_bytes', T, B, V, max_label_len)
-        ws = _ws(nbytes, logits.device)
-        costs = torch.empty(B, dtype=torch.float32, device=logits.device)
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        N.call('asr_ctc_forward', N.ptr(logits), V, T * V, T, B, V, N.ptr(labels_flat),
-               N.ptr(label_lens), N.ptr(act_lens), int(max_label_len), int(blank),
-               int(bool(zero_infinity)), N.ptr(costs), N.ptr(loss), float(loss_scale), N.ptr(ws),
-               nbytes, N.stream_handle(logits.device))
+        costs, loss, ws, nbytes = _ctc_forward(logits, V, T * V, T, B, V, None, labels_flat,
+                                               label_lens, act_lens, max_label_len, blank,
+                                               zero_infinity, loss_scale)
         ctx.save_for_backward(logits, labels_flat, label_lens, act_lens, ws)
         ctx.meta = (int(max_label_len), int(blank), float(loss_scale), nbytes)
         ctx.mark_non_differentiable(costs)

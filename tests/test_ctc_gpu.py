@@ -467,6 +467,12 @@ def test_wide_fused_head_v10001_vs_oracle(prec, cuda_dev):
     N.call('asr_ctc_last_path', ctypes.cast(path, ctypes.c_void_p))
     assert path[0] == 1, list(path)                      # epilogue normaliser
     assert path[1] == (4 if prec == 'bf16' else 0), list(path)
+    if prec == 'bf16':
+        # the host-only plan query names the same kernel; the logits live inside the autograd
+        # function, so their 16-B alignment, pitch V + 3 and gld are assumed here, not observed
+        plan = N.ctc_grad_plan(T, B, V, (V + 7) // 8 * 8, int(label_lens.max()), 0, V + 3,
+                               T * (V + 3), True)
+        assert plan.path == path[1], (plan.path, list(path))
     got = [xd.grad.cpu().numpy(), wd.grad.cpu().numpy(), bd.grad.cpu().numpy()]
     refs = [dx_ref, dw_ref, db_ref]
     names = ['dX', 'dW', 'db']

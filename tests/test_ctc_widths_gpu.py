@@ -118,6 +118,9 @@ def _run(c, P, dev, with_bias=True, expect_refusal=False):
     else:
         N.call('asr_ctc_backward_bf16', *args, st)
     path = _last_path()
+    if not expect_refusal:   # the host-only plan query names the kernel that ran
+        assert N.ctc_grad_plan(T, B, V, gld, mll, logits.data_ptr(), P, T * P,
+                               with_bias).path == path
     torch.cuda.synchronize()
     return dict(costs=costs.cpu().numpy(), loss=float(loss.item()),
                 dy=dy.cpu().numpy().view(np.uint16), dbias=dbias.cpu().numpy(), path=path)
@@ -297,6 +300,8 @@ def test_fused_head_beyond_bias_table_vs_oracle(V, K, cuda_dev):
     finally:
         ops.set_compute_dtype('fp32')
     assert _last_path() == 1                       # the fused head's bf16 gradient, wide form
+    P = (V + 3) // 4 * 4                           # (the logits' pitch; their address is aligned)
+    assert _N().ctc_grad_plan(T, B, V, R.gld_of(V), 5, 0, P, T * P, False).path == 1
     lerr = abs(float(loss.item()) - loss_ref) / abs(loss_ref)
     got = [xd.grad.cpu().numpy(), wd.grad.cpu().numpy(), bd.grad.cpu().numpy()]
     errs = [float(np.linalg.norm(g - r) / np.linalg.norm(r)) for g, r in zip(got, refs)]
