@@ -2581,6 +2581,14 @@ int f32_tile_rows(const asr_gemm_t* g, int nprob) {
 int choose_family(const asr_gemm_t* g, int nprob, int compute_dtype, const CallOpts& o, Params& P,
                   int* mode, int* wg) {
   static_assert(T8 == 256 && BT2 == 256, "resplit256");
+  // An empty sum (C = beta C + bias) goes to the generic kernel: its k loop
+  // runs zero tiles and its loads past K give zeros; the LDS-DMA kernels'
+  // pipelined prologues are not written for a k range with no tile.
+  for (int i = 0; i < nprob; ++i)
+    if (g[i].K == 0) {
+      *mode = 0;
+      return compute_dtype == ASR_DT_BF16 ? ASR_PTAG_GEMM_GEN_BF16 : ASR_PTAG_GEMM_GEN_F32;
+    }
   const int fast = compute_dtype == ASR_DT_BF16 ? fast_modes(g, P) : -1;
   *mode = max(fast, 0);
   if (fast >= 0 && big8_ok(g, nprob, o)) {
