@@ -971,6 +971,49 @@ int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opt
                            long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
                            void* stream);
 
+/* Shallow fusion with an RNN language model: asr_att_beam_decode_ex with every
+ * candidate's score joined by weight * lp_lm(c | g), the f32 log-softmax of the
+ * LM's output logits after the row's prefix g (csrc/att_beam.hip states the
+ * semantics): score = (parent + (1 - lambda) lp_att(c) + lambda delta_ctc +
+ * weight lp_lm(c | g)) + length_penalty.  The candidates stay the min(W, V) best
+ * attention classes of each row; LM class c is attention class c, <eos> included,
+ * and <sos> is the eos index.  The LM is `layers` stacked LSTM layers (torch's
+ * gate rows i, f, g, o) over an embedding: emb [V][Y], w_ih[0] [4H][Y], w_ih[l]
+ * [4H][H] (l > 0), w_hh[l] [4H][H], b_ih[l] / b_hh[l] [4H], w_out [V][H] (tied
+ * weights: the emb pointer, H == Y), b_out [V]; its state starts at zero and
+ * steps at every t >= 0.  The decoder's cell type (ex->cell) is independent of it.
+ * lm null or weight 0: exactly asr_att_beam_decode_ex's launches; else 2 more
+ * launches per step (beam_lm_cell, beam_lm_score) and a select variant in the
+ * plain one's place.  The workspace is asr_att_beam_lm_ws_bytes: that of
+ * asr_att_beam_ctc_ws_bytes (whatever lambda) plus 4 B W layers H floats of LM
+ * state, B W V logits and B W W candidate terms.
+ * ASR_ERR_ARG before any launch: lm->V != opts->V, weight < 0, a null pointer.
+ * ASR_ERR_UNSUPPORTED (nothing launched; asr_att_beam_lm_ws_bytes is 0 for the
+ * first two): layers > ASR_ATT_BEAM_LM_MAX_LAYERS, beam_lm_cell's LDS need
+ * (2 max(Y, H) + H floats) above 64 KiB, cell != ASR_ATT_BEAM_CELL_LSTM (a GRU
+ * LM), and asr_att_beam_decode's own refusals. */
+#define ASR_ATT_BEAM_LM_MAX_LAYERS 4
+typedef struct {
+  int layers, H, Y, V;
+  int cell; /* the LM's cell type: ASR_ATT_BEAM_CELL_LSTM */
+  const float* emb;
+  const float* w_ih[ASR_ATT_BEAM_LM_MAX_LAYERS];
+  const float* w_hh[ASR_ATT_BEAM_LM_MAX_LAYERS];
+  const float* b_ih[ASR_ATT_BEAM_LM_MAX_LAYERS];
+  const float* b_hh[ASR_ATT_BEAM_LM_MAX_LAYERS];
+  const float* w_out;
+  const float* b_out;
+  double weight;
+} asr_att_beam_lm_t;
+size_t asr_att_beam_lm_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
+                                int max_len, const int32_t* lens_host, int lm_layers, int lm_H,
+                                int lm_Y);
+int asr_att_beam_decode_lm(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
+                           const asr_att_beam_ex_t* ex, const asr_att_beam_lm_t* lm,
+                           const float* enc, const float* enc_a, const int32_t* lens,
+                           const float* h0, void* workspace, size_t ws_bytes, long long* tokens,
+                           int32_t* hyp_lens, double* scores, float* aw, void* stream);
+
 /* Test / diagnostics: the attention-step kernel instantiations the last
  * asr_attdec_forward_ex / _backward_ex launched: out4 = {forward conv-channel
  * template (10 or 3; 0 = generic), forward 32-frame chunks per utterance,

@@ -255,6 +255,10 @@ SIGNATURES = {
     'asr_att_beam_ctc_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     'asr_att_beam_decode_ctc': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_att_beam_decode_ex': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
+    'asr_att_beam_lm_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
+                                          c_int, c_int]),
+    'asr_att_beam_decode_lm': (c_int, [c_vp, c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] +
+                               [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
@@ -373,6 +377,16 @@ ATT_BEAM_CELL_GRU = 1
 class AttBeamEx(ctypes.Structure):
     """asr_att_beam_ex_t"""
     _fields_ = [('cell', c_int), ('ctc', c_vp)]
+
+
+ATT_BEAM_LM_MAX_LAYERS = 4
+
+
+class AttBeamLm(ctypes.Structure):
+    """asr_att_beam_lm_t"""
+    _fields_ = [(n, c_int) for n in ('layers', 'H', 'Y', 'V', 'cell')] + [('emb', c_vp)] + [
+        (n, c_vp * ATT_BEAM_LM_MAX_LAYERS) for n in ('w_ih', 'w_hh', 'b_ih', 'b_hh')] + [
+        ('w_out', c_vp), ('b_out', c_vp), ('weight', ctypes.c_double)]
 
 
 ASR_ED_TOKEN = 0

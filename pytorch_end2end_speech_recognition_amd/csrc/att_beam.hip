@@ -97,6 +97,37 @@
 //                       candidate, lanes over frames, a wave log-sum-exp:
 //                       psi(g.c) and delta of the row's min(W, V) candidates
 //   beam_select_ctc (utt)  beam_select with the joint score; hands psi on
+//
+// Shallow fusion with an RNN language model (asr_att_beam_decode_lm, weight =
+// gamma > 0; the host path of the model follows the same contract; gamma == 0 or
+// no LM is the search above, with the launches above):
+//   * label spaces: LM class c is attention class c, <eos> included (an ordinary
+//     LM class); <sos> is the <eos> index.
+//   * candidates are still the min(W, V) best ATTENTION classes of each row in
+//     (parent, rank) order: the LM re-ranks the candidates, it nominates none.
+//   * LM state of a row: (h, c) per LM layer (stacked LSTM layers, torch's gate
+//     rows i, f, g, o), zero before step 0.  At EVERY step t >= 0 the row feeds
+//     its last token (<sos> at t = 0) from its PARENT's LM state: the attention
+//     cell takes no step at t = 0, the LM does.
+//   * lp_lm(c | g): the f32 log-softmax (lg - max) - log(sum(exp(lg - max))) of
+//     the LM's output logits W_out h_top + b_out after that step.
+//   * score = (parent score + (1 - lambda) lp_att(c) + lambda delta_ctc +
+//     gamma lp_lm(c | g)) + length_penalty, in double; the CTC term only when
+//     lambda > 0 (else lp_att(c) stands alone).  The tie rules, the
+//     min_decode_len rule, completion and backtracking are unchanged.
+// Added kernels:
+//   beam_lm_cell   (row)  every t, before beam_lm_score: embedding of the row's
+//                       token, then the LM's layers in order inside the
+//                       work-group: [x; h] of the parent row in LDS, one wave per
+//                       hidden unit as beam_cell, a barrier between layers (a
+//                       layer's h is the next one's x).  State [2][R][layers][H],
+//                       double buffered by step parity, read through the parent
+//                       index
+//   beam_lm_score  (row)  after beam_expand: the V output logits, one wave per
+//                       class, to the workspace; max and log-sum; lp_lm of the
+//                       row's min(W, V) candidates to a [row][W] table
+//   beam_select_lm / beam_select_ctc_lm (utt)  beam_select / beam_select_ctc
+//                       with the gamma term
 #include <limits.h>
 
 #include "common.h"
@@ -144,6 +175,21 @@ struct CtcP {
   double *delta, *psic;    // [R][W] per candidate: CTC term, psi(g.c)
 };
 constexpr double kLogZero = -1.0e10;
+
+// the language model's additions (asr_att_beam_decode_lm); its V is p.V
+constexpr int kMaxLmLayers = ASR_ATT_BEAM_LM_MAX_LAYERS;
+struct LmP {
+  int layers, H, Y;
+  double weight;
+  const float* emb;        // [V][Y]
+  const float *w_ih[kMaxLmLayers], *w_hh[kMaxLmLayers];   // [4H][Y or H], [4H][H]
+  const float *b_ih[kMaxLmLayers], *b_hh[kMaxLmLayers];   // [4H]
+  const float *w_out, *b_out;   // [V][H], [V]
+  // workspace
+  float *h, *c;            // [2][R][layers][H] by step parity
+  float *lg;               // [R][V] output logits
+  float *lp;               // [R][W] lp_lm of the row's candidates
+};
 
 __device__ __forceinline__ int utt_len(const BeamP& p, int b) {
   return max(0, min(p.lens[b], p.T));
@@ -440,10 +486,113 @@ __global__ void __launch_bounds__(EXP_THREADS) beam_expand(int t, BeamP p) {
   }
 }
 
+// ----------------------------------------------------------- language model
+constexpr int LM_THREADS = 256;
+
+__host__ __device__ inline size_t lm_cell_lds_floats(int Y, int H) {
+  return 2 * (size_t)(Y > H ? Y : H) + H;
+}
+
+// One step of the LM's stacked LSTM for row i of step t: token and parent from
+// the tables (t == 0: <sos> from the zero state).  xa / xb alternate as a
+// layer's input and output; hp is the parent's h of the layer.
+__global__ void __launch_bounds__(LM_THREADS) beam_lm_cell(int t, BeamP p, LmP m) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
+  const long long R = (long long)p.B * p.W;
+  int par = 0, tok = p.eos;
+  if (t > 0) {
+    const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
+    par = p.par_tab[tab];
+    tok = p.tok_tab[tab];
+  }
+  const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
+  const int cur = t & 1, prev = cur ^ 1;
+  const int H = m.H, XM = max(m.Y, H);
+  float* xa = sm;            // [max(Y, H)]
+  float* xb = xa + XM;       // [max(Y, H)]
+  float* hp = xb + XM;       // [H]
+  for (int y = tid; y < m.Y; y += LM_THREADS) xa[y] = m.emb[(long long)tok * m.Y + y];
+  for (int l = 0; l < m.layers; ++l) {
+    const int in = l == 0 ? m.Y : H;
+    const long long so = ((cur * R + r) * m.layers + l) * H;    // this row's state
+    const long long sp = ((prev * R + pr) * m.layers + l) * H;  // the parent's
+    for (int j = tid; j < H; j += LM_THREADS) hp[j] = t > 0 ? m.h[sp + j] : 0.f;
+    __syncthreads();
+    const float* wi_l = m.w_ih[l];
+    const float* wh_l = m.w_hh[l];
+    for (int u = w; u < H; u += nw) {   // one wave per hidden unit, lanes over K
+      float s[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const long long row = (long long)g * H + u;
+        const float* wi = wi_l + row * in;
+        const float* wh = wh_l + row * H;
+        float a = 0.f;
+        for (int k = lane; k < in; k += 64) a += wi[k] * xa[k];
+        for (int k = lane; k < H; k += 64) a += wh[k] * hp[k];
+        s[g] = wave_sum(a) + m.b_ih[l][row] + m.b_hh[l][row];
+      }
+      if (lane == 0) {
+        const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
+        const float gg = tanhf_(s[2]), og = sigmoidf_(s[3]);
+        const float cn = fg * (t > 0 ? m.c[sp + u] : 0.f) + ig * gg;
+        const float hn = og * tanhf_(cn);
+        m.c[so + u] = cn;
+        m.h[so + u] = hn;
+        xb[u] = hn;
+      }
+    }
+    __syncthreads();         // xb is complete; xa and hp are free
+    float* sw = xa;
+    xa = xb;
+    xb = sw;
+  }
+}
+
+// lp_lm of the row's candidates (beam_expand's topc) from the top layer's h
+__global__ void __launch_bounds__(LM_THREADS) beam_lm_score(int t, BeamP p, LmP m) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
+  const long long R = (long long)p.B * p.W;
+  const long long r = (long long)b * p.W + i;
+  const int cur = t & 1, H = m.H;
+  float* hS = sm;            // [H]
+  float* red = hS + H;       // [4]
+  const float* hs = m.h + (((cur * R + r) * m.layers) + (m.layers - 1)) * H;
+  for (int j = tid; j < H; j += LM_THREADS) hS[j] = hs[j];
+  __syncthreads();
+  float* lg = m.lg + r * p.V;
+  float mx = neg_inf();
+  for (int v = w; v < p.V; v += nw) {      // one wave per class
+    const float* wr = m.w_out + (long long)v * H;
+    float s = 0.f;
+    for (int k = lane; k < H; k += 64) s += wr[k] * hS[k];
+    s = wave_sum(s) + m.b_out[v];
+    if (lane == 0) lg[v] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = block_red(mx, red, true);           // its barriers also publish lg to the work-group
+  float se = 0.f;
+  for (int v = tid; v < p.V; v += LM_THREADS) se += expf(lg[v] - mx);
+  se = block_red(se, red, false);
+  const float lse = logf(se);
+  const int ktop = min(p.W, p.V);
+  for (int k = tid; k < ktop; k += LM_THREADS) {
+    const int c = p.topc[r * p.W + k];
+    m.lp[r * p.W + k] = c >= 0 ? (lg[c] - mx) - lse : 0.f;
+  }
+}
+
 // ----------------------------------------------------------------- select
-// CTC: the joint score, and psi(g.c) of a kept candidate goes on with its row
-template <bool CTC>
-__device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q) {
+// CTC: the joint score, and psi(g.c) of a kept candidate goes on with its row;
+// LM: the candidate's gamma lp_lm(c | g) joins the sum inside the parentheses
+template <bool CTC, bool LM>
+__device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q, const LmP* m) {
   __shared__ double s_score[kMaxBeam * kMaxBeam];
   __shared__ int s_tok[kMaxBeam * kMaxBeam];
   __shared__ double s_selv[kMaxBeam];
@@ -459,7 +608,16 @@ __device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q
     const int tok = p.topc[(r0 + i) * p.W + k];
     const bool drop = tok < 0 || (tok == p.eos && t + 1 < p.min_len);
     s_tok[e] = drop ? -1 : tok;
-    if constexpr (CTC) {
+    if constexpr (LM) {
+      const double gl = tok < 0 ? 0.0 : m->weight * (double)m->lp[(r0 + i) * p.W + k];
+      if constexpr (CTC) {
+        const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[(r0 + i) * p.W + k];
+        s_score[e] = (p.sc[r0 + i] + (1.0 - lam) * (double)p.topv[(r0 + i) * p.W + k] + lam * d +
+                      gl) + p.penalty;
+      } else {
+        s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k] + gl) + p.penalty;
+      }
+    } else if constexpr (CTC) {
       const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[(r0 + i) * p.W + k];
       s_score[e] = (p.sc[r0 + i] + (1.0 - lam) * (double)p.topv[(r0 + i) * p.W + k] + lam * d) +
                    p.penalty;
@@ -530,10 +688,20 @@ __device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q
   }
 }
 
-__global__ void __launch_bounds__(64) beam_select(int t, BeamP p) { select_body<false>(t, p, nullptr); }
+__global__ void __launch_bounds__(64) beam_select(int t, BeamP p) {
+  select_body<false, false>(t, p, nullptr, nullptr);
+}
 
 __global__ void __launch_bounds__(64) beam_select_ctc(int t, BeamP p, CtcP q) {
-  select_body<true>(t, p, &q);
+  select_body<true, false>(t, p, &q, nullptr);
+}
+
+__global__ void __launch_bounds__(64) beam_select_lm(int t, BeamP p, LmP m) {
+  select_body<false, true>(t, p, nullptr, &m);
+}
+
+__global__ void __launch_bounds__(64) beam_select_ctc_lm(int t, BeamP p, CtcP q, LmP m) {
+  select_body<true, true>(t, p, &q, &m);
 }
 
 // ------------------------------------------------------ CTC prefix scoring
@@ -806,6 +974,35 @@ CtcWs ctc_ws(size_t base, int B, int T, int W) {
   return w;
 }
 
+// the language model's part, laid after the joint search's
+struct LmWs {
+  size_t h, c, lg, lp, total;
+};
+
+LmWs lm_ws(size_t base, int B, int W, int V, int layers, int H) {
+  LmWs w;
+  const size_t R = (size_t)B * W;
+  size_t o = base;
+  w.h = o; o += al256(2 * R * layers * H * 4);
+  w.c = o; o += al256(2 * R * layers * H * 4);
+  w.lg = o; o += al256(R * V * 4);
+  w.lp = o; o += al256(R * W * 4);
+  w.total = o;
+  return w;
+}
+
+// the LM's shape limits (its pointers and V are the decode call's to check)
+int lm_check(int layers, int H, int Y) {
+  ASR_REQUIRE(layers >= 1 && H > 0 && Y > 0, ASR_ERR_ARG, "att_beam_lm: bad dims (layers %d, H %d, "
+              "Y %d)", layers, H, Y);
+  ASR_REQUIRE(layers <= kMaxLmLayers, ASR_ERR_UNSUPPORTED, "att_beam_lm: %d LM layers > %d", layers,
+              kMaxLmLayers);
+  const size_t lc = lm_cell_lds_floats(Y, H) * 4;
+  ASR_REQUIRE(lc <= kLdsLimit, ASR_ERR_UNSUPPORTED, "att_beam_lm: LDS need (lm cell %zu B) > %zu B",
+              lc, kLdsLimit);
+  return ASR_OK;
+}
+
 // ASR_OK, or the refusal with its reason in the error text
 int beam_check(const asr_attdec_dims_t& d, int W, int V, int Y, int Dz, int max_len) {
   ASR_REQUIRE(d.B > 0 && d.T > 0 && d.E > 0 && d.A > 0 && d.C > 0 && d.K > 0 && d.D > 0 && V >= 2 &&
@@ -843,10 +1040,20 @@ extern "C" size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W
   return base ? ctc_ws(base, dims->B, dims->T, W).total : 0;
 }
 
+extern "C" size_t asr_att_beam_lm_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y,
+                                           int Dz, int max_len, const int32_t* lens_host,
+                                           int lm_layers, int lm_H, int lm_Y) {
+  const size_t base = asr_att_beam_ctc_ws_bytes(dims, W, V, Y, Dz, max_len, lens_host);
+  if (!base || lm_check(lm_layers, lm_H, lm_Y) != ASR_OK) return 0;
+  return lm_ws(base, dims->B, W, V, lm_layers, lm_H).total;
+}
+
 // ctc == nullptr: the attention-only search, its launches unchanged; cell: which
-// cell kernel steps the rows (ASR_ATT_BEAM_CELL_*), the only difference it makes
+// cell kernel steps the rows (ASR_ATT_BEAM_CELL_*), the only difference it makes;
+// lm == nullptr: no language model, the launches unchanged
 static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                            const asr_att_beam_ctc_t* ctc, int cell, const float* enc,
+                            const asr_att_beam_ctc_t* ctc, const asr_att_beam_lm_t* lm, int cell,
+                            const float* enc,
                             const float* enc_a,
                             const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
                             long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
@@ -879,7 +1086,25 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
                 ASR_ERR_ARG, "att_beam_decode_ctc: Vc = %d, blank = %d, label_offset = %d do not "
                 "fit V = %d, eos = %d", ctc->Vc, ctc->blank, ctc->label_offset, o->V, o->eos);
   }
-  const size_t need = ctc ? cw.total : w.total;
+  LmWs lw = {};
+  if (lm) {
+    ASR_REQUIRE(lm->weight > 0.0, ASR_ERR_ARG, "att_beam_decode_lm: weight = %g is negative",
+                lm->weight);
+    ASR_REQUIRE(lm->V == o->V, ASR_ERR_ARG, "att_beam_decode_lm: the LM has %d classes, the "
+                "decoder %d", lm->V, o->V);
+    const int lrc = lm_check(lm->layers, lm->H, lm->Y);
+    if (lrc) return lrc;
+    ASR_REQUIRE(lm->cell == ASR_ATT_BEAM_CELL_LSTM, ASR_ERR_UNSUPPORTED,
+                "att_beam_decode_lm: only an LSTM language model runs on the device (cell %d)",
+                lm->cell);
+    ASR_REQUIRE(lm->emb && lm->w_out && lm->b_out, ASR_ERR_ARG,
+                "att_beam_decode_lm: null pointer");
+    for (int l = 0; l < lm->layers; ++l)
+      ASR_REQUIRE(lm->w_ih[l] && lm->w_hh[l] && lm->b_ih[l] && lm->b_hh[l], ASR_ERR_ARG,
+                  "att_beam_decode_lm: null pointer (layer %d)", l);
+    lw = lm_ws(cw.total, dims->B, o->W, o->V, lm->layers, lm->H);
+  }
+  const size_t need = lm ? lw.total : ctc ? cw.total : w.total;
   ASR_REQUIRE(ws_bytes >= need, ASR_ERR_WORKSPACE, "att_beam_decode: workspace %zu < %zu bytes",
               ws_bytes, need);
   ASR_REQUIRE(((uintptr_t)workspace & 255) == 0, ASR_ERR_ARG,
@@ -918,6 +1143,20 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
     q.psi = (double*)(base + cw.psi); q.delta = (double*)(base + cw.delta);
     q.psic = (double*)(base + cw.psic);
   }
+  LmP m = {};
+  size_t lds_lmc = 0, lds_lms = 0;
+  if (lm) {
+    m.layers = lm->layers; m.H = lm->H; m.Y = lm->Y; m.weight = lm->weight;
+    m.emb = lm->emb; m.w_out = lm->w_out; m.b_out = lm->b_out;
+    for (int l = 0; l < lm->layers; ++l) {
+      m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l];
+      m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l];
+    }
+    m.h = (float*)(base + lw.h); m.c = (float*)(base + lw.c);
+    m.lg = (float*)(base + lw.lg); m.lp = (float*)(base + lw.lp);
+    lds_lmc = lm_cell_lds_floats(m.Y, m.H) * 4;
+    lds_lms = ((size_t)m.H + 8) * 4;
+  }
   hipLaunchKernelGGL(beam_init, dim3(p.B), dim3(256), 0, s, p);
   ASR_LAUNCH_CHECK();
   if (ctc) {
@@ -938,6 +1177,12 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
     ASR_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_expand, rows, dim3(EXP_THREADS), lds_exp, s, t, p);
     ASR_LAUNCH_CHECK();
+    if (lm) {
+      hipLaunchKernelGGL(beam_lm_cell, rows, dim3(LM_THREADS), lds_lmc, s, t, p, m);
+      ASR_LAUNCH_CHECK();
+      hipLaunchKernelGGL(beam_lm_score, rows, dim3(LM_THREADS), lds_lms, s, t, p, m);
+      ASR_LAUNCH_CHECK();
+    }
     if (ctc) {
       if (t > 0) {
         hipLaunchKernelGGL(beam_ctc_advance, rows, dim3(64), 0, s, t, p, q);
@@ -945,10 +1190,16 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
       }
       hipLaunchKernelGGL(beam_ctc_score, rows, dim3(SCORE_THREADS), 0, s, t, p, q);
       ASR_LAUNCH_CHECK();
-      hipLaunchKernelGGL(beam_select_ctc, dim3(p.B), dim3(64), 0, s, t, p, q);
+      if (lm)
+        hipLaunchKernelGGL(beam_select_ctc_lm, dim3(p.B), dim3(64), 0, s, t, p, q, m);
+      else
+        hipLaunchKernelGGL(beam_select_ctc, dim3(p.B), dim3(64), 0, s, t, p, q);
       ASR_LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL(beam_select, dim3(p.B), dim3(64), 0, s, t, p);
+      if (lm)
+        hipLaunchKernelGGL(beam_select_lm, dim3(p.B), dim3(64), 0, s, t, p, m);
+      else
+        hipLaunchKernelGGL(beam_select, dim3(p.B), dim3(64), 0, s, t, p);
       ASR_LAUNCH_CHECK();
     }
   }
@@ -963,7 +1214,7 @@ extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_
                                    const float* h0, void* workspace, size_t ws_bytes,
                                    long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
                                    void* stream) {
-  return beam_decode_impl(dims, o, nullptr, ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace,
+  return beam_decode_impl(dims, o, nullptr, nullptr, ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace,
                           ws_bytes, tokens, hyp_lens, scores, aw, stream);
 }
 
@@ -974,8 +1225,8 @@ extern "C" int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_
                                        int32_t* hyp_lens, double* scores, float* aw, void* stream) {
   ASR_REQUIRE(ctc, ASR_ERR_ARG, "att_beam_decode_ctc: ctc is null");
   // weight 0 is the attention-only search itself
-  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, ASR_ATT_BEAM_CELL_LSTM, enc,
-                          enc_a, lens, h0, workspace, ws_bytes, tokens, hyp_lens, scores, aw,
+  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, nullptr,
+                          ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace, ws_bytes, tokens, hyp_lens, scores, aw,
                           stream);
 }
 
@@ -987,6 +1238,20 @@ extern "C" int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_a
                                       int32_t* hyp_lens, double* scores, float* aw, void* stream) {
   ASR_REQUIRE(ex, ASR_ERR_ARG, "att_beam_decode_ex: ex is null");
   const asr_att_beam_ctc_t* ctc = (ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
-  return beam_decode_impl(dims, o, ctc, ex->cell, enc, enc_a, lens, h0, workspace, ws_bytes, tokens,
-                          hyp_lens, scores, aw, stream);
+  return beam_decode_impl(dims, o, ctc, nullptr, ex->cell, enc, enc_a, lens, h0, workspace,
+                          ws_bytes, tokens, hyp_lens, scores, aw, stream);
+}
+
+// the search with a language model: lm null or weight 0 is asr_att_beam_decode_ex
+extern "C" int asr_att_beam_decode_lm(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                      const asr_att_beam_ex_t* ex, const asr_att_beam_lm_t* lm,
+                                      const float* enc, const float* enc_a, const int32_t* lens,
+                                      const float* h0, void* workspace, size_t ws_bytes,
+                                      long long* tokens, int32_t* hyp_lens, double* scores,
+                                      float* aw, void* stream) {
+  ASR_REQUIRE(ex, ASR_ERR_ARG, "att_beam_decode_lm: ex is null");
+  const asr_att_beam_ctc_t* ctc = (ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
+  if (lm && lm->weight == 0.0) lm = nullptr;
+  return beam_decode_impl(dims, o, ctc, lm, ex->cell, enc, enc_a, lens, h0, workspace, ws_bytes,
+                          tokens, hyp_lens, scores, aw, stream);
 }

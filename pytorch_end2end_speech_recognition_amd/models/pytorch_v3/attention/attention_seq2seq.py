@@ -525,15 +525,18 @@ class AttentionSeq2seq(ModelBase):
     @torch.no_grad()
     def decode(self, xs, x_lens, beam_width, max_decode_len, min_decode_len=0,
                length_penalty=0, coverage_penalty=0, task_index=0, resolving_unk=False,
-               ctc_weight=0):
+               ctc_weight=0, rnnlm=None, lm_weight=0):
         """:866-915.  Returns (best_hyps int64 [B, T_out], aw [B, T_out, T_in],
         perm_idx), rows in the encoder's length-sorted order like the reference.
         ctc_weight in (0, 1]: one-pass joint CTC/attention beam search, every
         candidate's score (1 - ctc_weight) * attention + ctc_weight * CTC prefix
         term of fc_ctc_0 (csrc/att_beam.hip states the semantics); 0: the
-        attention decoder alone."""
+        attention decoder alone.  rnnlm (lm.rnnlm.RNNLM) with lm_weight > 0:
+        shallow fusion, lm_weight * the LM's log-probability of every candidate
+        added to its score; lm_weight == 0 or rnnlm None: the search without it."""
         dir = 'fwd' if self.fwd_weight_0 >= self.bwd_weight_0 else 'bwd'   # :893
         self._check_ctc_weight(ctc_weight, beam_width, 0, dir)
+        lm_weight = self._check_lm(rnnlm, lm_weight, beam_width, 0, dir)
         self.eval()
         xs_d = self.np2var(xs, dtype='float')
         enc_out, enc_lens_d, _ = self._encode(xs_d, x_lens)
@@ -544,9 +547,30 @@ class AttentionSeq2seq(ModelBase):
             best_hyps, aw = self._decode_infer_beam(enc_out, self.encoder.last_lens_np, beam_width,
                                                     max_decode_len, min_decode_len,
                                                     length_penalty, coverage_penalty, dir=dir,
-                                                    ctc_weight=ctc_weight)
+                                                    ctc_weight=ctc_weight, rnnlm=rnnlm,
+                                                    lm_weight=lm_weight)
         check_recurrences(self)
         return best_hyps, aw, self.encoder.last_perm_np.copy()
+
+    def _check_lm(self, rnnlm, lm_weight, beam_width, task, dir):
+        """The shallow-fusion decode's preconditions, checked before the encoder
+        runs.  Returns the weight in effect (0 without an LM)."""
+        if lm_weight < 0:
+            raise ValueError('lm_weight = %r is negative' % (lm_weight,))
+        if rnnlm is None or lm_weight == 0:
+            return 0
+        if dir != 'fwd':
+            raise NotImplementedError('lm_weight > 0 with the backward decoder: its hypotheses '
+                                      'are reversed, the language model reads left to right')
+        if beam_width <= 1:
+            raise ValueError('lm_weight > 0 needs beam_width > 1: the language model rescores '
+                             'a beam')
+        V = getattr(self, 'eos_%d' % task) + 1
+        if rnnlm.num_classes != V:
+            raise ValueError('rnnlm.num_classes = %d, task %d has %d classes (<eos> included): '
+                             'LM class c must be attention class c'
+                             % (rnnlm.num_classes, task, V))
+        return lm_weight
 
     def _check_ctc_weight(self, ctc_weight, beam_width, task, dir):
         """The joint decode's preconditions, checked before the encoder runs."""
@@ -661,7 +685,7 @@ class AttentionSeq2seq(ModelBase):
 
     def _decode_infer_beam(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
                            length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
-                           _scores=None, ctc_weight=0):
+                           _scores=None, ctc_weight=0, rnnlm=None, lm_weight=0):
         """:1038-1237.  Decoders the fused pass covers and their GRU twins
         (_beam_device_ok) search on the device (native_ops.att_decode_beam,
         csrc/att_beam.hip: no host read inside the step loop); the others,
@@ -672,26 +696,30 @@ class AttentionSeq2seq(ModelBase):
         only); _scores: a list that receives each best hypothesis' score.
         ctc_weight > 0: the joint CTC/attention search on fc_ctc_<task>'s
         logits, on the same two paths (margins and scores are then those of
-        the joint score)."""
+        the joint score).  rnnlm with lm_weight > 0: shallow fusion on the
+        same two paths (a language model the kernels refuse -- a GRU, more
+        than 4 layers -- runs the host path)."""
         if coverage_penalty > 0:
             raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
         self._check_ctc_weight(ctc_weight, beam_width, task, dir)
+        lm_weight = self._check_lm(rnnlm, lm_weight, beam_width, task, dir)
         if (self._beam_device_ok(task, dir) and max_decode_len >= 1
                 and os.environ.get('ASR_ATT_BEAM', 'device') != 'host'):
             out = self._decode_infer_beam_device(enc_out, x_lens, beam_width, max_decode_len,
                                                  min_decode_len, length_penalty, task, dir,
-                                                 _scores, ctc_weight)
+                                                 _scores, ctc_weight, rnnlm, lm_weight)
             if out is not None:
                 ops._set_att_beam_path('device')
                 return out
         ops._set_att_beam_path('host')
         return self._decode_infer_beam_host(enc_out, x_lens, beam_width, max_decode_len,
                                             min_decode_len, length_penalty, coverage_penalty,
-                                            task, dir, _gaps, _scores, ctc_weight)
+                                            task, dir, _gaps, _scores, ctc_weight, rnnlm,
+                                            lm_weight)
 
     def _decode_infer_beam_device(self, enc_out, x_lens, beam_width, max_decode_len,
                                   min_decode_len, length_penalty, task=0, dir='fwd',
-                                  _scores=None, ctc_weight=0):
+                                  _scores=None, ctc_weight=0, rnnlm=None, lm_weight=0):
         """The whole search as one op; None when the kernels refuse the shape.
         One device-to-host copy of the compact results at the end."""
         att = getattr(self, 'attend_%d_%s' % (task, dir))
@@ -718,6 +746,8 @@ class AttentionSeq2seq(ModelBase):
             joint = dict(ctc_logits=self._ctc_logits_f32(enc_out, task), ctc_weight=ctc_weight)
         if dec.rnn_type == 'gru':
             joint['cell'] = 'gru'
+        if rnnlm is not None and lm_weight > 0:
+            joint['lm'] = dict(rnnlm.device_weights(), weight=lm_weight)
         out = ops.att_decode_beam(enc_out, enc_a, lens.astype(np.int32), h0, self._emb_dims[task],
                                   self.sharpening_factor, self.sigmoid_smoothing,
                                   cell.weight_ih, cell.weight_hh, att.W_dec_head0.fc.weight,
@@ -742,7 +772,7 @@ class AttentionSeq2seq(ModelBase):
 
     def _decode_infer_beam_host(self, enc_out, x_lens, beam_width, max_decode_len, min_decode_len,
                                 length_penalty, coverage_penalty, task=0, dir='fwd', _gaps=None,
-                                _scores=None, ctc_weight=0):
+                                _scores=None, ctc_weight=0, rnnlm=None, lm_weight=0):
         """:1038-1237 (any decoding order / decoder depth).  Utterance by utterance like the
         reference, each over its own frames (enc_out[b, :x_len]); the live
         hypotheses of an utterance advance as ONE batch per step on the HIP ops
@@ -757,10 +787,14 @@ class AttentionSeq2seq(ModelBase):
         scores are joint, (1 - ctc_weight) * log-prob + ctc_weight * CTC prefix
         term (ctc_prefix_score.CtcPrefixScorer, numpy doubles on the f32
         log-softmax of fc_ctc_<task>); every hypothesis carries its prefix
-        state."""
+        state.  rnnlm with lm_weight > 0: every hypothesis carries its LM
+        state (row `lmrow` of the step's batch); the live rows advance as one
+        batch through rnnlm.step at every step, t = 0 included, and lm_weight *
+        the f32 log-softmax of its logits joins every candidate's score."""
         if coverage_penalty > 0:
             raise NotImplementedError('coverage penalty (the reference raises too, :1150)')
         self._check_ctc_weight(ctc_weight, beam_width, task, dir)
+        gam = float(self._check_lm(rnnlm, lm_weight, beam_width, task, dir))
         lam = float(ctc_weight)
         ctc_lp = None
         if lam > 0:
@@ -799,11 +833,19 @@ class AttentionSeq2seq(ModelBase):
                 beam[0]['ctc'] = scorer.empty()
             complete, step_aw = [], []
             gap = float('inf')
+            lm_state = None
             for t in range(max_decode_len):
                 n = len(beam)
                 if n == 0:
                     break
                 rows = torch.tensor([c['row'] for c in beam], dtype=torch.long, device=dev)
+                if gam > 0:       # the rows' last tokens from their parents' LM states
+                    if lm_state is not None:
+                        lm_state = tuple([x.index_select(0, rows) for x in v] for v in lm_state)
+                    lm_tok = torch.tensor([c['hyp'][-1] for c in beam], dtype=torch.long,
+                                          device=dev)
+                    lm_lg, lm_state = rnnlm.step(lm_tok, lm_state)
+                    lm_lp = log_softmax_f32(lm_lg.float().cpu().numpy())
                 st = {k: ([x.index_select(0, rows) for x in v] if isinstance(v, list)
                           else v.index_select(0, rows)) for k, v in state.items()}
                 toks = np.array([c['hyp'][-1] for c in beam], np.int64).reshape(n, 1)
@@ -835,17 +877,23 @@ class AttentionSeq2seq(ModelBase):
                         tok = int(order[i, k])
                         if tok == eos and len(beam[i]['hyp']) < min_decode_len:
                             continue
+                        glm = gam * float(lm_lp[i, tok]) if gam > 0 else None
                         if lam > 0:
                             st, g = beam[i]['ctc'], beam[i]['hyp'][1:]
                             psi = None if tok == eos else scorer.psi(st, g, tok)
                             delta = (scorer.eos(st) if tok == eos else psi) - st['psi']
                             new.append(dict(hyp=beam[i]['hyp'] + [tok],
-                                            score=beam[i]['score'] + (1.0 - lam) * float(lp[i, tok])
+                                            score=(beam[i]['score'] + (1.0 - lam) * float(lp[i, tok])
+                                                   + lam * delta + glm + length_penalty)
+                                            if gam > 0 else
+                                            beam[i]['score'] + (1.0 - lam) * float(lp[i, tok])
                                             + lam * delta + length_penalty,
                                             row=i, hist=beam[i]['hist'] + [(t, i)], psi=psi))
                             continue
                         new.append(dict(hyp=beam[i]['hyp'] + [tok],
-                                        score=beam[i]['score'] + float(lp[i, tok]) + length_penalty,
+                                        score=(beam[i]['score'] + float(lp[i, tok]) + glm
+                                               + length_penalty) if gam > 0 else
+                                        beam[i]['score'] + float(lp[i, tok]) + length_penalty,
                                         row=i, hist=beam[i]['hist'] + [(t, i)]))
                 new.sort(key=lambda c: c['score'], reverse=True)     # stable, as sorted()
                 if _gaps is not None:

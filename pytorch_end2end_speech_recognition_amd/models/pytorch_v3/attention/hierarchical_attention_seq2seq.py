@@ -225,16 +225,20 @@ class HierarchicalAttentionSeq2seq(AttentionSeq2seq):
 
     @eval_retry
     def decode(self, xs, x_lens, beam_width, max_decode_len, min_decode_len=0,
-               length_penalty=0, coverage_penalty=0, task_index=0, ctc_weight=0, **kwargs):
+               length_penalty=0, coverage_penalty=0, task_index=0, ctc_weight=0, rnnlm=None, lm_weight=0,
+               **kwargs):
         """:569-648 (greedy or beam search; the joint word/char decodings
         are not provided): task_index 0 decodes words from the top layer, 1
         characters from layer encoder_num_layers_sub.  ctc_weight > 0: joint
         CTC/attention beam search (AttentionSeq2seq.decode); task 1 scores with
-        fc_ctc_1 on the sub-encoder output, task 0 has no CTC head."""
+        fc_ctc_1 on the sub-encoder output, task 0 has no CTC head.  rnnlm with
+        lm_weight > 0: shallow fusion with a language model over the task's
+        classes (AttentionSeq2seq.decode)."""
         import torch
         if kwargs.get('joint_decoding') is not None:
             raise NotImplementedError('joint word/char decoding (:620-880)')
         self._check_ctc_weight(ctc_weight, beam_width, task_index, 'fwd')
+        lm_weight = self._check_lm(rnnlm, lm_weight, beam_width, task_index, 'fwd')
         with torch.no_grad():
             self.eval()
             xs_d = self.np2var(xs, dtype='float')
@@ -250,6 +254,7 @@ class HierarchicalAttentionSeq2seq(AttentionSeq2seq):
                 hyps, aw = self._decode_infer_beam(enc, lens_np, beam_width, max_decode_len,
                                                    min_decode_len, length_penalty,
                                                    coverage_penalty, task=task_index,
-                                                   ctc_weight=ctc_weight)
+                                                   ctc_weight=ctc_weight, rnnlm=rnnlm,
+                                                   lm_weight=lm_weight)
             check_recurrences(self)
             return hyps, aw, self.encoder.last_perm_np.copy()

@@ -1078,7 +1078,7 @@ def _set_att_beam_path(path):
 @torch.no_grad()
 def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh, w_dec, w_conv,
                     conv_w, v, gen, beam_width, max_len, min_len, length_penalty, eos,
-                    ctc_logits=None, ctc_weight=0, cell='lstm'):
+                    ctc_logits=None, ctc_weight=0, cell='lstm', lm=None):
     """Attention beam search on the device (asr_att_beam_decode, csrc/att_beam.hip;
     attention_seq2seq.py:1038-1237, bahdanau order): every utterance over its
     own lens[b] frames, f32 in both compute modes, no host read inside the
@@ -1087,7 +1087,11 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     the raw f32 logits of the CTC head (blank 0, attention class c is CTC class
     c + 1); ctc_weight == 0 is the plain search.  cell: 'lstm' (w_ih [4D, .],
     the calls above), or 'gru' for a GRUCell decoder (w_ih [3D, .], gate rows r,
-    z, n; asr_att_beam_decode_ex, plain or joint).  Returns (tokens int64 [B, max_len],
+    z, n; asr_att_beam_decode_ex, plain or joint).  lm: shallow fusion with a
+    language model (asr_att_beam_decode_lm), a dict of cell ('lstm'; 'gru' is
+    refused: None), weight (>= 0; 0 is the search without it), emb [V, Y], the
+    per-layer lists w_ih / w_hh / b_ih / b_hh, w_out [V, H] and b_out [V], all
+    f32 on the device; an LM of another V raises.  Returns (tokens int64 [B, max_len],
     lengths int32 [B], scores float64 [B], aw float32 [B, max_len, T]) on the
     device, or None when the kernels do not cover the shape
     (ASR_ERR_UNSUPPORTED; the reason is asr_last_error's)."""
@@ -1122,8 +1126,20 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
             raise ValueError('att_decode_beam: ctc_logits %s is not [%d, %d, Vc]'
                              % (tuple(ctc_logits.shape), B, T))
         N.require_device(ctc_logits)
-    nb = N.query('asr_att_beam_ctc_ws_bytes' if lam > 0 else 'asr_att_beam_ws_bytes',
-                 ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz), max_len, None)
+    if lm is not None and float(lm['weight']) < 0:
+        raise ValueError('att_decode_beam: lm weight = %r is negative' % (lm['weight'],))
+    if lm is not None and float(lm['weight']) == 0:
+        lm = None
+    if lm is not None:
+        if lm['cell'] not in ('lstm', 'gru'):
+            raise ValueError("att_decode_beam: lm cell = %r is not 'lstm' or 'gru'" % (lm['cell'],))
+        lm_layers = len(lm['w_ih'])
+        lm_H, lm_Y = int(lm['w_hh'][0].shape[1]), int(lm['emb'].shape[1])
+        nb = N.query('asr_att_beam_lm_ws_bytes', ctypes.byref(dims), W, int(V), int(emb_dim),
+                     int(Dz), max_len, None, lm_layers, lm_H, lm_Y)
+    else:
+        nb = N.query('asr_att_beam_ctc_ws_bytes' if lam > 0 else 'asr_att_beam_ws_bytes',
+                     ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz), max_len, None)
     if nb == 0:
         return None
     ws = _att_beam['ws'].get(dev)
@@ -1145,7 +1161,24 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     h0c = h0.contiguous().float() if h0 is not None else None
     tail = (N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d), N.ptr(h0c), N.ptr(ws), ws.numel(),
             N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw), N.stream_handle(dev))
-    if cell == 'gru':
+    if lm is not None:
+        fn = 'asr_att_beam_decode_lm'
+        nl = N.ATT_BEAM_LM_MAX_LAYERS
+        lk = [[t.contiguous().float() for t in lm[k][:nl]] for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')]
+        lo = [lm[k].contiguous().float() for k in ('emb', 'w_out', 'b_out')]
+        N.require_device(*(lo + [t for ts in lk for t in ts]))
+        arr = lambda ts: (N.c_vp * nl)(*[t.data_ptr() for t in ts])   # noqa: E731
+        lms = N.AttBeamLm(lm_layers, lm_H, lm_Y, int(lo[0].shape[0]),
+                          N.ATT_BEAM_CELL_GRU if lm['cell'] == 'gru' else N.ATT_BEAM_CELL_LSTM,
+                          lo[0].data_ptr(), arr(lk[0]), arr(lk[1]), arr(lk[2]), arr(lk[3]),
+                          lo[1].data_ptr(), lo[2].data_ptr(), float(lm['weight']))
+        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) \
+            if lam > 0 else None
+        ex = N.AttBeamEx(N.ATT_BEAM_CELL_GRU if cell == 'gru' else N.ATT_BEAM_CELL_LSTM,
+                         ctypes.addressof(ctc) if ctc is not None else None)
+        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ex),
+                                  ctypes.byref(lms), *tail)
+    elif cell == 'gru':
         fn = 'asr_att_beam_decode_ex'
         ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) \
             if lam > 0 else None

@@ -21,6 +21,10 @@ convolution, init_dec_state zero, 61 phones + <eos>); (W 4, V 62), (W 10, V 62);
 B, T and max_decode_len as above.  Without it the shapes, the models and the
 output are the ones above.
 
+--lm-weight G > 0: shallow fusion (decode(..., rnnlm=, lm_weight=G)) with a
+random LSTM language model over the same V classes: --lm-layers x --lm-units
+(2 x 512), --lm-embedding (512).  --host_repeats 0 skips the host path.
+
 Writes profiles/att_beam_bench.txt (or --out).
 """
 import argparse
@@ -57,6 +61,10 @@ def main():
     ap.add_argument('--max_decode_len', type=int, default=100)
     ap.add_argument('--ctc-weight', type=float, default=0.0)
     ap.add_argument('--timit', action='store_true')
+    ap.add_argument('--lm-weight', type=float, default=0.0)
+    ap.add_argument('--lm-layers', type=int, default=2)
+    ap.add_argument('--lm-units', type=int, default=512)
+    ap.add_argument('--lm-embedding', type=int, default=512)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('att_beam_bench: needs an MI355X; a CPU run gives no time')
@@ -78,6 +86,9 @@ def main():
              '%d host calls after %d warm-up; ctc_weight %g'
              % (B, T, lens.min(), lens.max(), S, args.repeats, args.host_repeats, args.warmup,
                 args.ctc_weight)]
+    if args.lm_weight > 0:
+        lines[0] += '; lm_weight %g, LSTM LM %d x %d, embedding %d' % (
+            args.lm_weight, args.lm_layers, args.lm_units, args.lm_embedding)
     joint = dict(ctc_loss_weight=0.2) if args.ctc_weight > 0 else {}
     sizes = dict(encoder_type='lstm', encoder_num_units=320, decoder_type='lstm',
                  decoder_num_units=320, embedding_dim=64, init_dec_state='first')
@@ -101,17 +112,30 @@ def main():
             model.fc_0_fwd.fc.bias[V - 1] -= 30.0
         model.set_cuda()
         model.eval()
+        lm = {}
+        if args.lm_weight > 0:
+            from pytorch_end2end_speech_recognition_amd.models.pytorch_v3.lm.rnnlm import RNNLM
+            rnnlm = RNNLM(V - 1, args.lm_embedding, 'lstm', False, args.lm_units, args.lm_layers,
+                          0, 0, 0)
+            rnnlm.set_cuda()
+            rnnlm.eval()
+            lm = dict(rnnlm=rnnlm, lm_weight=args.lm_weight)
 
         def run(mode):
             os.environ['ASR_ATT_BEAM'] = mode
             with torch.no_grad():
                 out = model._decode_infer_beam(enc, lens, W, S, 0, 0, 0,
-                                               ctc_weight=args.ctc_weight)
+                                               ctc_weight=args.ctc_weight, **lm)
             assert ops.last_att_beam_path() == mode
             return out
 
         dev_t = _time_ms(lambda: run('device'), args.warmup, args.repeats)
-        host_t = _time_ms(lambda: run('host'), args.warmup, args.host_repeats)
+        if args.host_repeats <= 0:
+            lines.append('W %2d V %5d: device %.1f ms (%.1f .. %.1f)' % ((W, V) + dev_t))
+            del model
+            continue
+        host_t = _time_ms(lambda: run('host'), 0 if args.host_repeats == 1 else args.warmup,
+                          args.host_repeats)
         hd, _ = run('device')
         hh, _ = run('host')
         same = sum(int(np.array_equal(a, b)) for a, b in zip(hd, hh))
