@@ -595,6 +595,34 @@ int asr_ctc_beam_search(const float* logits, long long stride_t, long long strid
 int asr_ctc_beam_rows(const float* logits, long long stride_t, long long stride_b, int T, int B,
                       int V, const int32_t* lens, int blank, int beam_width, int normalize,
                       void* ws, size_t ws_bytes, void* stream);
+/* asr_ctc_beam_search_lm: the prefix search with shallow fusion of an RNN
+ * language model and an insertion bonus (csrc/ctc_beam.hip states the contract
+ * in full).  lm (asr_att_beam_lm_t, declared with asr_att_beam_decode_lm below;
+ * alpha = lm->weight >= 0) has exactly V classes: CTC class c != blank is LM
+ * class c - (c > blank), and LM class V - 1 is <eos>, also the LM's start
+ * token.  The score of a prefix l after t frames is
+ *   log P_ctc,t(l) + alpha sum_i log p_lm(l_i | <eos>, l_<i) + beta |l|,
+ * the beam holds the beam_width best distinct prefixes by it, and after the
+ * last frame the entries are re-ranked with alpha log p_lm(<eos> | l) added;
+ * scores[b] is that value (f32; the LM and every log-softmax run in f32).
+ * lm null or lm->weight == 0: the LM term is absent (beta still applies); with
+ * beta == 0 too the hypotheses are asr_ctc_beam_search's, by other launches.
+ * Launches: 2 + (lm ? 1 : 0) up front, then per frame 2 + (lm ? 1 : 0), then 1;
+ * no host read or synchronisation.  Workspace: asr_ctc_beam_lm_ws_bytes
+ * (lm_layers == 0: no LM), which needs no initialisation.
+ * ASR_ERR_ARG before any launch: asr_ctc_beam_search's refusals, lm->V != V,
+ * weight < 0, beta not finite, a null pointer.  ASR_ERR_UNSUPPORTED (nothing
+ * launched; the workspace query is 0 for the first two): layers >
+ * ASR_ATT_BEAM_LM_MAX_LAYERS, the LM cell's LDS need (2 max(Y, H) + H floats)
+ * above 64 KiB, lm->cell != ASR_ATT_BEAM_CELL_LSTM (a GRU LM). */
+struct asr_att_beam_lm_s;
+size_t asr_ctc_beam_lm_ws_bytes(int T, int B, int V, int beam_width, int lm_layers, int lm_H,
+                                int lm_Y);
+int asr_ctc_beam_search_lm(const float* logits, long long stride_t, long long stride_b, int T,
+                           int B, int V, const int32_t* lens, int blank, int beam_width,
+                           int normalize, const struct asr_att_beam_lm_s* lm, double beta, void* ws,
+                           size_t ws_bytes, int32_t* hyps, int32_t* hyp_lens, float* scores,
+                           void* stream);
 
 /* ------------------------------------------------------ hypothesis scoring
  * asr_edit_distance: per utterance pair the edit distance between a decoded
@@ -993,7 +1021,7 @@ int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opt
  * (2 max(Y, H) + H floats) above 64 KiB, cell != ASR_ATT_BEAM_CELL_LSTM (a GRU
  * LM), and asr_att_beam_decode's own refusals. */
 #define ASR_ATT_BEAM_LM_MAX_LAYERS 4
-typedef struct {
+typedef struct asr_att_beam_lm_s {
   int layers, H, Y, V;
   int cell; /* the LM's cell type: ASR_ATT_BEAM_CELL_LSTM */
   const float* emb;

@@ -136,6 +136,10 @@ SIGNATURES = {
                                     c_int, c_vp, c_size, c_vp, c_vp, c_vp, c_vp]),
     'asr_ctc_beam_rows': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                   c_vp, c_size, c_vp]),
+    'asr_ctc_beam_lm_ws_bytes': (c_size, [c_int] * 7),
+    'asr_ctc_beam_search_lm': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                       c_int, c_vp, ctypes.c_double, c_vp, c_size, c_vp, c_vp,
+                                       c_vp, c_vp]),
     'asr_edit_distance_ws_bytes': (c_size, [c_int, c_int, c_int]),
     'asr_edit_distance': (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp,
                                   c_vp, c_vp, c_vp, c_size, c_vp]),

@@ -30,6 +30,45 @@
 // entries before extensions; stays by their rank in the previous beam;
 // extensions by the parent's rank, then by the class's place in the frame's
 // (value descending, class ascending) list.
+//
+// With a language model and an insertion bonus (asr_ctc_beam_search_lm) -- the
+// contract; alpha == 0 and beta == 0 at the public interface is the search
+// above, by the launches above:
+//   * inputs: logits or log-probabilities [B, T, V], lens, blank, W in [1, 64];
+//     alpha >= 0 and beta, any finite float; an LM with exactly V classes,
+//     <eos> included.  CTC class c != blank is LM class c - (c > blank); LM
+//     <eos> is class V - 1 and is also the LM's start token.  With blank = 0 this
+//     is the - 1 shift CTC.decode applies, so LM class c is the class decode()
+//     returns, and the attention models' class c.
+//   * score of a prefix l after t frames:
+//       S_t(l) = log P_ctc,t(l) + alpha sum_i log p_lm(l_i | <eos>, l_<i) + beta |l|
+//     with P_ctc,t = p_b + p_nb.  Every alignment of l crosses the edge
+//     l_<i -> l_<=i exactly once, so the LM and bonus terms are added on the
+//     extension edge and ride inside p_b / p_nb; stays and merges need no other
+//     change.  An extension that equals a beam entry merges into that entry's
+//     p_nb, as above, and carries its own parent's LM term.
+//   * the beam after frame t holds the W best distinct prefixes by S_t; after
+//     the last frame the entries are re-ranked by S_T(l) + alpha log
+//     p_lm(<eos> | l), and that value is the returned score, in f32.  The LM
+//     runs in f32 in both compute modes; all log-softmaxes, acoustic and LM, are
+//     f32.
+//   * candidate pruning: per parent p the W + 1 best non-blank classes by
+//     lp_t[c] + alpha q_p[c] suffice (q_p: p's cached LM log-softmax row; value
+//     descending, class ascending).  An extension of p scores that value + beta
+//     + base_p; at most one class per parent is the repeat, whose base p_b is
+//     below the total, so the other W of the list dominate every class below
+//     it: the argument above, per parent.
+//   * order on exactly equal scores, independent of the launch geometry: stays
+//     before extensions; stays by their rank in the previous beam; extensions
+//     by the parent's rank, then by the class's place in that parent's list.
+//   * prefix identity stays depth + hash + confirmed chain walk.  A prefix that
+//     leaves the beam and returns gets its LM state made again from its
+//     parent's: correct by construction.
+// Kernels: the acoustic log-sum-exp of all frames once (beam_rows_kernel, K =
+// 0), lm_init_kernel, the root's LM step; per frame lm_topk_kernel (per entry),
+// lm_select_kernel (per utterance) and, with an LM, lm_step_kernel (per extended
+// entry: LSTM cell from the parent's state, output layer, log-softmax into the
+// entry's row); lm_final_kernel.  No host read, no host synchronisation.
 #include <limits.h>
 
 #include "common.h"
@@ -354,6 +393,362 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
   }
 }
 
+// ------------------------------------------- the search with a language model
+constexpr int kMaxLmLayers = ASR_ATT_BEAM_LM_MAX_LAYERS;
+constexpr size_t kLdsLimit = 64 * 1024;
+constexpr int LM_THREADS = 256;
+
+struct LmP {
+  // the call
+  const float* logits;
+  long long st, sb;
+  int T, B, V, blank, W;
+  const int32_t* lens;
+  float alpha, beta;
+  int has_lm;                    // 0: no LM term anywhere, q / h / c are not touched
+  // the language model
+  int layers, H, Y;
+  const float* emb;              // [V][Y]
+  const float *w_ih[kMaxLmLayers], *w_hh[kMaxLmLayers];   // [4H][Y or H], [4H][H]
+  const float *b_ih[kMaxLmLayers], *b_hh[kMaxLmLayers];   // [4H]
+  const float *w_out, *b_out;    // [V][H], [V]
+  // workspace
+  const float* lse;              // [B][T]
+  float* topv;                   // [B][W][W + 1] per parent: lp + alpha q, best first
+  int32_t* topc;
+  int32_t *n, *nnodes;           // [B]
+  int32_t *node, *par, *last, *depth, *slot;   // [B][W] the beam between frames
+  float *pb, *pnb;
+  unsigned long long *hash, *phash;
+  int32_t *src, *tok;            // [B][W] lm_step's work: parent slot (-1: zero state), LM token (-1: none)
+  Node* pools;
+  float *h, *c;                  // [B][2W][layers][H] by slot
+  float* q;                      // [B][2W][V] by slot: the LM's log-softmax after the entry's prefix
+};
+
+__host__ __device__ inline size_t lm_cell_lds_floats(int Y, int H) {
+  return 2 * (size_t)(Y > H ? Y : H) + H;
+}
+
+__device__ __forceinline__ int lm_class(int c, int blank) { return c - (c > blank ? 1 : 0); }
+
+// the root: the empty prefix in slot 0, whose LM state lm_step(t = -1) makes
+// from the zero state and <eos>
+__global__ void __launch_bounds__(64) lm_init_kernel(LmP p) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r = (long long)b * p.W;
+  if (lane < p.W) {
+    p.tok[r + lane] = lane == 0 ? p.V - 1 : -1;
+    p.src[r + lane] = -1;
+  }
+  if (lane == 0) {
+    Node* pool = p.pools + (long long)b * ((long long)p.T * p.W + 1);
+    pool[0].parent = 0;
+    pool[0].label = -1;
+    p.n[b] = 1; p.nnodes[b] = 1;
+    p.node[r] = 0; p.par[r] = 0; p.last[r] = -1; p.depth[r] = 0; p.slot[r] = 0;
+    p.pb[r] = 0.f; p.pnb[r] = neg_inf();
+    p.hash[r] = 0; p.phash[r] = 0;
+  }
+}
+
+// Per beam entry (parent) the W + 1 best non-blank classes by lp_t[c] + alpha
+// q_p[c] in the order (value descending, class ascending), as beam_rows_kernel
+// ranks a frame.  WAVES waves share one entry; a block is 4 / WAVES entries.
+template <int WAVES>
+__global__ void __launch_bounds__(256) lm_topk_kernel(int t, LmP p) {
+  __shared__ float shv[4];
+  __shared__ int shi[4];
+  const int tid = WAVES == 1 ? (threadIdx.x & 63) : threadIdx.x;
+  constexpr int NTH = WAVES * 64;
+  const long long e = WAVES == 1 ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x;
+  if (e >= (long long)p.B * p.W) return;  // the waves of one barrier group leave together
+  const int b = (int)(e / p.W), i = (int)(e % p.W);
+  if (t >= min(p.lens[b], p.T) || i >= p.n[b]) return;
+  const float* x = p.logits + (long long)t * p.st + (long long)b * p.sb;
+  const float lse = p.lse[(long long)b * p.T + t];
+  const float* q = p.has_lm ? p.q + ((long long)b * 2 * p.W + p.slot[e]) * p.V : nullptr;
+  const int K = p.W + 1, V = p.V, blank = p.blank;
+  const float alpha = p.alpha;
+
+  float pv = __builtin_huge_valf();
+  int pi = -1;
+  for (int k = 0; k < K; ++k) {
+    float bv = neg_inf();
+    int bi = INT_MAX;
+    for (int v = tid; v < V; v += NTH) {
+      if (v == blank) continue;
+      float xv = x[v] - lse;
+      if (q) xv += alpha * q[lm_class(v, blank)];
+      const bool after = xv < pv || (xv == pv && v > pi);   // false for a NaN
+      if (after) argmax_pair(bv, bi, xv, v);
+    }
+    group_argmax<WAVES>(bv, bi, shv, shi);
+    const bool none = bi == INT_MAX;        // fewer than K eligible classes
+    if (tid == 0) {
+      p.topv[e * K + k] = none ? neg_inf() : bv;
+      p.topc[e * K + k] = none ? -1 : bi;
+    }
+    if (none) { pv = neg_inf(); pi = INT_MAX; } else { pv = bv; pi = bi; }
+  }
+}
+
+// One frame of beam_search_kernel's steps A-E with per-parent class lists and
+// the LM / insertion terms on the extension edge.  The beam lives in global
+// memory between frames.  Every new entry gets its LM slot: a stay keeps its
+// own, an extension takes one that no entry of the previous beam holds (there
+// are 2 W, the previous beam holds at most W), so lm_step reads parents' slots
+// and writes children's without a copy and without a race.
+__global__ void __launch_bounds__(64) lm_select_kernel(int t, LmP p) {
+  __shared__ int s_node[kMaxBeam], s_par[kMaxBeam], s_last[kMaxBeam], s_depth[kMaxBeam];
+  __shared__ int s_slot[kMaxBeam];
+  __shared__ float s_pb[kMaxBeam], s_pnb[kMaxBeam], s_tot[kMaxBeam];
+  __shared__ float s_npb[kMaxBeam], s_npnb[kMaxBeam];
+  __shared__ unsigned long long s_hash[kMaxBeam], s_phash[kMaxBeam];
+  __shared__ int s_used[2 * kMaxBeam], s_free[2 * kMaxBeam];
+  __shared__ unsigned long long s_key[kMaxBeam + kMaxBeam * kMaxTop];
+
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int W = p.W, K = W + 1;
+  if (t >= min(p.lens[b], p.T)) return;
+  Node* pool = p.pools + (long long)b * ((long long)p.T * W + 1);
+  const long long r = (long long)b * W;
+  const int n = p.n[b], nnodes = p.nnodes[b];
+  const float* topv = p.topv + r * K;
+  const int32_t* topc = p.topc + r * K;
+  const float* qb = p.has_lm ? p.q + (long long)b * 2 * W * p.V : nullptr;
+
+  s_used[lane] = 0;
+  s_used[lane + 64] = 0;
+  if (lane < n) {
+    s_node[lane] = p.node[r + lane]; s_par[lane] = p.par[r + lane];
+    s_last[lane] = p.last[r + lane]; s_depth[lane] = p.depth[r + lane];
+    s_slot[lane] = p.slot[r + lane];
+    s_pb[lane] = p.pb[r + lane]; s_pnb[lane] = p.pnb[r + lane];
+    s_hash[lane] = p.hash[r + lane]; s_phash[lane] = p.phash[r + lane];
+  }
+  __syncthreads();
+  if (lane < n) s_used[s_slot[lane]] = 1;
+
+  const float* x = p.logits + (long long)t * p.st + (long long)b * p.sb;
+  const float lse = p.lse[(long long)b * p.T + t];
+  const float lpb = x[p.blank] - lse;
+
+  // A: entry `lane` stays: blank, repeat, and the extension that equals it
+  // (which carries ITS parent's LM term and the bonus)
+  int mpar = -1, my_last = -1;
+  unsigned long long key = 0;
+  if (lane < n) {
+    my_last = s_last[lane];
+    const float pb = s_pb[lane], pnb = s_pnb[lane];
+    const float tot = logaddexp_(pb, pnb);
+    const float npb = tot + lpb;
+    float npnb = neg_inf();
+    if (my_last >= 0) {
+      const float xl = x[my_last] - lse;
+      npnb = pnb + xl;
+      const int dep = s_depth[lane] - 1, par = s_par[lane];
+      const unsigned long long ph = s_phash[lane];
+      for (int j = 0; j < n; ++j) {
+        if (s_depth[j] != dep || s_hash[j] != ph) continue;
+        if (!same_prefix(pool, s_node[j], par, dep)) continue;
+        const float base = s_last[j] == my_last ? s_pb[j] : logaddexp_(s_pb[j], s_pnb[j]);
+        float edge = xl;
+        if (qb) edge += p.alpha * qb[(long long)s_slot[j] * p.V + lm_class(my_last, p.blank)];
+        npnb = logaddexp_(npnb, edge + p.beta + base);
+        mpar = j;
+        break;                // beam entries are distinct prefixes: at most one
+      }
+    }
+    s_tot[lane] = tot;
+    s_npb[lane] = npb;
+    s_npnb[lane] = npnb;
+    key = make_key(logaddexp_(npb, npnb), lane);
+  }
+  s_key[lane] = key;
+  __syncthreads();
+
+  // the slots no entry of this beam holds, in ascending order
+  {
+    const bool f0 = lane < 2 * W && !s_used[lane];
+    const bool f1 = lane + 64 < 2 * W && !s_used[lane + 64];
+    const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (f0) s_free[__popcll(m0 & below)] = lane;
+    if (f1) s_free[__popcll(m0) + __popcll(m1 & below)] = lane + 64;
+  }
+
+  // B: extensions by each parent's W + 1 best non-blank classes
+  for (int e = lane; e < n * K; e += 64) {
+    const int j = e / K;
+    const int c = topc[e];
+    const float base = c == s_last[j] ? s_pb[j] : s_tot[j];
+    s_key[kMaxBeam + e] = c >= 0 ? make_key(topv[e] + p.beta + base, kMaxBeam + e) : 0ull;
+  }
+  __syncthreads();
+  // C: ... except those counted in A
+  if (mpar >= 0)
+    for (int k = 0; k < K; ++k)
+      if (topc[mpar * K + k] == my_last) s_key[kMaxBeam + mpar * K + k] = 0ull;
+  __syncthreads();
+
+  // D: the W best keys, one per round, round r's into lane r
+  const int C = kMaxBeam + n * K;
+  unsigned long long prev = ~0ull, mine = 0ull;
+  int nsel = 0;
+  for (int rd = 0; rd < W; ++rd) {
+    unsigned long long best = 0ull;
+    for (int e = lane; e < C; e += 64) {
+      const unsigned long long k = s_key[e];
+      if (k < prev && k > best) best = k;
+    }
+    best = wave_max_u64(best);
+    if (best == 0ull) break;
+    if (lane == rd) mine = best;
+    prev = best;
+    ++nsel;
+  }
+
+  // E: the new beam, and lm_step's work list
+  const bool sel = lane < nsel;
+  const int idx = sel ? (int)(0xffffffffu - (unsigned)mine) : 0;
+  const bool ext = sel && idx >= kMaxBeam;
+  const unsigned long long emask = __ballot(ext);
+  if (sel && !ext) {
+    p.node[r + lane] = s_node[idx]; p.par[r + lane] = s_par[idx];
+    p.last[r + lane] = s_last[idx]; p.depth[r + lane] = s_depth[idx];
+    p.slot[r + lane] = s_slot[idx];
+    p.pb[r + lane] = s_npb[idx]; p.pnb[r + lane] = s_npnb[idx];
+    p.hash[r + lane] = s_hash[idx]; p.phash[r + lane] = s_phash[idx];
+  }
+  if (ext) {
+    const int e = idx - kMaxBeam;
+    const int j = e / K;
+    const int ord = __popcll(emask & ((1ull << lane) - 1ull));
+    const int e_node = nnodes + ord;
+    const int e_last = topc[e];
+    const unsigned long long e_phash = s_hash[j];
+    pool[e_node].parent = s_node[j];
+    pool[e_node].label = e_last;
+    p.node[r + lane] = e_node; p.par[r + lane] = s_node[j];
+    p.last[r + lane] = e_last; p.depth[r + lane] = s_depth[j] + 1;
+    p.slot[r + lane] = s_free[ord];
+    p.pb[r + lane] = neg_inf(); p.pnb[r + lane] = ord2f((unsigned)(mine >> 32));
+    p.hash[r + lane] = hash_push(e_phash, e_last); p.phash[r + lane] = e_phash;
+    p.src[r + lane] = s_slot[j];
+  }
+  if (lane < W) p.tok[r + lane] = ext ? lm_class(topc[idx - kMaxBeam], p.blank) : -1;
+  if (lane == 0) {
+    p.n[b] = nsel;
+    p.nnodes[b] = nnodes + __popcll(emask);
+  }
+}
+
+// The LM after an extended entry's new token: the stacked LSTM from the
+// parent's slot (beam_lm_cell's arithmetic, csrc/att_beam.hip), then the output
+// layer and its f32 log-softmax into the entry's row of q.  Entries that stayed
+// (most of them, at most frames) leave at once.  t = -1: the root.
+__global__ void __launch_bounds__(LM_THREADS) lm_step_kernel(int t, LmP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  __shared__ float red[4];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (t >= 0 && (t >= min(p.lens[b], p.T) || i >= p.n[b])) return;
+  const long long r = (long long)b * p.W + i;
+  const int tok = p.tok[r];
+  if (tok < 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
+  const int src = p.src[r], dst = p.slot[r];
+  const int H = p.H, XM = max(p.Y, H), V = p.V;
+  float* xa = sm;            // [max(Y, H)]
+  float* xb = xa + XM;       // [max(Y, H)]
+  float* hp = xb + XM;       // [H]
+  for (int y = tid; y < p.Y; y += LM_THREADS) xa[y] = p.emb[(long long)tok * p.Y + y];
+  for (int l = 0; l < p.layers; ++l) {
+    const int in = l == 0 ? p.Y : H;
+    const long long so = (((long long)b * 2 * p.W + dst) * p.layers + l) * H;
+    const long long sp = (((long long)b * 2 * p.W + max(src, 0)) * p.layers + l) * H;
+    for (int j = tid; j < H; j += LM_THREADS) hp[j] = src >= 0 ? p.h[sp + j] : 0.f;
+    __syncthreads();
+    const float* wi_l = p.w_ih[l];
+    const float* wh_l = p.w_hh[l];
+    for (int u = w; u < H; u += nw) {   // one wave per hidden unit, lanes over K
+      float s[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const long long row = (long long)g * H + u;
+        const float* wi = wi_l + row * in;
+        const float* wh = wh_l + row * H;
+        float a = 0.f;
+        for (int k = lane; k < in; k += 64) a += wi[k] * xa[k];
+        for (int k = lane; k < H; k += 64) a += wh[k] * hp[k];
+        s[g] = wave_sum(a) + p.b_ih[l][row] + p.b_hh[l][row];
+      }
+      if (lane == 0) {
+        const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
+        const float gg = tanhf_(s[2]), og = sigmoidf_(s[3]);
+        const float cn = fg * (src >= 0 ? p.c[sp + u] : 0.f) + ig * gg;
+        const float hn = og * tanhf_(cn);
+        p.c[so + u] = cn;
+        p.h[so + u] = hn;
+        xb[u] = hn;
+      }
+    }
+    __syncthreads();         // xb is complete; xa and hp are free
+    float* sw = xa;
+    xa = xb;
+    xb = sw;
+  }
+  // xa: the top layer's h
+  float* q = p.q + ((long long)b * 2 * p.W + dst) * V;
+  float mx = neg_inf();
+  for (int v = w; v < V; v += nw) {        // one wave per class
+    const float* wr = p.w_out + (long long)v * H;
+    float s = 0.f;
+    for (int k = lane; k < H; k += 64) s += wr[k] * xa[k];
+    s = wave_sum(s) + p.b_out[v];
+    if (lane == 0) q[v] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = group_max<4>(mx, red);              // its barriers also publish q to the work-group
+  float se = 0.f;
+  for (int v = tid; v < V; v += LM_THREADS) se += expf(q[v] - mx);
+  se = group_sum<4>(se, red);
+  const float lse = logf(se);
+  for (int v = tid; v < V; v += LM_THREADS) q[v] = (q[v] - mx) - lse;
+}
+
+// After the last frame: the entries re-ranked by S_T + alpha lp_lm(<eos> | l)
+// (ties: the better rank), the best one's labels and that score.
+__global__ void __launch_bounds__(64) lm_final_kernel(LmP p, int32_t* __restrict__ hyps,
+                                                      int32_t* __restrict__ hyp_lens,
+                                                      float* __restrict__ scores) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r = (long long)b * p.W;
+  const int n = p.n[b];
+  float s = neg_inf();
+  unsigned long long key = 0;
+  if (lane < n) {
+    s = logaddexp_(p.pb[r + lane], p.pnb[r + lane]);
+    if (p.has_lm)
+      s += p.alpha * p.q[((long long)b * 2 * p.W + p.slot[r + lane]) * p.V + (p.V - 1)];
+    key = make_key(s, lane);
+  }
+  const unsigned long long best = wave_max_u64(key);
+  if (lane < n && key == best) {           // keys are distinct: one lane
+    const Node* pool = p.pools + (long long)b * ((long long)p.T * p.W + 1);
+    const int d = p.depth[r + lane];
+    int node = p.node[r + lane];
+    int32_t* out = hyps + (long long)b * p.T;
+    for (int k = d - 1; k >= 0; --k) {     // d <= lens[b] <= T
+      const Node nd = pool[node];
+      out[k] = nd.label;
+      node = nd.parent;
+    }
+    hyp_lens[b] = d;
+    scores[b] = s;
+  }
+}
+
 inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 struct BeamWs { size_t lse, topv, topc, pool, total; };
@@ -436,4 +831,167 @@ extern "C" int asr_ctc_beam_rows(const float* logits, long long stride_t, long l
                                  int normalize, void* ws, size_t ws_bytes, void* stream) {
   return beam_launch(logits, stride_t, stride_b, T, B, V, lens, blank, beam_width, normalize, ws,
                      ws_bytes, nullptr, nullptr, nullptr, false, stream);
+}
+
+// ------------------------------------------- the search with a language model
+namespace asr {
+namespace {
+
+struct LmBeamWs {
+  size_t lse, topv, topc, n, nnodes, node, par, last, depth, slot, src, tok, pb, pnb, hash, phash,
+      pool, h, c, q, total;
+};
+
+// layers == 0: no language model, no state and no row cache
+inline LmBeamWs lm_beam_ws(int T, int B, int V, int W, int layers, int H) {
+  LmBeamWs w;
+  const size_t frames = (size_t)B * T, K = (size_t)W + 1, R = (size_t)B * W;
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += align16(bytes); return at; };
+  w.lse = take(frames * sizeof(float));
+  w.topv = take(R * K * sizeof(float));
+  w.topc = take(R * K * sizeof(int32_t));
+  w.n = take((size_t)B * sizeof(int32_t));
+  w.nnodes = take((size_t)B * sizeof(int32_t));
+  w.node = take(R * sizeof(int32_t));
+  w.par = take(R * sizeof(int32_t));
+  w.last = take(R * sizeof(int32_t));
+  w.depth = take(R * sizeof(int32_t));
+  w.slot = take(R * sizeof(int32_t));
+  w.src = take(R * sizeof(int32_t));
+  w.tok = take(R * sizeof(int32_t));
+  w.pb = take(R * sizeof(float));
+  w.pnb = take(R * sizeof(float));
+  w.hash = take(R * sizeof(unsigned long long));
+  w.phash = take(R * sizeof(unsigned long long));
+  w.pool = take((size_t)B * ((size_t)T * W + 1) * sizeof(Node));
+  w.h = take(2 * R * (size_t)layers * H * sizeof(float));
+  w.c = take(2 * R * (size_t)layers * H * sizeof(float));
+  w.q = take(layers > 0 ? 2 * R * (size_t)V * sizeof(float) : 0);
+  w.total = o;
+  return w;
+}
+
+// the LM's shape limits, as asr_att_beam_decode_lm's
+int lm_beam_check(int layers, int H, int Y) {
+  ASR_REQUIRE(layers >= 1 && H > 0 && Y > 0, ASR_ERR_ARG, "ctc_beam_search_lm: bad LM dims (layers "
+              "%d, H %d, Y %d)", layers, H, Y);
+  ASR_REQUIRE(layers <= kMaxLmLayers, ASR_ERR_UNSUPPORTED, "ctc_beam_search_lm: %d LM layers > %d",
+              layers, kMaxLmLayers);
+  const size_t lc = lm_cell_lds_floats(Y, H) * 4;
+  ASR_REQUIRE(lc <= kLdsLimit, ASR_ERR_UNSUPPORTED, "ctc_beam_search_lm: LDS need (lm cell %zu B) "
+              "> %zu B", lc, kLdsLimit);
+  return ASR_OK;
+}
+
+}  // namespace
+}  // namespace asr
+
+extern "C" size_t asr_ctc_beam_lm_ws_bytes(int T, int B, int V, int beam_width, int lm_layers,
+                                           int lm_H, int lm_Y) {
+  if (!beam_args_ok(T, B, V, beam_width)) return 0;
+  if (lm_layers == 0) return lm_beam_ws(T, B, V, beam_width, 0, 0).total;
+  if (lm_beam_check(lm_layers, lm_H, lm_Y) != ASR_OK) return 0;
+  return lm_beam_ws(T, B, V, beam_width, lm_layers, lm_H).total;
+}
+
+extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, long long stride_b,
+                                      int T, int B, int V, const int32_t* lens, int blank,
+                                      int beam_width, int normalize, const asr_att_beam_lm_t* lm,
+                                      double beta, void* ws, size_t ws_bytes, int32_t* hyps,
+                                      int32_t* hyp_lens, float* scores, void* stream) {
+  ASR_REQUIRE(logits && lens && ws && hyps && hyp_lens && scores, ASR_ERR_ARG,
+              "ctc_beam_search_lm: null pointer");
+  ASR_REQUIRE(T > 0 && B > 0, ASR_ERR_ARG, "ctc_beam_search_lm: bad shape");
+  ASR_REQUIRE(V >= 2, ASR_ERR_ARG, "ctc_beam_search_lm: V = %d < 2", V);
+  ASR_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, ASR_ERR_ARG,
+              "ctc_beam_search_lm: beam_width = %d outside [1, %d]", beam_width, kMaxBeam);
+  ASR_REQUIRE(blank >= 0 && blank < V, ASR_ERR_ARG,
+              "ctc_beam_search_lm: blank = %d outside [0, %d)", blank, V);
+  ASR_REQUIRE(beta == beta && fabs(beta) <= 3.0e38, ASR_ERR_ARG,
+              "ctc_beam_search_lm: beta = %g is not finite", beta);
+  if (lm) {
+    ASR_REQUIRE(lm->weight >= 0.0 && lm->weight <= 3.0e38, ASR_ERR_ARG,
+                "ctc_beam_search_lm: weight = %g is negative or not finite", lm->weight);
+    ASR_REQUIRE(lm->V == V, ASR_ERR_ARG, "ctc_beam_search_lm: the LM has %d classes, the CTC "
+                "head %d (blank included; <eos> takes the blank's place)", lm->V, V);
+    const int lrc = lm_beam_check(lm->layers, lm->H, lm->Y);
+    if (lrc != ASR_OK) return lrc;
+    ASR_REQUIRE(lm->cell == ASR_ATT_BEAM_CELL_LSTM, ASR_ERR_UNSUPPORTED,
+                "ctc_beam_search_lm: only an LSTM language model runs on the device (cell %d)",
+                lm->cell);
+    ASR_REQUIRE(lm->emb && lm->w_out && lm->b_out, ASR_ERR_ARG, "ctc_beam_search_lm: null pointer");
+    for (int l = 0; l < lm->layers; ++l)
+      ASR_REQUIRE(lm->w_ih[l] && lm->w_hh[l] && lm->b_ih[l] && lm->b_hh[l], ASR_ERR_ARG,
+                  "ctc_beam_search_lm: null pointer (layer %d)", l);
+    if (lm->weight == 0.0) lm = nullptr;      // the LM term is absent
+  }
+  const int W = beam_width;
+  const LmBeamWs w = lm_beam_ws(T, B, V, W, lm ? lm->layers : 0, lm ? lm->H : 0);
+  ASR_REQUIRE(ws_bytes >= w.total, ASR_ERR_WORKSPACE,
+              "ctc_beam_search_lm: workspace %zu < %zu bytes", ws_bytes, w.total);
+  ASR_REQUIRE(((uintptr_t)ws & 15) == 0, ASR_ERR_ARG,
+              "ctc_beam_search_lm: workspace not 16-B aligned");
+  char* base = (char*)ws;
+  LmP p = {};
+  p.logits = logits; p.st = stride_t; p.sb = stride_b;
+  p.T = T; p.B = B; p.V = V; p.blank = blank; p.W = W; p.lens = lens;
+  p.alpha = lm ? (float)lm->weight : 0.f;
+  p.beta = (float)beta;
+  p.has_lm = lm ? 1 : 0;
+  if (lm) {
+    p.layers = lm->layers; p.H = lm->H; p.Y = lm->Y;
+    p.emb = lm->emb; p.w_out = lm->w_out; p.b_out = lm->b_out;
+    for (int l = 0; l < lm->layers; ++l) {
+      p.w_ih[l] = lm->w_ih[l]; p.w_hh[l] = lm->w_hh[l];
+      p.b_ih[l] = lm->b_ih[l]; p.b_hh[l] = lm->b_hh[l];
+    }
+  }
+  float* lse = (float*)(base + w.lse);
+  p.lse = lse;
+  p.topv = (float*)(base + w.topv); p.topc = (int32_t*)(base + w.topc);
+  p.n = (int32_t*)(base + w.n); p.nnodes = (int32_t*)(base + w.nnodes);
+  p.node = (int32_t*)(base + w.node); p.par = (int32_t*)(base + w.par);
+  p.last = (int32_t*)(base + w.last); p.depth = (int32_t*)(base + w.depth);
+  p.slot = (int32_t*)(base + w.slot); p.src = (int32_t*)(base + w.src);
+  p.tok = (int32_t*)(base + w.tok);
+  p.pb = (float*)(base + w.pb); p.pnb = (float*)(base + w.pnb);
+  p.hash = (unsigned long long*)(base + w.hash); p.phash = (unsigned long long*)(base + w.phash);
+  p.pools = (Node*)(base + w.pool);
+  p.h = (float*)(base + w.h); p.c = (float*)(base + w.c); p.q = (float*)(base + w.q);
+
+  hipStream_t s = (hipStream_t)stream;
+  const long long frames = (long long)B * T;
+  // the acoustic log-sum-exp of every frame, once (K = 0: no class ranking)
+  if (V <= kWaveModeMaxV) {
+    hipLaunchKernelGGL(beam_rows_kernel<1>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s,
+                       logits, stride_t, stride_b, T, B, V, lens, blank, 0, normalize, lse,
+                       (float*)nullptr, (int32_t*)nullptr);
+  } else {
+    hipLaunchKernelGGL(beam_rows_kernel<4>, dim3((unsigned)frames), dim3(256), 0, s, logits,
+                       stride_t, stride_b, T, B, V, lens, blank, 0, normalize, lse,
+                       (float*)nullptr, (int32_t*)nullptr);
+  }
+  ASR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lm_init_kernel, dim3(B), dim3(64), 0, s, p);
+  ASR_LAUNCH_CHECK();
+  const size_t lds_step = lm ? lm_cell_lds_floats(p.Y, p.H) * 4 : 0;
+  if (lm) {
+    hipLaunchKernelGGL(lm_step_kernel, dim3(1, B), dim3(LM_THREADS), lds_step, s, -1, p);
+    ASR_LAUNCH_CHECK();
+  }
+  const long long entries = (long long)B * W;
+  for (int t = 0; t < T; ++t) {
+    if (V <= kWaveModeMaxV)
+      hipLaunchKernelGGL(lm_topk_kernel<1>, dim3((unsigned)((entries + 3) / 4)), dim3(256), 0, s,
+                         t, p);
+    else
+      hipLaunchKernelGGL(lm_topk_kernel<4>, dim3((unsigned)entries), dim3(256), 0, s, t, p);
+    hipLaunchKernelGGL(lm_select_kernel, dim3(B), dim3(64), 0, s, t, p);
+    if (lm) hipLaunchKernelGGL(lm_step_kernel, dim3(W, B), dim3(LM_THREADS), lds_step, s, t, p);
+    ASR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lm_final_kernel, dim3(B), dim3(64), 0, s, p, hyps, hyp_lens, scores);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
 }

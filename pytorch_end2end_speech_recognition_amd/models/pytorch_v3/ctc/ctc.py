@@ -235,19 +235,36 @@ class CTC(ModelBase):
             return logits, lens_d, self.encoder.last_lens_np
         return logits_sub, lens_sub_d, self.encoder.last_lens_sub_np
 
+    def _check_lm(self, rnnlm, lm_weight, insertion_bonus, task):
+        """The LM decode's preconditions, checked before the encoder runs (the
+        LM against the width of the head `task` selects).  Returns (alpha,
+        beta) in effect: alpha is 0 without an LM term."""
+        sub = hasattr(self, 'main_loss_weight') and task == 1
+        V = self.num_classes_sub if sub else self.num_classes
+        BeamSearchDecoder.check_lm(lm_weight, insertion_bonus, rnnlm, V)
+        return float(lm_weight), float(insertion_bonus)
+
     @eval_retry
     @torch.no_grad()
     def decode(self, xs, x_lens, beam_width, max_decode_len=None, min_decode_len=0,
-               length_penalty=0, coverage_penalty=0, task_index=0):
+               length_penalty=0, coverage_penalty=0, task_index=0, rnnlm=None, lm_weight=0,
+               insertion_bonus=0):
         """ctc.py:398-452.  beam_width == 1: device best path; beam_width > 1:
         device prefix beam search on the raw logits (log-softmax fused, no
-        [B, T, V] log-probability tensor).  Returns (best_hyps [B] object array
-        of int arrays, None, perm_idx)."""
+        [B, T, V] log-probability tensor).  lm_weight > 0 (with rnnlm, an RNNLM
+        of the head's width: num_classes labels + <eos>) and insertion_bonus
+        != 0: the prefix search with shallow fusion (csrc/ctc_beam.hip), at any
+        beam_width >= 1; LM class c is the class this method returns.  Returns
+        (best_hyps [B] object array of int arrays, None, perm_idx)."""
+        alpha, beta = self._check_lm(rnnlm, lm_weight, insertion_bonus, task_index)
         self.eval()
         xs_d = self.np2var(xs, dtype='float')
         logits, out_lens_d, _ = self._task_logits(xs_d, x_lens, task_index)
         check_recurrences(self)
-        if beam_width == 1:
+        if alpha != 0 or beta != 0:
+            best_hyps = self._decode_beam_np(logits, out_lens_d, beam_width=beam_width,
+                                             alpha=alpha, beta=beta, normalize=True, rnnlm=rnnlm)
+        elif beam_width == 1:
             best_hyps = self._decode_greedy_np(logits, out_lens_d)
         else:
             best_hyps = self._decode_beam_np(logits, out_lens_d, beam_width=beam_width,
@@ -266,15 +283,22 @@ class CTC(ModelBase):
         (utils.evaluation.edit_distance.ErrorRateMeter; a throw-away token
         meter when None).  Returns the batch's int32 [B, 5] device tensor
         (distance, sub, ins, del, reference units), rows in perm_idx order.
-        decode_kwargs: decode()'s remaining arguments (they do not affect CTC
-        decoding)."""
+        decode_kwargs: decode()'s remaining arguments; rnnlm, lm_weight and
+        insertion_bonus select the LM search as in decode(), the others do not
+        affect CTC decoding."""
         from ....utils.evaluation.edit_distance import ErrorRateMeter, score_decoded
+        alpha, beta = self._check_lm(decode_kwargs.get('rnnlm'), decode_kwargs.get('lm_weight', 0),
+                                     decode_kwargs.get('insertion_bonus', 0), task_index)
         self.eval()
         xs_d = self.np2var(xs, dtype='float')
         logits, out_lens_d, _ = self._task_logits(xs_d, x_lens, task_index)
         check_recurrences(self)
         lens = out_lens_d.to(logits.device).int()
-        if beam_width == 1:
+        if alpha != 0 or beta != 0:
+            hyps, hl, _ = self._decode_beam_np.search(
+                logits, lens, beam_width=beam_width, alpha=alpha, beta=beta, normalize=True,
+                rnnlm=decode_kwargs.get('rnnlm'))
+        elif beam_width == 1:
             hyps, hl = ops.ctc_best_path(logits, lens, 0)
         else:
             hyps, hl, _ = ops.ctc_beam_search(logits, lens, int(beam_width), 0, normalize=True)
@@ -298,11 +322,19 @@ class CTC(ModelBase):
         return self.var2np(probs), np.asarray(lens_np).astype(np.int32).copy(), \
             self.encoder.last_perm_np.copy()
 
-    def decode_from_probs(self, probs, x_lens, beam_width=1, max_decode_len=None):
+    def decode_from_probs(self, probs, x_lens, beam_width=1, max_decode_len=None, rnnlm=None,
+                          lm_weight=0, insertion_bonus=0):
         """ctc.py:504-529.  beam_width == 1 on the host, as the reference;
-        beam_width > 1 on the device, fed log(probs + 1e-10) as it stands."""
+        beam_width > 1 on the device, fed log(probs + 1e-10) as it stands.
+        rnnlm / lm_weight / insertion_bonus as in decode() (the LM against the
+        width of probs)."""
         log_probs = np.log(probs + 1e-10)
-        if beam_width == 1:
+        BeamSearchDecoder.check_lm(lm_weight, insertion_bonus, rnnlm, int(log_probs.shape[-1]))
+        if lm_weight != 0 or insertion_bonus != 0:
+            best = self._decode_beam_np(log_probs, x_lens, beam_width=beam_width,
+                                        alpha=float(lm_weight), beta=float(insertion_bonus),
+                                        rnnlm=rnnlm)
+        elif beam_width == 1:
             best = self._decode_greedy_np(log_probs, x_lens)
         else:
             best = self._decode_beam_np(log_probs, x_lens, beam_width=beam_width)

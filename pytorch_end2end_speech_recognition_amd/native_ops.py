@@ -2922,26 +2922,91 @@ def ctc_best_path(logits, lens, blank=0):
 
 
 _beam_ws = {}    # device -> workspace of the largest ctc_beam_search call so far
+_ctc_beam = {'path': None}
 
 
-def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True):
-    """CTC prefix beam search on device (asr_ctc_beam_search): logits [B, T, V]
-    raw (normalize=True: the log-softmax is fused) or log-probabilities.
-    Returns (hyps int32 [B, T], hyp_lens int32 [B], scores float32 [B])."""
+def last_ctc_beam_path():
+    """Where the last CTC prefix beam search ran (None before the first one):
+    'device' (asr_ctc_beam_search, no LM and no insertion bonus), 'device_lm'
+    (asr_ctc_beam_search_lm) or 'host' (the decoder's numpy search: the kernels
+    refused the LM, or ASR_CTC_BEAM=host)."""
+    return _ctc_beam['path']
+
+
+def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, beta=0.0):
+    """CTC prefix beam search on device: logits [B, T, V] raw (normalize=True:
+    the log-softmax is fused) or log-probabilities.  Returns (hyps int32 [B, T],
+    hyp_lens int32 [B], scores float32 [B]).
+
+    lm is None and beta == 0: asr_ctc_beam_search.  Otherwise
+    asr_ctc_beam_search_lm (csrc/ctc_beam.hip states the contract): lm is
+    RNNLM.device_weights() plus weight (alpha >= 0; 0: the LM term is absent), an
+    LM of exactly V classes (CTC class c != blank is LM class c - (c > blank),
+    <eos> = V - 1), all f32 on the device; beta is the insertion bonus per
+    label.  Returns None when the kernels refuse the LM (ASR_ERR_UNSUPPORTED: a
+    GRU LM, more layers than the limit; the reason is asr_last_error's)."""
     N.require_device(logits, lens)
     logits = logits.contiguous().float()
     B, T, V = logits.shape
     dev = logits.device
+    W, beta = int(beam_width), float(beta)
+    if lm is not None:
+        if float(lm['weight']) < 0:
+            raise ValueError('ctc_beam_search: lm weight = %r is negative' % (lm['weight'],))
+        if lm['cell'] not in ('lstm', 'gru'):
+            raise ValueError("ctc_beam_search: lm cell = %r is not 'lstm' or 'gru'" % (lm['cell'],))
+        if int(lm['emb'].shape[0]) != V or int(lm['w_out'].shape[0]) != V:
+            raise ValueError('ctc_beam_search: the LM has %d classes, the CTC head %d (blank '
+                             'included; <eos> takes its place)' % (lm['w_out'].shape[0], V))
+    if not np.isfinite(beta):
+        raise ValueError('ctc_beam_search: beta = %r is not finite' % (beta,))
     hyps = torch.empty(B, T, dtype=torch.int32, device=dev)
     hl = torch.empty(B, dtype=torch.int32, device=dev)
     scores = torch.empty(B, dtype=torch.float32, device=dev)
-    nb = N.query('asr_ctc_beam_ws_bytes', T, B, V, int(beam_width))
+    lens_d = lens.int().contiguous()
+    if lm is None and beta == 0:
+        nb = N.query('asr_ctc_beam_ws_bytes', T, B, V, W)
+        ws = _beam_ws.get(dev)
+        if ws is None or ws.numel() < nb:
+            ws = _beam_ws[dev] = _ws(nb, dev)
+        N.call('asr_ctc_beam_search', N.ptr(logits), V, T * V, T, B, V, N.ptr(lens_d), int(blank),
+               W, int(bool(normalize)), N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl),
+               N.ptr(scores), N.stream_handle(dev))
+        _ctc_beam['path'] = 'device'
+        return hyps, hl, scores
+    lms, keep = None, None
+    if lm is not None:
+        nl = N.ATT_BEAM_LM_MAX_LAYERS
+        lm_layers = len(lm['w_ih'])
+        lm_H, lm_Y = int(lm['w_hh'][0].shape[1]), int(lm['emb'].shape[1])
+        lk = [[t.contiguous().float() for t in lm[k][:nl]] for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')]
+        lo = [lm[k].contiguous().float() for k in ('emb', 'w_out', 'b_out')]
+        N.require_device(*(lo + [t for ts in lk for t in ts]))
+        keep = (lk, lo)
+        arr = lambda ts: (N.c_vp * nl)(*[t.data_ptr() for t in ts])   # noqa: E731
+        lms = N.AttBeamLm(lm_layers, lm_H, lm_Y, int(lo[0].shape[0]),
+                          N.ATT_BEAM_CELL_GRU if lm['cell'] == 'gru' else N.ATT_BEAM_CELL_LSTM,
+                          lo[0].data_ptr(), arr(lk[0]), arr(lk[1]), arr(lk[2]), arr(lk[3]),
+                          lo[1].data_ptr(), lo[2].data_ptr(), float(lm['weight']))
+        nb = N.query('asr_ctc_beam_lm_ws_bytes', T, B, V, W, lm_layers, lm_H, lm_Y)
+        if nb == 0 and 1 <= W <= 64:
+            return None                  # the LM's shape is outside the kernels' limits
+    else:
+        nb = N.query('asr_ctc_beam_lm_ws_bytes', T, B, V, W, 0, 0, 0)
     ws = _beam_ws.get(dev)
     if ws is None or ws.numel() < nb:
         ws = _beam_ws[dev] = _ws(nb, dev)
-    N.call('asr_ctc_beam_search', N.ptr(logits), V, T * V, T, B, V,
-           N.ptr(lens.int().contiguous()), int(blank), int(beam_width), int(bool(normalize)),
-           N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl), N.ptr(scores), N.stream_handle(dev))
+    rc = N.lib().asr_ctc_beam_search_lm(
+        N.ptr(logits), V, T * V, T, B, V, N.ptr(lens_d), int(blank), W, int(bool(normalize)),
+        N.ptr_struct(lms), beta, N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl), N.ptr(scores),
+        N.stream_handle(dev))
+    del keep
+    if rc == N.ASR_ERR_UNSUPPORTED:
+        return None
+    if rc != N.ASR_OK:
+        raise N.NativeError('asr_ctc_beam_search_lm failed (rc=%d): %s'
+                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
+    _ctc_beam['path'] = 'device_lm'
     return hyps, hl, scores
 
 
