@@ -438,6 +438,43 @@ int asr_gru_backward(const float* dy, const float* whh, const int32_t* lens, int
                      float* act_dgx, const float* ghn, const float* y, float* dgh,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------ unidirectional LSTM layer
+ * Replaces the packed nn.LSTM(bidirectional=False) of
+ * models/pytorch_v3/encoders/rnn.py:166-172 (fast path) / :218-224 (per layer),
+ * the encoder_bidirectional=False form.  Gate order i, f, g, o; h0 = c0 = 0;
+ * outputs and state are 0 for t >= lens[b] (pad_packed's zeros).
+ *   gx_act [B][T][4H] f32: in  x W_ih^T + b_ih + b_hh
+ *                          out i, f, g, o (post-activation, 0 at padded frames),
+ *                          then the pre-activation gate gradients dG after backward
+ *   whh    [4H][H], w_dtype f32 or bf16 (f32 compute needs f32)
+ *   lens   int32 [B];  y, cst [B][T][H] f32 out (h_t, c_t)
+ *   ybf    optional bf16 copy of y;  dgbf optional bf16 copy of dG
+ * Backward: dy [B][T][H] (NULL = 0; values at t >= lens[b] are ignored);
+ * db_ih (required) and db_hh (optional), [4H], are accumulated (+=) with the
+ * column sums of dG, identical values, by a fixed-order reduction: results
+ * are bitwise reproducible.  The weight and input gradients are GEMMs of dG
+ * by the caller.
+ * compute_dtype f32: f32 state, exact-f32 MFMA.  bf16: h (forward) and dG
+ * (backward) rounded to bf16 as MFMA operands beside a bf16 W_hh, f32
+ * accumulation and f32 state.
+ * One launch per time step and pass (product and cell math in one kernel;
+ * only the stream orders the steps), plus one weight conversion / transpose
+ * launch and, in the backward, the two column-sum launches.
+ * Accepted shapes: 1 <= B <= 8192, 1 <= T <= 65536, 1 <= H <= 1024 (H % 8 == 0
+ * takes vector fragment loads, any other H guarded scalar ones).  Any other
+ * positive shape is ASR_ERR_UNSUPPORTED before any launch, nothing written.  workspace: asr_lstm_uni_workspace_bytes(B, H,
+ * compute_dtype, backward != 0); it need not be zero.
+ * asr_lstm_uni_shape_ok: 1 for an accepted shape, else 0 (host only). */
+int asr_lstm_uni_shape_ok(int B, int T, int H);
+size_t asr_lstm_uni_workspace_bytes(int B, int H, int compute_dtype, int backward);
+int asr_lstm_uni_forward(float* gx_act, const void* whh, int w_dtype, const int32_t* lens, int B,
+                         int T, int H, int compute_dtype, float* y, float* cst, uint16_t* ybf,
+                         void* workspace, size_t ws_bytes, void* stream);
+int asr_lstm_uni_backward(const float* dy, const void* whh, int w_dtype, const int32_t* lens, int B,
+                          int T, int H, int compute_dtype, float* act_dg, const float* cst,
+                          uint16_t* dgbf, float* db_ih, float* db_hh, void* workspace,
+                          size_t ws_bytes, void* stream);
+
 /* nn.GRUCell nonlinearity (decoder cells, rnn_decoder.py:91-95): gi = x W_ih^T +
  * b_ih, gh = h W_hh^T + b_hh [B][3D] (GEMMs by the caller); act [B][3D] out =
  * r, z, n; hout = (1 - z) n + z h.  Backward: dgi, dgh [B][3D] (the gate

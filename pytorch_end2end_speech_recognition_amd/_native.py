@@ -105,6 +105,12 @@ SIGNATURES = {
     'asr_gru_forward': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'asr_gru_backward': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_size, c_vp]),
+    'asr_lstm_uni_shape_ok': (c_int, [c_int, c_int, c_int]),
+    'asr_lstm_uni_workspace_bytes': (c_size, [c_int, c_int, c_int, c_int]),
+    'asr_lstm_uni_forward': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                     c_vp, c_vp, c_vp, c_size, c_vp]),
+    'asr_lstm_uni_backward': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     'asr_gru_cell_forward': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     'asr_gru_cell_backward': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
                                       c_vp]),

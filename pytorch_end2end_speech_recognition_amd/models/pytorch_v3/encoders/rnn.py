@@ -7,6 +7,9 @@ for the fast path, ``lstm_l{l}.weight_ih_l0[_reverse]`` for the per-layer path,
 construction, so a model built under the same seed holds bit-identical initial
 weights.  ``nn.LSTM`` / ``nn.GRU`` modules are used only as parameter holders;
 their forward never runs (GRU layers: native_ops.bgru_layer, csrc/gru.hip).
+``bidirectional=False`` (LSTM only) builds the reference's unidirectional
+modules -- no ``_reverse`` tensors, output width ``num_units`` -- and runs each
+layer on native_ops.lstm_layer (csrc/lstm_uni.hip).
 
 Forward semantics (rnn.py:284-487): input dropout, the optional VGG front-end
 (encoders/cnn.py, rnn.py:143-160, 314-316), length sort (perm_idx is
@@ -49,8 +52,8 @@ class RNNEncoder(nn.Module):
         unsupported = []
         if rnn_type == 'rnn':
             unsupported.append('rnn_type=rnn')
-        if not bidirectional:
-            unsupported.append('unidirectional')
+        if not bidirectional and rnn_type == 'gru':
+            unsupported.append('unidirectional gru')
         if nin or merge_bidirectional or not batch_first or not pack_sequence:
             unsupported.append('nin/merge/time-major/no-pack')
         if unsupported:
@@ -59,7 +62,7 @@ class RNNEncoder(nn.Module):
 
         self.rnn_type = rnn_type
         self.bidirectional = bidirectional
-        self.num_directions = 2
+        self.num_directions = 2 if bidirectional else 1
         self.num_units = num_units
         self.num_proj = num_proj if num_proj is not None else 0
         self.num_layers = num_layers
@@ -108,36 +111,41 @@ class RNNEncoder(nn.Module):
         if self.fast_impl:   # rnn.py:162-198: one multi-layer nn.LSTM / nn.GRU
             setattr(self, rnn_type,
                     cell(input_size, hidden_size=num_units, num_layers=num_layers, bias=True,
-                         batch_first=batch_first, dropout=dropout_hidden, bidirectional=True))
+                         batch_first=batch_first, dropout=dropout_hidden,
+                         bidirectional=bidirectional))
             self.dropout_last = nn.Dropout(p=dropout_hidden)
         else:                # rnn.py:200-251: one nn.LSTM / nn.GRU per layer (+ projection)
+            out_units = num_units * self.num_directions
             for l in range(num_layers):
                 if l == 0:
                     din = input_size
                 else:
-                    din = self.num_proj if self.num_proj > 0 else num_units * 2
+                    din = self.num_proj if self.num_proj > 0 else out_units
                     if subsample_type == 'concat' and self.subsample_list[l - 1]:
                         din *= 2
                 setattr(self, '%s_l%d' % (rnn_type, l),
                         cell(din, hidden_size=num_units, num_layers=1, bias=True,
-                             batch_first=batch_first, dropout=0, bidirectional=True))
+                             batch_first=batch_first, dropout=0, bidirectional=bidirectional))
                 setattr(self, 'dropout_l%d' % l, nn.Dropout(p=dropout_hidden))
                 if l != num_layers - 1 and self.num_proj > 0:
                     setattr(self, 'proj_l%d' % l,
-                            LinearND(num_units * 2, self.num_proj, dropout=dropout_hidden))
+                            LinearND(out_units, self.num_proj, dropout=dropout_hidden))
 
-    # parameters of layer l: (w_ih_f, w_ih_r), (w_hh_f, w_hh_r), (b_ih_f, b_ih_r), (b_hh_f, b_hh_r)
+    # parameters of layer l: (w_ih_f, w_ih_r), (w_hh_f, w_hh_r), (b_ih_f, b_ih_r), (b_hh_f, b_hh_r);
+    # unidirectional: one-tensor groups (w_ih,), (w_hh,), (b_ih,), (b_hh,)
     def _layer_params(self, l):
         if self.fast_impl:
             mod, k = getattr(self, self.rnn_type), l
         else:
             mod, k = getattr(self, '%s_l%d' % (self.rnn_type, l)), 0
-        return [(getattr(mod, '%s_l%d' % (n, k)), getattr(mod, '%s_l%d_reverse' % (n, k)))
+        sfx = ('', '_reverse')[:self.num_directions]
+        return [tuple(getattr(mod, '%s_l%d%s' % (n, k, s)) for s in sfx)
                 for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
 
     def flat_order(self):
         """Forward and reverse tensors of each LSTM weight adjacent in the flat
-        buffer, so one GEMM / one recurrence launch covers both directions."""
+        buffer, so one GEMM / one recurrence launch covers both directions
+        (unidirectional: single-tensor groups)."""
         groups = []
         for l in range(self.num_layers):
             for pair in self._layer_params(l):
@@ -145,19 +153,21 @@ class RNNEncoder(nn.Module):
         return groups
 
     def _layer_tensors(self, l):
-        """Combined [fwd; rev] views (params and their grads) of layer l."""
+        """Combined [fwd; rev] views (params and their grads) of layer l
+        (unidirectional: the one direction's tensors)."""
         model = self._owner
         ts, gs = [], []
-        for f, r in self._layer_params(l):
-            n = f.numel() + r.numel()
-            shape = (f.shape[0] * 2,) + tuple(f.shape[1:])
+        for grp in self._layer_params(l):
+            f = grp[0]
+            n = sum(p.numel() for p in grp)
+            shape = (f.shape[0] * len(grp),) + tuple(f.shape[1:])
             ts.append(model.flat_view(f, n).view(shape))
             gs.append(model.flat_view(f, n, grad=True).view(shape))
         return ts, gs
 
     def forward(self, xs, x_lens, volatile=False):
         """xs: device tensor [B, T, input_size]; x_lens: numpy / list / tensor [B].
-        Returns (xs [B, T', 2H], x_lens int32 device tensor [B], perm_idx int64
+        Returns (xs [B, T', 2H] (H when unidirectional), x_lens int32 device tensor [B], perm_idx int64
         device tensor [B]) like rnn.py:284-487; host copies of the output
         lengths and perm are kept in ``self.last_lens_np`` / ``self.last_perm_np``."""
         if torch.is_tensor(x_lens):
@@ -181,7 +191,8 @@ class RNNEncoder(nn.Module):
         pending = None   # (p, seed): this layer's dropout, fused into the next layer's staging
         self.pending_output_drop = None
         lens_d, lens_key = None, None
-        if self.rnn_type != 'gru':
+        uni = self.num_directions == 1
+        if self.rnn_type != 'gru' and not uni:
             # one fill for the recurrence workspaces of every layer's forward and
             # backward pass (instead of a memset launch before each)
             ops.rec_arena_begin(dev, int(h.shape[0]), self.num_units, 2 * self.num_layers)
@@ -193,7 +204,13 @@ class RNNEncoder(nn.Module):
                 lens_key = lens.copy()
                 lens_d = ops.h2d(lens.astype(np.int32), dev)
             graph = tuple(p for pair in self._layer_params(l) for p in pair)
-            if self.rnn_type == 'gru':
+            if uni:
+                # the unidirectional op (csrc/lstm_uni.hip): dropout between
+                # layers is the plain pass below, no hand-off, no arena
+                h = ops.lstm_layer(h, lens_d, T, w_ih, w_hh, b_ih, b_hh, perm=pm, t_mul=t_mul,
+                                   t_add=t_add, gbufs=tuple(gbufs), graph_params=graph,
+                                   concat=concat)
+            elif self.rnn_type == 'gru':
                 if pending is not None:
                     h = ops.dropout(h, pending[0], seed=pending[1])
                 h = ops.bgru_layer(h, lens_d, T, w_ih, w_hh, b_ih, b_hh, perm=pm, t_mul=t_mul,
@@ -202,7 +219,7 @@ class RNNEncoder(nn.Module):
             # this layer's output feeds only the next BLSTM layer, through an
             # identity row map: bf16 mode hands it over as that layer's staged
             # bf16 input (dropout applied) instead of an f32 tensor
-            handoff = (self.rnn_type != 'gru' and ops.fuse_dropout_ok() and
+            handoff = (self.rnn_type != 'gru' and not uni and ops.fuse_dropout_ok() and
                        l < self.num_layers - 1 and
                        not (self.num_layers_sub >= 1 and l == self.num_layers_sub - 1) and
                        not (self.residual or self.dense_residual or self.num_proj > 0) and
@@ -210,7 +227,7 @@ class RNNEncoder(nn.Module):
             drop_out = self.training and self.dropout_hidden_p > 0
             # same seed stream either way (one seed per layer, drawn in order)
             seed = ops.next_seed() if drop_out and handoff else None
-            if self.rnn_type != 'gru':
+            if self.rnn_type != 'gru' and not uni:
                 h = ops.blstm_layer(h, lens_d, T, w_ih, w_hh, b_ih, b_hh, perm=pm, t_mul=t_mul,
                                     t_add=t_add, gbufs=tuple(gbufs), graph_params=graph,
                                     concat=concat, drop=pending, next_rec=l > 0,
@@ -223,7 +240,7 @@ class RNNEncoder(nn.Module):
                 # and nothing else reads the dropped h
                 if seed is None:
                     seed = ops.next_seed()
-                if (ops.fuse_dropout_ok() and l < self.num_layers - 1 and
+                if (not uni and ops.fuse_dropout_ok() and l < self.num_layers - 1 and
                         not (self.num_layers_sub >= 1 and l == self.num_layers_sub - 1) and
                         not (self.residual or self.dense_residual or self.num_proj > 0) and
                         not (self.subsample_list[l] and self.subsample_type != 'drop')):

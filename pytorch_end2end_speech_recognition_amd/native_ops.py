@@ -2218,6 +2218,97 @@ def bgru_layer(x_src, lens, T, w_ih, w_hh, b_ih, b_hh, perm=None, t_mul=1, t_add
                              w_ih, w_hh, b_ih, b_hh, *graph_params)
 
 
+class LSTMLayerFn(torch.autograd.Function):
+    """Unidirectional LSTM layer (nn.LSTM(bidirectional=False), rnn.py:166-172 /
+    :218-224) on the per-step recurrence of csrc/lstm_uni.hip.  Same input
+    addressing as BLSTMLayerFn (row map with perm / subsampling / 'concat' rows
+    read in place, drop = (p, seed) on x_src); parameters are one direction's
+    tensors (w_ih [4H, Din], w_hh [4H, H], b_ih, b_hh [4H]).  The recurrence
+    runs in the session's compute dtype; the layer GEMMs read the f32 tensors
+    and, in bf16 mode, round them to bf16 in their loads."""
+
+    @staticmethod
+    def forward(ctx, x_src, lens, T, perm, t_mul, t_add, gbufs, concat, drop, w_ih, w_hh, b_ih,
+                b_hh, *graph_params):
+        N.require_device(x_src, lens, w_ih, w_hh, b_ih, b_hh)
+        x_src = x_src.contiguous()
+        dev = x_src.device
+        if drop is not None:   # the layer reads dropout(x_src)
+            xd = torch.empty_like(x_src)
+            N.call('asr_dropout', N.ptr(x_src), N.ptr(xd), x_src.numel(), float(drop[0]),
+                   int(drop[1]), N.stream_handle(dev))
+            x_src = xd
+        B, T_src, Dsrc = x_src.shape
+        Din = 2 * Dsrc if concat else Dsrc
+        assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
+        H = w_hh.shape[1]
+        cd = compute_dtype()
+        nb = int(N.query('asr_lstm_uni_workspace_bytes', B, H, cd, 0))
+        ws = _ws(nb, dev)
+        in_map = _InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Din)
+        gx = torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev)
+        y = torch.empty(B, T, H, dtype=torch.float32, device=dev)
+        cst = torch.empty(B, T, H, dtype=torch.float32, device=dev)
+        run_gemm([gemm_problem(operand(x_src, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
+                               rowmap(4 * H), B * T, 4 * H, Din, bias=b_ih, bias2=b_hh)], dev)
+        N.call('asr_lstm_uni_forward', N.ptr(gx), N.ptr(w_hh), F32, N.ptr(lens), B, T, H, cd,
+               N.ptr(y), N.ptr(cst), None, N.ptr(ws), nb, N.stream_handle(dev))
+        ctx.save_for_backward(x_src, w_ih, w_hh, b_ih, b_hh, lens, gx, cst, y)
+        ctx.meta = (in_map, gbufs, cd, drop)
+        ctx.n_graph = len(graph_params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x_src, w_ih, w_hh, b_ih, b_hh, lens, act, cst, y = ctx.saved_tensors
+        in_map, gbufs, cd, drop = ctx.meta
+        B, T, Din = x_src.shape[0], in_map.T, in_map.Din
+        H = w_hh.shape[1]
+        dev = act.device
+        dy = dy.contiguous()
+        if gbufs is None:
+            gbufs = tuple(grad_buffer(p) for p in (w_ih, w_hh, b_ih, b_hh))
+        g_ih, g_hh, g_bih, g_bhh = gbufs
+        nb = int(N.query('asr_lstm_uni_workspace_bytes', B, H, cd, 1))
+        ws = _ws(nb, dev)
+        # the saved activations become the gate gradients dG in place; the bias
+        # gradients are its column sums (fixed order)
+        N.call('asr_lstm_uni_backward', N.ptr(dy), N.ptr(w_hh), F32, N.ptr(lens), B, T, H, cd,
+               N.ptr(act), N.ptr(cst), None, N.ptr(g_bih), N.ptr(g_bhh), N.ptr(ws), nb,
+               N.stream_handle(dev))
+        notify_grad_event('recurrence')
+        BT = B * T
+        # dW_ih [4H, Din] += dG^T x ; dW_hh [4H, H] += dG^T h_prev, h_prev = y[b, t-1]
+        hp = rowmap(H, stride_b=T * H, rows_per_b=T, t_add=-1, t_limit=T)
+        run_gemm([gemm_problem(operand(act, 1, rowmap(4 * H)), operand(x_src, 1, in_map.rows()),
+                               g_ih, rowmap(Din), 4 * H, Din, BT, beta=1.0)], dev)
+        run_gemm([gemm_problem(operand(act, 1, rowmap(4 * H)), operand(y, 1, hp), g_hh, rowmap(H),
+                               4 * H, H, BT, beta=1.0)], dev)
+        notify_grad_event('grads', gbufs)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # scattered back through the input map; dropout's backward (the
+            # forward mask over x_src's flat offsets) in the GEMM's epilogue
+            dx = in_map.alloc_dx(B, dev)
+            run_gemm([gemm_problem(operand(act, 0, rowmap(4 * H)), operand(w_ih, 1, rowmap(Din)),
+                                   dx, in_map.rows(), BT, Din, 4 * H, drop=drop)], dev)
+        return (dx,) + (None,) * (12 + ctx.n_graph)
+
+
+def lstm_layer(x_src, lens, T, w_ih, w_hh, b_ih, b_hh, perm=None, t_mul=1, t_add=0, gbufs=None,
+               graph_params=(), concat=False, drop=None):
+    """The unidirectional counterpart of blstm_layer (same addressing, same
+    drop / gbufs / graph_params contract); output [B, T, H].  A shape the
+    recurrence does not take (asr_hip.h) raises NativeError before any launch."""
+    B, H = x_src.shape[0], w_hh.shape[1]
+    if N.query('asr_lstm_uni_shape_ok', int(B), int(T), int(H)) != 1:
+        raise N.NativeError('asr_lstm_uni_forward refused (rc=%d): B %d T %d H %d is outside the '
+                            'shapes the unidirectional recurrence accepts'
+                            % (N.ASR_ERR_UNSUPPORTED, B, T, H))
+    return LSTMLayerFn.apply(x_src, lens, T, perm, t_mul, t_add, gbufs, bool(concat), drop,
+                             w_ih, w_hh, b_ih, b_hh, *graph_params)
+
+
 def _act_h_on():
     """Fused bf16 forward: keep the gate activations as packed fp16
     (asr_lstm_forward_xh; ASR_XG_ACT_H=0 keeps f32)."""
