@@ -634,7 +634,7 @@ int asr_ctc_beam_rows(const float* logits, long long stride_t, long long stride_
                       void* ws, size_t ws_bytes, void* stream);
 /* asr_ctc_beam_search_lm: the prefix search with shallow fusion of an RNN
  * language model and an insertion bonus (csrc/ctc_beam.hip states the contract
- * in full).  lm (asr_att_beam_lm_t, declared with asr_att_beam_decode_lm below;
+ * in full).  lm (asr_att_beam_lm_t, declared with asr_att_beam_decode below;
  * alpha = lm->weight >= 0) has exactly V classes: CTC class c != blank is LM
  * class c - (c > blank), and LM class V - 1 is <eos>, also the LM's start
  * token.  The score of a prefix l after t frames is
@@ -936,11 +936,11 @@ int asr_att_heads_backward(const asr_att_heads_t* p, const float* enc, const flo
 
 /* Attention beam search on the device (AttentionSeq2seq._decode_infer_beam,
  * attention_seq2seq.py:1038-1237; csrc/att_beam.hip states the semantics) for
- * bahdanau order, a one-layer LSTMCell decoder without residual (a GRUCell one:
- * asr_att_beam_decode_ex below), location or content attention.  f32
- * arithmetic whatever the compute mode.  dims as above
- * (T = the padded frame count, S ignored); every utterance decodes over its
- * own lens[b] frames (clipped to [0, T]; 0 frames: empty hypothesis).
+ * bahdanau order, a one-layer LSTMCell or GRUCell decoder without residual,
+ * location or content attention.  f32 arithmetic whatever the compute mode.
+ * dims as above (T = the padded frame count, S ignored); every utterance
+ * decodes over its own lens[b] frames (clipped to [0, T]; 0 frames: empty
+ * hypothesis).
  * opts: W beam width, V classes, Y embedding width, Dz bottleneck width,
  *   max_len / min_len (min_decode_len counts <sos>), eos, length_penalty
  *   (added in double), the decoder weights: w_ih [4D][ld_ih] (columns [0, Y)
@@ -955,11 +955,50 @@ int asr_att_heads_backward(const asr_att_heads_t* p, const float* enc, const flo
  * Plain launches on `stream` in a fixed order, 4 per step; no allocation, no
  * host synchronisation.  The workspace (asr_att_beam_ws_bytes; 256-B aligned,
  * no initialisation) holds the per-step attention record [max_len][B*W][T]
- * and the logits [B*W][V]; utterances read enc in place, so lens_host (nullable)
- * does not change its size.
+ * and the logits [B*W][V]; utterances read enc in place.
+ * ASR_ERR_ARG before any launch: a null pointer, eos outside [0, V), ld_ih <
+ *   Y + E, max_len <= 0, an even conv width, and the optional parts' below.
  * ASR_ERR_UNSUPPORTED (nothing launched, asr_last_error says why): W outside
  *   [2, 32], C > 16, or a kernel's LDS need above 64 KiB (attention: D + 2A +
- *   C K + A C + 2T + K + 63 floats); asr_att_beam_ws_bytes is 0 then. */
+ *   C K + A C + 2T + K + 63 floats); asr_att_beam_ws_bytes is 0 then.
+ *
+ * ex (nullable: an LSTM cell and neither optional part) chooses the cell and
+ * adds the optional parts; whatever is absent costs no launch.
+ *   cell: ASR_ATT_BEAM_CELL_LSTM, or ASR_ATT_BEAM_CELL_GRU for a GRUCell
+ *     decoder (torch's gate rows r, z, n; r scales the hidden part of n, bias
+ *     included): opts' w_ih [3D][ld_ih], w_hh [3D][D], b_ih / b_hh [3D] then
+ *     hold the 3-gate tensors.  Only the cell kernel differs; launch counts,
+ *     limits, workspace and output layout are the same.  Any other cell is
+ *     ASR_ERR_ARG.
+ *   ctc (null or weight 0: absent): the joint CTC/attention search, score =
+ *     (parent + (1 - weight) lp_att(c) + weight delta_ctc(g, c)) +
+ *     length_penalty.  ctc_logits f32 [B][T][Vc]: the raw logits of the CTC head
+ *     over the same frames (read in place, frames t < lens[b] only); attention
+ *     class c != eos is CTC class c + label_offset, which must lie in [0, Vc)
+ *     and differ from blank, and weight must lie in (0, 1] (else ASR_ERR_ARG,
+ *     as a null ctc_logits).  Launches: 2 once, then 7 per step (6 at step 0).
+ *     Workspace: the plain one plus 2 B T floats and (4 B W T + 2 B W + 2 B W
+ *     W) doubles.  The added kernels use a fixed 2 KiB of LDS and add no limit.
+ *   lm (null or weight 0: absent): shallow fusion with an RNN language model,
+ *     score = (parent + (1 - lambda) lp_att(c) + lambda delta_ctc + weight
+ *     lp_lm(c | g)) + length_penalty, lp_lm the f32 log-softmax of the LM's
+ *     output logits after the row's prefix g.  The candidates stay the min(W,
+ *     V) best attention classes of each row; LM class c is attention class c,
+ *     <eos> included, and <sos> is the eos index.  The LM is `layers` stacked
+ *     LSTM layers (torch's gate rows i, f, g, o) over an embedding: emb [V][Y],
+ *     w_ih[0] [4H][Y], w_ih[l] [4H][H] (l > 0), w_hh[l] [4H][H], b_ih[l] /
+ *     b_hh[l] [4H], w_out [V][H] (tied weights: the emb pointer, H == Y), b_out
+ *     [V]; its state starts at zero and steps at every t >= 0, whatever the
+ *     decoder's cell.  2 more launches per step (beam_lm_cell, beam_lm_score)
+ *     and a select variant in the plain one's place.  Workspace: the joint
+ *     search's (whatever lambda) plus 4 B W layers H floats of LM state, B W V
+ *     logits and B W W candidate terms.  ASR_ERR_ARG: lm->V != opts->V, weight
+ *     < 0, a null pointer.  ASR_ERR_UNSUPPORTED (the query is 0 for the first
+ *     two): layers > ASR_ATT_BEAM_LM_MAX_LAYERS, beam_lm_cell's LDS need (2
+ *     max(Y, H) + H floats) above 64 KiB, lm->cell != ASR_ATT_BEAM_CELL_LSTM (a
+ *     GRU LM).
+ * asr_att_beam_ws_bytes reads of ex only whether ctc and lm are null and
+ * lm->layers / H / Y. */
 typedef struct {
   int W, V, Y, Dz, max_len, min_len, eos, emb_trans;
   double length_penalty;
@@ -980,83 +1019,13 @@ typedef struct {
   const float* b_fc;
   const float* emb_w;
 } asr_att_beam_opts_t;
-size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
-                             int max_len, const int32_t* lens_host);
-int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
-                        const float* enc, const float* enc_a, const int32_t* lens,
-                        const float* h0, void* workspace, size_t ws_bytes, long long* tokens,
-                        int32_t* hyp_lens, double* scores, float* aw, void* stream);
-
-/* Joint CTC/attention beam search: asr_att_beam_decode with every candidate's
- * attention log-probability joined by its CTC prefix term (csrc/att_beam.hip
- * states the semantics): score = (parent + (1 - weight) lp_att(c) + weight
- * delta_ctc(g, c)) + length_penalty.  ctc_logits f32 [B][T][Vc]: the raw logits
- * of the CTC head over the same frames (read in place, frames t < lens[b]
- * only); attention class c != eos is CTC class c + label_offset, which must lie
- * in [0, Vc) and differ from blank (else ASR_ERR_ARG).  weight in (0, 1];
- * weight == 0 is asr_att_beam_decode itself (same launches).  Launches: 2 once,
- * then 7 per step (6 at step 0).  The workspace is asr_att_beam_ctc_ws_bytes:
- * that of asr_att_beam_ws_bytes plus 2 B T floats and (4 B W T + 2 B W +
- * 2 B W W) doubles.  ASR_ERR_UNSUPPORTED as asr_att_beam_decode: the added
- * kernels use a fixed 2 KiB of LDS and add no limit. */
 typedef struct {
   const float* ctc_logits;
   int Vc, blank, label_offset;
   double weight;
 } asr_att_beam_ctc_t;
-size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
-                                 int max_len, const int32_t* lens_host);
-int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
-                            const asr_att_beam_ctc_t* ctc, const float* enc, const float* enc_a,
-                            const int32_t* lens, const float* h0, void* workspace,
-                            size_t ws_bytes, long long* tokens, int32_t* hyp_lens, double* scores,
-                            float* aw, void* stream);
-
-/* The search with the decoder's cell type chosen: the two entry points above
- * are cell == ASR_ATT_BEAM_CELL_LSTM (ctc null: asr_att_beam_decode; non-null:
- * asr_att_beam_decode_ctc, weight 0 again the attention-only search), with
- * exactly their launches.  ASR_ATT_BEAM_CELL_GRU: a one-layer GRUCell decoder
- * (torch's gate rows r, z, n; r scales the hidden part of n, bias included);
- * opts' w_ih [3D][ld_ih], w_hh [3D][D], b_ih / b_hh [3D] then hold the 3-gate
- * tensors.  Only the cell kernel differs (beam_cell_gru for beam_cell): the
- * launch counts, the limits (the cell's LDS need is the same Y + E + D floats)
- * and the outputs' layout are those above.  The workspace is sized by the same
- * asr_att_beam_ws_bytes / asr_att_beam_ctc_ws_bytes: the GRU search needs no
- * more than the LSTM one (it leaves the c rows unused).  Any other cell is
- * ASR_ERR_ARG, before any launch. */
 #define ASR_ATT_BEAM_CELL_LSTM 0
 #define ASR_ATT_BEAM_CELL_GRU 1
-typedef struct {
-  int cell;
-  const asr_att_beam_ctc_t* ctc; /* nullable */
-} asr_att_beam_ex_t;
-int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
-                           const asr_att_beam_ex_t* ex, const float* enc, const float* enc_a,
-                           const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
-                           long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
-                           void* stream);
-
-/* Shallow fusion with an RNN language model: asr_att_beam_decode_ex with every
- * candidate's score joined by weight * lp_lm(c | g), the f32 log-softmax of the
- * LM's output logits after the row's prefix g (csrc/att_beam.hip states the
- * semantics): score = (parent + (1 - lambda) lp_att(c) + lambda delta_ctc +
- * weight lp_lm(c | g)) + length_penalty.  The candidates stay the min(W, V) best
- * attention classes of each row; LM class c is attention class c, <eos> included,
- * and <sos> is the eos index.  The LM is `layers` stacked LSTM layers (torch's
- * gate rows i, f, g, o) over an embedding: emb [V][Y], w_ih[0] [4H][Y], w_ih[l]
- * [4H][H] (l > 0), w_hh[l] [4H][H], b_ih[l] / b_hh[l] [4H], w_out [V][H] (tied
- * weights: the emb pointer, H == Y), b_out [V]; its state starts at zero and
- * steps at every t >= 0.  The decoder's cell type (ex->cell) is independent of it.
- * lm null or weight 0: exactly asr_att_beam_decode_ex's launches; else 2 more
- * launches per step (beam_lm_cell, beam_lm_score) and a select variant in the
- * plain one's place.  The workspace is asr_att_beam_lm_ws_bytes: that of
- * asr_att_beam_ctc_ws_bytes (whatever lambda) plus 4 B W layers H floats of LM
- * state, B W V logits and B W W candidate terms.
- * ASR_ERR_ARG before any launch: lm->V != opts->V, weight < 0, a null pointer.
- * ASR_ERR_UNSUPPORTED (nothing launched; asr_att_beam_lm_ws_bytes is 0 for the
- * first two): layers > ASR_ATT_BEAM_LM_MAX_LAYERS, beam_lm_cell's LDS need
- * (2 max(Y, H) + H floats) above 64 KiB, cell != ASR_ATT_BEAM_CELL_LSTM (a GRU
- * LM), and asr_att_beam_decode's own refusals. */
 #define ASR_ATT_BEAM_LM_MAX_LAYERS 4
 typedef struct asr_att_beam_lm_s {
   int layers, H, Y, V;
@@ -1070,14 +1039,18 @@ typedef struct asr_att_beam_lm_s {
   const float* b_out;
   double weight;
 } asr_att_beam_lm_t;
-size_t asr_att_beam_lm_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
-                                int max_len, const int32_t* lens_host, int lm_layers, int lm_H,
-                                int lm_Y);
-int asr_att_beam_decode_lm(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
-                           const asr_att_beam_ex_t* ex, const asr_att_beam_lm_t* lm,
-                           const float* enc, const float* enc_a, const int32_t* lens,
-                           const float* h0, void* workspace, size_t ws_bytes, long long* tokens,
-                           int32_t* hyp_lens, double* scores, float* aw, void* stream);
+typedef struct {
+  int cell;
+  const asr_att_beam_ctc_t* ctc; /* nullable */
+  const asr_att_beam_lm_t* lm;   /* nullable */
+} asr_att_beam_ex_t;
+size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
+                             int max_len, const asr_att_beam_ex_t* ex);
+int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* opts,
+                        const asr_att_beam_ex_t* ex, const float* enc, const float* enc_a,
+                        const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
+                        long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
+                        void* stream);
 
 /* Test / diagnostics: the attention-step kernel instantiations the last
  * asr_attdec_forward_ex / _backward_ex launched: out4 = {forward conv-channel

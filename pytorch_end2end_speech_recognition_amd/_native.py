@@ -261,14 +261,7 @@ SIGNATURES = {
     'asr_att_heads_forward': (c_int, [c_vp] + [c_vp] * 8 + [c_size, c_vp]),
     'asr_att_heads_backward': (c_int, [c_vp] + [c_vp] * 17 + [c_size, c_vp]),
     'asr_att_beam_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
-    'asr_att_beam_decode': (c_int, [c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
-    'asr_att_beam_ctc_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
-    'asr_att_beam_decode_ctc': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
-    'asr_att_beam_decode_ex': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
-    'asr_att_beam_lm_ws_bytes': (c_size, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
-                                          c_int, c_int]),
-    'asr_att_beam_decode_lm': (c_int, [c_vp, c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] +
-                               [c_vp] * 5),
+    'asr_att_beam_decode': (c_int, [c_vp, c_vp, c_vp] + [c_vp] * 5 + [c_size] + [c_vp] * 5),
     'asr_lstm_xg_mode': (c_int, [c_vp, c_int]),
     'asr_lstm_last_path': (c_int, [c_vp]),
     'asr_ctc_last_path': (c_int, [c_vp]),
@@ -386,7 +379,7 @@ ATT_BEAM_CELL_GRU = 1
 
 class AttBeamEx(ctypes.Structure):
     """asr_att_beam_ex_t"""
-    _fields_ = [('cell', c_int), ('ctc', c_vp)]
+    _fields_ = [('cell', c_int), ('ctc', c_vp), ('lm', c_vp)]
 
 
 ATT_BEAM_LM_MAX_LAYERS = 4

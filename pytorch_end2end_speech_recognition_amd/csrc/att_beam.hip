@@ -1,7 +1,7 @@
 // Attention beam search on gfx950 (AttentionSeq2seq._decode_infer_beam,
 // attention_seq2seq.py:1038-1237 of the reference) for bahdanau order, one
 // decoder layer without residual -- an LSTMCell (the decoders the fused pass
-// covers) or a GRUCell (asr_att_beam_decode_ex; the TIMIT attention recipes) --
+// covers) or a GRUCell (ex->cell; the TIMIT attention recipes) --
 // and one head of location or content attention.  f32 arithmetic in both
 // compute modes: a beam of at most W rows needs no MFMA throughput, and a bf16
 // near-tie flip changes whole hypotheses.
@@ -50,7 +50,7 @@
 // The state is double buffered by step parity and read through the parent
 // index, so no gather pass exists.
 //
-// Joint CTC/attention search (asr_att_beam_decode_ctc, weight = lambda in
+// Joint CTC/attention search (ex->ctc, weight = lambda in
 // (0, 1]; the host path of the model follows the same contract; lambda == 0 is
 // the search above, with the launches above):
 //   * label spaces: attention class c (c != <eos>) is CTC class c +
@@ -98,7 +98,7 @@
 //                       psi(g.c) and delta of the row's min(W, V) candidates
 //   beam_select_ctc (utt)  beam_select with the joint score; hands psi on
 //
-// Shallow fusion with an RNN language model (asr_att_beam_decode_lm, weight =
+// Shallow fusion with an RNN language model (ex->lm, weight =
 // gamma > 0; the host path of the model follows the same contract; gamma == 0 or
 // no LM is the search above, with the launches above):
 //   * label spaces: LM class c is attention class c, <eos> included (an ordinary
@@ -116,6 +116,7 @@
 //     lambda > 0 (else lp_att(c) stands alone).  The tie rules, the
 //     min_decode_len rule, completion and backtracking are unchanged.
 // Added kernels:
+// (the LM's arithmetic is csrc/beam_lm.h's, shared with the CTC prefix search)
 //   beam_lm_cell   (row)  every t, before beam_lm_score: embedding of the row's
 //                       token, then the LM's layers in order inside the
 //                       work-group: [x; h] of the parent row in LDS, one wave per
@@ -130,7 +131,7 @@
 //                       with the gamma term
 #include <limits.h>
 
-#include "common.h"
+#include "beam_lm.h"
 
 namespace asr {
 namespace {
@@ -138,7 +139,6 @@ namespace {
 constexpr int kMinBeam = 2, kMaxBeam = 32;
 constexpr int CELL_THREADS = 256, ATT_THREADS = 512, EXP_THREADS = 256, BT_THREADS = 256;
 constexpr int kMaxC = 16;
-constexpr size_t kLdsLimit = 64 * 1024;
 
 struct BeamP {
   int B, T, E, A, C, K, D, W, V, Y, Dz, max_len, min_len, eos, sigmoid, emb_trans;
@@ -163,7 +163,7 @@ struct BeamP {
   int *rows;               // [B][max_len]: the best hypothesis' row per step
 };
 
-// the joint search's additions (asr_att_beam_decode_ctc)
+// the joint search's additions (ex->ctc)
 struct CtcP {
   const float* lg;         // [B][T][Vc] logits of the CTC head
   int Vc, blank, off;
@@ -176,15 +176,10 @@ struct CtcP {
 };
 constexpr double kLogZero = -1.0e10;
 
-// the language model's additions (asr_att_beam_decode_lm); its V is p.V
-constexpr int kMaxLmLayers = ASR_ATT_BEAM_LM_MAX_LAYERS;
+// the language model's additions (ex->lm); net.V is p.V
 struct LmP {
-  int layers, H, Y;
+  LmNet net;
   double weight;
-  const float* emb;        // [V][Y]
-  const float *w_ih[kMaxLmLayers], *w_hh[kMaxLmLayers];   // [4H][Y or H], [4H][H]
-  const float *b_ih[kMaxLmLayers], *b_hh[kMaxLmLayers];   // [4H]
-  const float *w_out, *b_out;   // [V][H], [V]
   // workspace
   float *h, *c;            // [2][R][layers][H] by step parity
   float *lg;               // [R][V] output logits
@@ -224,23 +219,33 @@ __global__ void __launch_bounds__(256) beam_init(BeamP p) {
 }
 
 // ------------------------------------------------------------------- cell
-__global__ void __launch_bounds__(CELL_THREADS) beam_cell(int t, BeamP p) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int i = blockIdx.x, b = blockIdx.y;
-  if (p.done[b] || i >= p.n_live[b]) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = CELL_THREADS / 64;
+// Row i of step t: its state's place (cur) and its parent's (prev), and [e; ctx;
+// h] of the parent row staged to x ([Y + E + D], LDS) for the whole work-group.
+struct CellRow { long long cur, prev; };
+
+__device__ __forceinline__ CellRow cell_stage(int t, const BeamP& p, int i, int b, float* x) {
+  const int tid = threadIdx.x;
   const long long R = (long long)p.B * p.W;
   const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
   const int par = p.par_tab[tab], tok = p.tok_tab[tab];
   const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
   const int cur = t & 1, prev = cur ^ 1;
-  const int YE = p.Y + p.E;
-  float* x = sm;   // [Y + E + D] = [e; ctx; h] of the parent row
   for (int y = tid; y < p.Y; y += CELL_THREADS)
     x[y] = p.emb_trans ? p.emb_w[(long long)y * p.V + tok] : p.emb_w[(long long)tok * p.Y + y];
   for (int e = tid; e < p.E; e += CELL_THREADS) x[p.Y + e] = p.ctx[(prev * R + pr) * p.E + e];
-  for (int j = tid; j < p.D; j += CELL_THREADS) x[YE + j] = p.h[(prev * R + pr) * p.D + j];
+  for (int j = tid; j < p.D; j += CELL_THREADS) x[p.Y + p.E + j] = p.h[(prev * R + pr) * p.D + j];
   __syncthreads();
+  return {cur * R + r, prev * R + pr};
+}
+
+__global__ void __launch_bounds__(CELL_THREADS) beam_cell(int t, BeamP p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (p.done[b] || i >= p.n_live[b]) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = CELL_THREADS / 64;
+  const int YE = p.Y + p.E;
+  float* x = sm;
+  const CellRow cr = cell_stage(t, p, i, b, x);
   for (int u = w; u < p.D; u += nw) {   // one wave per hidden unit, lanes over K
     float s[4];
 #pragma unroll
@@ -256,33 +261,23 @@ __global__ void __launch_bounds__(CELL_THREADS) beam_cell(int t, BeamP p) {
     if (lane == 0) {
       const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
       const float gg = tanhf_(s[2]), og = sigmoidf_(s[3]);
-      const float cn = fg * p.c[(prev * R + pr) * p.D + u] + ig * gg;
-      p.c[(cur * R + r) * p.D + u] = cn;
-      p.h[(cur * R + r) * p.D + u] = og * tanhf_(cn);
+      const float cn = fg * p.c[cr.prev * p.D + u] + ig * gg;
+      p.c[cr.cur * p.D + u] = cn;
+      p.h[cr.cur * p.D + u] = og * tanhf_(cn);
     }
   }
 }
 
-// GRUCell (gate rows r, z, n): the same row, tables and LDS staging as
-// beam_cell.  r scales the hidden part of the n gate only, its bias included,
+// GRUCell (gate rows r, z, n): beam_cell's row, tables and staging.  r scales the hidden part of the n gate only, its bias included,
 // so that gate's two parts are summed apart.  No c state.
 __global__ void __launch_bounds__(CELL_THREADS) beam_cell_gru(int t, BeamP p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int i = blockIdx.x, b = blockIdx.y;
   if (p.done[b] || i >= p.n_live[b]) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = CELL_THREADS / 64;
-  const long long R = (long long)p.B * p.W;
-  const long long tab = ((long long)(t - 1) * p.B + b) * p.W + i;
-  const int par = p.par_tab[tab], tok = p.tok_tab[tab];
-  const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
-  const int cur = t & 1, prev = cur ^ 1;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = CELL_THREADS / 64;
   const int YE = p.Y + p.E;
-  float* x = sm;   // [Y + E + D] = [e; ctx; h] of the parent row
-  for (int y = tid; y < p.Y; y += CELL_THREADS)
-    x[y] = p.emb_trans ? p.emb_w[(long long)y * p.V + tok] : p.emb_w[(long long)tok * p.Y + y];
-  for (int e = tid; e < p.E; e += CELL_THREADS) x[p.Y + e] = p.ctx[(prev * R + pr) * p.E + e];
-  for (int j = tid; j < p.D; j += CELL_THREADS) x[YE + j] = p.h[(prev * R + pr) * p.D + j];
-  __syncthreads();
+  float* x = sm;
+  const CellRow cr = cell_stage(t, p, i, b, x);
   for (int u = w; u < p.D; u += nw) {   // one wave per hidden unit, lanes over K
     float si[3], sh[3];
 #pragma unroll
@@ -299,7 +294,7 @@ __global__ void __launch_bounds__(CELL_THREADS) beam_cell_gru(int t, BeamP p) {
     if (lane == 0) {
       const float rg = sigmoidf_(si[0] + sh[0]), zg = sigmoidf_(si[1] + sh[1]);
       const float ng = tanhf_(si[2] + rg * sh[2]);
-      p.h[(cur * R + r) * p.D + u] = (1.f - zg) * ng + zg * x[YE + u];
+      p.h[cr.cur * p.D + u] = (1.f - zg) * ng + zg * x[YE + u];
     }
   }
 }
@@ -487,20 +482,16 @@ __global__ void __launch_bounds__(EXP_THREADS) beam_expand(int t, BeamP p) {
 }
 
 // ----------------------------------------------------------- language model
-constexpr int LM_THREADS = 256;
-
-__host__ __device__ inline size_t lm_cell_lds_floats(int Y, int H) {
-  return 2 * (size_t)(Y > H ? Y : H) + H;
-}
-
 // One step of the LM's stacked LSTM for row i of step t: token and parent from
-// the tables (t == 0: <sos> from the zero state).  xa / xb alternate as a
-// layer's input and output; hp is the parent's h of the layer.
+// the tables (t == 0: <sos> from the zero state).  The loop is lm_lstm_step's
+// (csrc/beam_lm.h), kept in its own text here: through the shared function this
+// kernel measured 3 % slower (620 ms against 601 ms a call at W 4, V 29, a 2 x
+// 512 LM), with the same registers and the same instructions in the loop.  A
+// change to either copy goes into both.
 __global__ void __launch_bounds__(LM_THREADS) beam_lm_cell(int t, BeamP p, LmP m) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int i = blockIdx.x, b = blockIdx.y;
   if (p.done[b] || i >= p.n_live[b]) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
   const long long R = (long long)p.B * p.W;
   int par = 0, tok = p.eos;
   if (t > 0) {
@@ -510,19 +501,21 @@ __global__ void __launch_bounds__(LM_THREADS) beam_lm_cell(int t, BeamP p, LmP m
   }
   const long long r = (long long)b * p.W + i, pr = (long long)b * p.W + par;
   const int cur = t & 1, prev = cur ^ 1;
-  const int H = m.H, XM = max(m.Y, H);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
+  const LmNet& n = m.net;
+  const int H = n.H, XM = max(n.Y, H);
   float* xa = sm;            // [max(Y, H)]
   float* xb = xa + XM;       // [max(Y, H)]
   float* hp = xb + XM;       // [H]
-  for (int y = tid; y < m.Y; y += LM_THREADS) xa[y] = m.emb[(long long)tok * m.Y + y];
-  for (int l = 0; l < m.layers; ++l) {
-    const int in = l == 0 ? m.Y : H;
-    const long long so = ((cur * R + r) * m.layers + l) * H;    // this row's state
-    const long long sp = ((prev * R + pr) * m.layers + l) * H;  // the parent's
+  for (int y = tid; y < n.Y; y += LM_THREADS) xa[y] = n.emb[(long long)tok * n.Y + y];
+  for (int l = 0; l < n.layers; ++l) {
+    const int in = l == 0 ? n.Y : H;
+    const long long so = ((cur * R + r) * n.layers + l) * H;    // this row's state
+    const long long sp = ((prev * R + pr) * n.layers + l) * H;  // the parent's
     for (int j = tid; j < H; j += LM_THREADS) hp[j] = t > 0 ? m.h[sp + j] : 0.f;
     __syncthreads();
-    const float* wi_l = m.w_ih[l];
-    const float* wh_l = m.w_hh[l];
+    const float* wi_l = n.w_ih[l];
+    const float* wh_l = n.w_hh[l];
     for (int u = w; u < H; u += nw) {   // one wave per hidden unit, lanes over K
       float s[4];
 #pragma unroll
@@ -533,7 +526,7 @@ __global__ void __launch_bounds__(LM_THREADS) beam_lm_cell(int t, BeamP p, LmP m
         float a = 0.f;
         for (int k = lane; k < in; k += 64) a += wi[k] * xa[k];
         for (int k = lane; k < H; k += 64) a += wh[k] * hp[k];
-        s[g] = wave_sum(a) + m.b_ih[l][row] + m.b_hh[l][row];
+        s[g] = wave_sum(a) + n.b_ih[l][row] + n.b_hh[l][row];
       }
       if (lane == 0) {
         const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
@@ -557,30 +550,18 @@ __global__ void __launch_bounds__(LM_THREADS) beam_lm_score(int t, BeamP p, LmP 
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int i = blockIdx.x, b = blockIdx.y;
   if (p.done[b] || i >= p.n_live[b]) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
+  const int tid = threadIdx.x;
   const long long R = (long long)p.B * p.W;
   const long long r = (long long)b * p.W + i;
-  const int cur = t & 1, H = m.H;
+  const int cur = t & 1, H = m.net.H;
   float* hS = sm;            // [H]
   float* red = hS + H;       // [4]
-  const float* hs = m.h + (((cur * R + r) * m.layers) + (m.layers - 1)) * H;
+  const float* hs = m.h + (((cur * R + r) * m.net.layers) + (m.net.layers - 1)) * H;
   for (int j = tid; j < H; j += LM_THREADS) hS[j] = hs[j];
   __syncthreads();
   float* lg = m.lg + r * p.V;
-  float mx = neg_inf();
-  for (int v = w; v < p.V; v += nw) {      // one wave per class
-    const float* wr = m.w_out + (long long)v * H;
-    float s = 0.f;
-    for (int k = lane; k < H; k += 64) s += wr[k] * hS[k];
-    s = wave_sum(s) + m.b_out[v];
-    if (lane == 0) lg[v] = s;
-    mx = fmaxf(mx, s);
-  }
-  mx = block_red(mx, red, true);           // its barriers also publish lg to the work-group
-  float se = 0.f;
-  for (int v = tid; v < p.V; v += LM_THREADS) se += expf(lg[v] - mx);
-  se = block_red(se, red, false);
-  const float lse = logf(se);
+  float mx, lse;
+  lm_output_lse<wave_sum>(m.net, hS, lg, red, mx, lse);
   const int ktop = min(p.W, p.V);
   for (int k = tid; k < ktop; k += LM_THREADS) {
     const int c = p.topc[r * p.W + k];
@@ -608,22 +589,17 @@ __device__ __forceinline__ void select_body(int t, const BeamP& p, const CtcP* q
     const int tok = p.topc[(r0 + i) * p.W + k];
     const bool drop = tok < 0 || (tok == p.eos && t + 1 < p.min_len);
     s_tok[e] = drop ? -1 : tok;
-    if constexpr (LM) {
-      const double gl = tok < 0 ? 0.0 : m->weight * (double)m->lp[(r0 + i) * p.W + k];
-      if constexpr (CTC) {
-        const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[(r0 + i) * p.W + k];
-        s_score[e] = (p.sc[r0 + i] + (1.0 - lam) * (double)p.topv[(r0 + i) * p.W + k] + lam * d +
-                      gl) + p.penalty;
-      } else {
-        s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k] + gl) + p.penalty;
-      }
-    } else if constexpr (CTC) {
-      const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[(r0 + i) * p.W + k];
-      s_score[e] = (p.sc[r0 + i] + (1.0 - lam) * (double)p.topv[(r0 + i) * p.W + k] + lam * d) +
-                   p.penalty;
+    // ((sc + att) [+ lam d] [+ gl]) + penalty, in this order
+    const long long ck = (r0 + i) * p.W + k;
+    double s = p.sc[r0 + i];
+    if constexpr (CTC) {
+      const double lam = q->weight, d = tok < 0 ? 0.0 : q->delta[ck];
+      s = s + (1.0 - lam) * (double)p.topv[ck] + lam * d;
     } else {
-      s_score[e] = (p.sc[r0 + i] + (double)p.topv[(r0 + i) * p.W + k]) + p.penalty;
+      s = s + (double)p.topv[ck];
     }
+    if constexpr (LM) s = s + (tok < 0 ? 0.0 : m->weight * (double)m->lp[ck]);
+    s_score[e] = s + p.penalty;
   }
   __syncthreads();
   // W rounds of (score descending, generation index ascending)
@@ -991,17 +967,7 @@ LmWs lm_ws(size_t base, int B, int W, int V, int layers, int H) {
   return w;
 }
 
-// the LM's shape limits (its pointers and V are the decode call's to check)
-int lm_check(int layers, int H, int Y) {
-  ASR_REQUIRE(layers >= 1 && H > 0 && Y > 0, ASR_ERR_ARG, "att_beam_lm: bad dims (layers %d, H %d, "
-              "Y %d)", layers, H, Y);
-  ASR_REQUIRE(layers <= kMaxLmLayers, ASR_ERR_UNSUPPORTED, "att_beam_lm: %d LM layers > %d", layers,
-              kMaxLmLayers);
-  const size_t lc = lm_cell_lds_floats(Y, H) * 4;
-  ASR_REQUIRE(lc <= kLdsLimit, ASR_ERR_UNSUPPORTED, "att_beam_lm: LDS need (lm cell %zu B) > %zu B",
-              lc, kLdsLimit);
-  return ASR_OK;
-}
+constexpr LmWho kLmWho = {"att_beam_decode_lm", "att_beam_lm", "dims", "decoder", ""};
 
 // ASR_OK, or the refusal with its reason in the error text
 int beam_check(const asr_attdec_dims_t& d, int W, int V, int Y, int Dz, int max_len) {
@@ -1027,37 +993,30 @@ int beam_check(const asr_attdec_dims_t& d, int W, int V, int Y, int Dz, int max_
 
 using namespace asr;
 
+// plain; plain + the joint search's part; plain + the joint search's part + the
+// LM's (whatever lambda is, so the LM's part has one place)
 extern "C" size_t asr_att_beam_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y, int Dz,
-                                        int max_len, const int32_t* lens_host) {
+                                        int max_len, const asr_att_beam_ex_t* ex) {
   if (!dims || beam_check(*dims, W, V, Y, Dz, max_len) != ASR_OK) return 0;
-  (void)lens_host;   // every utterance reads enc in place: no per-length copies to size
-  return beam_ws(dims->B, dims->T, dims->E, dims->D, W, V, max_len).total;
+  const size_t plain = beam_ws(dims->B, dims->T, dims->E, dims->D, W, V, max_len).total;
+  if (!ex || (!ex->ctc && !ex->lm)) return plain;
+  const size_t joint = ctc_ws(plain, dims->B, dims->T, W).total;
+  if (!ex->lm) return joint;
+  if (lm_net_shape_check(ex->lm->layers, ex->lm->H, ex->lm->Y, kLmWho) != ASR_OK) return 0;
+  return lm_ws(joint, dims->B, W, V, ex->lm->layers, ex->lm->H).total;
 }
 
-extern "C" size_t asr_att_beam_ctc_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y,
-                                            int Dz, int max_len, const int32_t* lens_host) {
-  const size_t base = asr_att_beam_ws_bytes(dims, W, V, Y, Dz, max_len, lens_host);
-  return base ? ctc_ws(base, dims->B, dims->T, W).total : 0;
-}
-
-extern "C" size_t asr_att_beam_lm_ws_bytes(const asr_attdec_dims_t* dims, int W, int V, int Y,
-                                           int Dz, int max_len, const int32_t* lens_host,
-                                           int lm_layers, int lm_H, int lm_Y) {
-  const size_t base = asr_att_beam_ctc_ws_bytes(dims, W, V, Y, Dz, max_len, lens_host);
-  if (!base || lm_check(lm_layers, lm_H, lm_Y) != ASR_OK) return 0;
-  return lm_ws(base, dims->B, W, V, lm_layers, lm_H).total;
-}
-
-// ctc == nullptr: the attention-only search, its launches unchanged; cell: which
-// cell kernel steps the rows (ASR_ATT_BEAM_CELL_*), the only difference it makes;
-// lm == nullptr: no language model, the launches unchanged
-static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                            const asr_att_beam_ctc_t* ctc, const asr_att_beam_lm_t* lm, int cell,
-                            const float* enc,
-                            const float* enc_a,
-                            const int32_t* lens, const float* h0, void* workspace, size_t ws_bytes,
-                            long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
-                            void* stream) {
+// ex null: an LSTM cell, no CTC term, no LM.  cell: which cell kernel steps the
+// rows, the only difference it makes; ctc null or weight 0: the attention-only
+// launches; lm null or weight 0: no LM launches
+extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
+                                   const asr_att_beam_ex_t* ex, const float* enc,
+                                   const float* enc_a, const int32_t* lens, const float* h0,
+                                   void* workspace, size_t ws_bytes, long long* tokens,
+                                   int32_t* hyp_lens, double* scores, float* aw, void* stream) {
+  const int cell = ex ? ex->cell : ASR_ATT_BEAM_CELL_LSTM;
+  const asr_att_beam_ctc_t* ctc = (ex && ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
+  const asr_att_beam_lm_t* lm = (ex && ex->lm && ex->lm->weight != 0.0) ? ex->lm : nullptr;
   ASR_REQUIRE(dims && o, ASR_ERR_ARG, "att_beam_decode: dims / opts is null");
   ASR_REQUIRE(cell == ASR_ATT_BEAM_CELL_LSTM || cell == ASR_ATT_BEAM_CELL_GRU, ASR_ERR_ARG,
               "att_beam_decode: unknown cell %d", cell);
@@ -1090,18 +1049,8 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
   if (lm) {
     ASR_REQUIRE(lm->weight > 0.0, ASR_ERR_ARG, "att_beam_decode_lm: weight = %g is negative",
                 lm->weight);
-    ASR_REQUIRE(lm->V == o->V, ASR_ERR_ARG, "att_beam_decode_lm: the LM has %d classes, the "
-                "decoder %d", lm->V, o->V);
-    const int lrc = lm_check(lm->layers, lm->H, lm->Y);
+    const int lrc = lm_net_check(lm, o->V, kLmWho);
     if (lrc) return lrc;
-    ASR_REQUIRE(lm->cell == ASR_ATT_BEAM_CELL_LSTM, ASR_ERR_UNSUPPORTED,
-                "att_beam_decode_lm: only an LSTM language model runs on the device (cell %d)",
-                lm->cell);
-    ASR_REQUIRE(lm->emb && lm->w_out && lm->b_out, ASR_ERR_ARG,
-                "att_beam_decode_lm: null pointer");
-    for (int l = 0; l < lm->layers; ++l)
-      ASR_REQUIRE(lm->w_ih[l] && lm->w_hh[l] && lm->b_ih[l] && lm->b_hh[l], ASR_ERR_ARG,
-                  "att_beam_decode_lm: null pointer (layer %d)", l);
     lw = lm_ws(cw.total, dims->B, o->W, o->V, lm->layers, lm->H);
   }
   const size_t need = lm ? lw.total : ctc ? cw.total : w.total;
@@ -1146,16 +1095,12 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
   LmP m = {};
   size_t lds_lmc = 0, lds_lms = 0;
   if (lm) {
-    m.layers = lm->layers; m.H = lm->H; m.Y = lm->Y; m.weight = lm->weight;
-    m.emb = lm->emb; m.w_out = lm->w_out; m.b_out = lm->b_out;
-    for (int l = 0; l < lm->layers; ++l) {
-      m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l];
-      m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l];
-    }
+    m.net = lm_net_from(lm);
+    m.weight = lm->weight;
     m.h = (float*)(base + lw.h); m.c = (float*)(base + lw.c);
     m.lg = (float*)(base + lw.lg); m.lp = (float*)(base + lw.lp);
-    lds_lmc = lm_cell_lds_floats(m.Y, m.H) * 4;
-    lds_lms = ((size_t)m.H + 8) * 4;
+    lds_lmc = lm_cell_lds_floats(lm->Y, lm->H) * 4;
+    lds_lms = ((size_t)lm->H + 8) * 4;
   }
   hipLaunchKernelGGL(beam_init, dim3(p.B), dim3(256), 0, s, p);
   ASR_LAUNCH_CHECK();
@@ -1207,51 +1152,4 @@ static int beam_decode_impl(const asr_attdec_dims_t* dims, const asr_att_beam_op
                      scores, aw);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
-}
-
-extern "C" int asr_att_beam_decode(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                                   const float* enc, const float* enc_a, const int32_t* lens,
-                                   const float* h0, void* workspace, size_t ws_bytes,
-                                   long long* tokens, int32_t* hyp_lens, double* scores, float* aw,
-                                   void* stream) {
-  return beam_decode_impl(dims, o, nullptr, nullptr, ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace,
-                          ws_bytes, tokens, hyp_lens, scores, aw, stream);
-}
-
-extern "C" int asr_att_beam_decode_ctc(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                                       const asr_att_beam_ctc_t* ctc, const float* enc,
-                                       const float* enc_a, const int32_t* lens, const float* h0,
-                                       void* workspace, size_t ws_bytes, long long* tokens,
-                                       int32_t* hyp_lens, double* scores, float* aw, void* stream) {
-  ASR_REQUIRE(ctc, ASR_ERR_ARG, "att_beam_decode_ctc: ctc is null");
-  // weight 0 is the attention-only search itself
-  return beam_decode_impl(dims, o, ctc->weight == 0.0 ? nullptr : ctc, nullptr,
-                          ASR_ATT_BEAM_CELL_LSTM, enc, enc_a, lens, h0, workspace, ws_bytes, tokens, hyp_lens, scores, aw,
-                          stream);
-}
-
-// the search with the cell type chosen: cell == LSTM is the two entry points above
-extern "C" int asr_att_beam_decode_ex(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                                      const asr_att_beam_ex_t* ex, const float* enc,
-                                      const float* enc_a, const int32_t* lens, const float* h0,
-                                      void* workspace, size_t ws_bytes, long long* tokens,
-                                      int32_t* hyp_lens, double* scores, float* aw, void* stream) {
-  ASR_REQUIRE(ex, ASR_ERR_ARG, "att_beam_decode_ex: ex is null");
-  const asr_att_beam_ctc_t* ctc = (ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
-  return beam_decode_impl(dims, o, ctc, nullptr, ex->cell, enc, enc_a, lens, h0, workspace,
-                          ws_bytes, tokens, hyp_lens, scores, aw, stream);
-}
-
-// the search with a language model: lm null or weight 0 is asr_att_beam_decode_ex
-extern "C" int asr_att_beam_decode_lm(const asr_attdec_dims_t* dims, const asr_att_beam_opts_t* o,
-                                      const asr_att_beam_ex_t* ex, const asr_att_beam_lm_t* lm,
-                                      const float* enc, const float* enc_a, const int32_t* lens,
-                                      const float* h0, void* workspace, size_t ws_bytes,
-                                      long long* tokens, int32_t* hyp_lens, double* scores,
-                                      float* aw, void* stream) {
-  ASR_REQUIRE(ex, ASR_ERR_ARG, "att_beam_decode_lm: ex is null");
-  const asr_att_beam_ctc_t* ctc = (ex->ctc && ex->ctc->weight != 0.0) ? ex->ctc : nullptr;
-  if (lm && lm->weight == 0.0) lm = nullptr;
-  return beam_decode_impl(dims, o, ctc, lm, ex->cell, enc, enc_a, lens, h0, workspace, ws_bytes,
-                          tokens, hyp_lens, scores, aw, stream);
 }

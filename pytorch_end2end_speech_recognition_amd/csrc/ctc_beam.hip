@@ -68,10 +68,11 @@
 // 0), lm_init_kernel, the root's LM step; per frame lm_topk_kernel (per entry),
 // lm_select_kernel (per utterance) and, with an LM, lm_step_kernel (per extended
 // entry: LSTM cell from the parent's state, output layer, log-softmax into the
-// entry's row); lm_final_kernel.  No host read, no host synchronisation.
+// entry's row; the arithmetic is csrc/beam_lm.h's, shared with the attention
+// search); lm_final_kernel.  No host read, no host synchronisation.
 #include <limits.h>
 
-#include "common.h"
+#include "beam_lm.h"
 
 namespace asr {
 namespace {
@@ -106,10 +107,16 @@ __device__ __forceinline__ float group_max(float v, float* sh) {
   return v;
 }
 
-template <int WAVES>
-__device__ __forceinline__ float group_sum(float v, float* sh) {
+// the sum over a wave's lanes as this file has always formed it (an xor butterfly)
+__device__ __forceinline__ float wave_sum_xor(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <int WAVES>
+__device__ __forceinline__ float group_sum(float v, float* sh) {
+  v = wave_sum_xor(v);
   if (WAVES > 1) {
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
@@ -394,10 +401,6 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
 }
 
 // ------------------------------------------- the search with a language model
-constexpr int kMaxLmLayers = ASR_ATT_BEAM_LM_MAX_LAYERS;
-constexpr size_t kLdsLimit = 64 * 1024;
-constexpr int LM_THREADS = 256;
-
 struct LmP {
   // the call
   const float* logits;
@@ -406,12 +409,7 @@ struct LmP {
   const int32_t* lens;
   float alpha, beta;
   int has_lm;                    // 0: no LM term anywhere, q / h / c are not touched
-  // the language model
-  int layers, H, Y;
-  const float* emb;              // [V][Y]
-  const float *w_ih[kMaxLmLayers], *w_hh[kMaxLmLayers];   // [4H][Y or H], [4H][H]
-  const float *b_ih[kMaxLmLayers], *b_hh[kMaxLmLayers];   // [4H]
-  const float *w_out, *b_out;    // [V][H], [V]
+  LmNet net;                     // the language model; net.V is V
   // workspace
   const float* lse;              // [B][T]
   float* topv;                   // [B][W][W + 1] per parent: lp + alpha q, best first
@@ -425,10 +423,6 @@ struct LmP {
   float *h, *c;                  // [B][2W][layers][H] by slot
   float* q;                      // [B][2W][V] by slot: the LM's log-softmax after the entry's prefix
 };
-
-__host__ __device__ inline size_t lm_cell_lds_floats(int Y, int H) {
-  return 2 * (size_t)(Y > H ? Y : H) + H;
-}
 
 __device__ __forceinline__ int lm_class(int c, int blank) { return c - (c > blank ? 1 : 0); }
 
@@ -645,9 +639,9 @@ __global__ void __launch_bounds__(64) lm_select_kernel(int t, LmP p) {
 }
 
 // The LM after an extended entry's new token: the stacked LSTM from the
-// parent's slot (beam_lm_cell's arithmetic, csrc/att_beam.hip), then the output
-// layer and its f32 log-softmax into the entry's row of q.  Entries that stayed
-// (most of them, at most frames) leave at once.  t = -1: the root.
+// parent's slot, then the output layer and its f32 log-softmax into the entry's
+// row of q.  Entries that stayed (most of them, at most frames) leave at once.
+// t = -1: the root.
 __global__ void __launch_bounds__(LM_THREADS) lm_step_kernel(int t, LmP p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float red[4];
@@ -656,65 +650,16 @@ __global__ void __launch_bounds__(LM_THREADS) lm_step_kernel(int t, LmP p) {
   const long long r = (long long)b * p.W + i;
   const int tok = p.tok[r];
   if (tok < 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = LM_THREADS / 64;
-  const int src = p.src[r], dst = p.slot[r];
-  const int H = p.H, XM = max(p.Y, H), V = p.V;
-  float* xa = sm;            // [max(Y, H)]
-  float* xb = xa + XM;       // [max(Y, H)]
-  float* hp = xb + XM;       // [H]
-  for (int y = tid; y < p.Y; y += LM_THREADS) xa[y] = p.emb[(long long)tok * p.Y + y];
-  for (int l = 0; l < p.layers; ++l) {
-    const int in = l == 0 ? p.Y : H;
-    const long long so = (((long long)b * 2 * p.W + dst) * p.layers + l) * H;
-    const long long sp = (((long long)b * 2 * p.W + max(src, 0)) * p.layers + l) * H;
-    for (int j = tid; j < H; j += LM_THREADS) hp[j] = src >= 0 ? p.h[sp + j] : 0.f;
-    __syncthreads();
-    const float* wi_l = p.w_ih[l];
-    const float* wh_l = p.w_hh[l];
-    for (int u = w; u < H; u += nw) {   // one wave per hidden unit, lanes over K
-      float s[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const long long row = (long long)g * H + u;
-        const float* wi = wi_l + row * in;
-        const float* wh = wh_l + row * H;
-        float a = 0.f;
-        for (int k = lane; k < in; k += 64) a += wi[k] * xa[k];
-        for (int k = lane; k < H; k += 64) a += wh[k] * hp[k];
-        s[g] = wave_sum(a) + p.b_ih[l][row] + p.b_hh[l][row];
-      }
-      if (lane == 0) {
-        const float ig = sigmoidf_(s[0]), fg = sigmoidf_(s[1]);
-        const float gg = tanhf_(s[2]), og = sigmoidf_(s[3]);
-        const float cn = fg * (src >= 0 ? p.c[sp + u] : 0.f) + ig * gg;
-        const float hn = og * tanhf_(cn);
-        p.c[so + u] = cn;
-        p.h[so + u] = hn;
-        xb[u] = hn;
-      }
-    }
-    __syncthreads();         // xb is complete; xa and hp are free
-    float* sw = xa;
-    xa = xb;
-    xb = sw;
-  }
-  // xa: the top layer's h
+  const int src = p.src[r], dst = p.slot[r], V = p.V;
+  const long long LH = (long long)p.net.layers * p.net.H;
+  const long long so = ((long long)b * 2 * p.W + dst) * LH;
+  const long long sp = ((long long)b * 2 * p.W + max(src, 0)) * LH;
+  const float* h = lm_lstm_step(p.net, tok, src >= 0 ? p.h + sp : nullptr,
+                                src >= 0 ? p.c + sp : nullptr, p.h + so, p.c + so, sm);
   float* q = p.q + ((long long)b * 2 * p.W + dst) * V;
-  float mx = neg_inf();
-  for (int v = w; v < V; v += nw) {        // one wave per class
-    const float* wr = p.w_out + (long long)v * H;
-    float s = 0.f;
-    for (int k = lane; k < H; k += 64) s += wr[k] * xa[k];
-    s = wave_sum(s) + p.b_out[v];
-    if (lane == 0) q[v] = s;
-    mx = fmaxf(mx, s);
-  }
-  mx = group_max<4>(mx, red);              // its barriers also publish q to the work-group
-  float se = 0.f;
-  for (int v = tid; v < V; v += LM_THREADS) se += expf(q[v] - mx);
-  se = group_sum<4>(se, red);
-  const float lse = logf(se);
-  for (int v = tid; v < V; v += LM_THREADS) q[v] = (q[v] - mx) - lse;
+  float mx, lse;
+  lm_output_lse<wave_sum_xor>(p.net, h, q, red, mx, lse);
+  for (int v = threadIdx.x; v < V; v += LM_THREADS) q[v] = (q[v] - mx) - lse;
 }
 
 // After the last frame: the entries re-ranked by S_T + alpha lp_lm(<eos> | l)
@@ -778,30 +723,30 @@ extern "C" size_t asr_ctc_beam_ws_bytes(int T, int B, int V, int beam_width) {
   return beam_ws(T, B, V, beam_width).total;
 }
 
-static int beam_launch(const float* logits, long long stride_t, long long stride_b, int T, int B,
-                       int V, const int32_t* lens, int blank, int beam_width, int normalize,
-                       void* ws, size_t ws_bytes, int32_t* hyps, int32_t* hyp_lens, float* scores,
-                       bool search, void* stream) {
-  ASR_REQUIRE(logits && lens && ws && (!search || (hyps && hyp_lens && scores)), ASR_ERR_ARG,
-              "ctc_beam_search: null pointer");
-  ASR_REQUIRE(T > 0 && B > 0, ASR_ERR_ARG, "ctc_beam_search: bad shape");
-  ASR_REQUIRE(V >= 2, ASR_ERR_ARG, "ctc_beam_search: V = %d < 2", V);
+// what both searches ask of their arguments, and of the workspace once its size is known
+static int beam_args_check(const char* who, bool pointers, int T, int B, int V, int blank,
+                           int beam_width) {
+  ASR_REQUIRE(pointers, ASR_ERR_ARG, "%s: null pointer", who);
+  ASR_REQUIRE(T > 0 && B > 0, ASR_ERR_ARG, "%s: bad shape", who);
+  ASR_REQUIRE(V >= 2, ASR_ERR_ARG, "%s: V = %d < 2", who, V);
   ASR_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, ASR_ERR_ARG,
-              "ctc_beam_search: beam_width = %d outside [1, %d]", beam_width, kMaxBeam);
-  ASR_REQUIRE(blank >= 0 && blank < V, ASR_ERR_ARG, "ctc_beam_search: blank = %d outside [0, %d)",
-              blank, V);
-  const BeamWs w = beam_ws(T, B, V, beam_width);
-  ASR_REQUIRE(ws_bytes >= w.total, ASR_ERR_WORKSPACE, "ctc_beam_search: workspace %zu < %zu bytes",
-              ws_bytes, w.total);
-  ASR_REQUIRE(((uintptr_t)ws & 15) == 0, ASR_ERR_ARG, "ctc_beam_search: workspace not 16-B aligned");
-  char* base = (char*)ws;
-  float* lse = (float*)(base + w.lse);
-  float* topv = (float*)(base + w.topv);
-  int32_t* topc = (int32_t*)(base + w.topc);
-  Node* pool = (Node*)(base + w.pool);
+              "%s: beam_width = %d outside [1, %d]", who, beam_width, kMaxBeam);
+  ASR_REQUIRE(blank >= 0 && blank < V, ASR_ERR_ARG, "%s: blank = %d outside [0, %d)", who, blank, V);
+  return ASR_OK;
+}
+
+static int beam_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+  ASR_REQUIRE(ws_bytes >= need, ASR_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes,
+              need);
+  ASR_REQUIRE(((uintptr_t)ws & 15) == 0, ASR_ERR_ARG, "%s: workspace not 16-B aligned", who);
+  return ASR_OK;
+}
+
+// pass 1: the log-sum-exp of every frame and its K best non-blank classes (K == 0: none)
+static void launch_rows(const float* logits, long long stride_t, long long stride_b, int T, int B,
+                        int V, const int32_t* lens, int blank, int K, int normalize, float* lse,
+                        float* topv, int32_t* topc, hipStream_t s) {
   const long long frames = (long long)B * T;
-  const int K = beam_width + 1;
-  hipStream_t s = (hipStream_t)stream;
   if (V <= kWaveModeMaxV) {
     hipLaunchKernelGGL(beam_rows_kernel<1>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s,
                        logits, stride_t, stride_b, T, B, V, lens, blank, K, normalize, lse, topv,
@@ -810,6 +755,26 @@ static int beam_launch(const float* logits, long long stride_t, long long stride
     hipLaunchKernelGGL(beam_rows_kernel<4>, dim3((unsigned)frames), dim3(256), 0, s, logits,
                        stride_t, stride_b, T, B, V, lens, blank, K, normalize, lse, topv, topc);
   }
+}
+
+static int beam_launch(const float* logits, long long stride_t, long long stride_b, int T, int B,
+                       int V, const int32_t* lens, int blank, int beam_width, int normalize,
+                       void* ws, size_t ws_bytes, int32_t* hyps, int32_t* hyp_lens, float* scores,
+                       bool search, void* stream) {
+  const char* who = "ctc_beam_search";
+  int rc = beam_args_check(who, logits && lens && ws && (!search || (hyps && hyp_lens && scores)),
+                           T, B, V, blank, beam_width);
+  if (rc != ASR_OK) return rc;
+  const BeamWs w = beam_ws(T, B, V, beam_width);
+  if ((rc = beam_ws_check(who, ws, ws_bytes, w.total)) != ASR_OK) return rc;
+  char* base = (char*)ws;
+  float* lse = (float*)(base + w.lse);
+  float* topv = (float*)(base + w.topv);
+  int32_t* topc = (int32_t*)(base + w.topc);
+  Node* pool = (Node*)(base + w.pool);
+  hipStream_t s = (hipStream_t)stream;
+  launch_rows(logits, stride_t, stride_b, T, B, V, lens, blank, beam_width + 1, normalize, lse, topv,
+              topc, s);
   ASR_LAUNCH_CHECK();
   if (!search) return ASR_OK;
   hipLaunchKernelGGL(beam_search_kernel, dim3(B), dim3(64), 0, s, logits, stride_t, stride_b, T, V,
@@ -872,17 +837,8 @@ inline LmBeamWs lm_beam_ws(int T, int B, int V, int W, int layers, int H) {
   return w;
 }
 
-// the LM's shape limits, as asr_att_beam_decode_lm's
-int lm_beam_check(int layers, int H, int Y) {
-  ASR_REQUIRE(layers >= 1 && H > 0 && Y > 0, ASR_ERR_ARG, "ctc_beam_search_lm: bad LM dims (layers "
-              "%d, H %d, Y %d)", layers, H, Y);
-  ASR_REQUIRE(layers <= kMaxLmLayers, ASR_ERR_UNSUPPORTED, "ctc_beam_search_lm: %d LM layers > %d",
-              layers, kMaxLmLayers);
-  const size_t lc = lm_cell_lds_floats(Y, H) * 4;
-  ASR_REQUIRE(lc <= kLdsLimit, ASR_ERR_UNSUPPORTED, "ctc_beam_search_lm: LDS need (lm cell %zu B) "
-              "> %zu B", lc, kLdsLimit);
-  return ASR_OK;
-}
+constexpr LmWho kLmWho = {"ctc_beam_search_lm", "ctc_beam_search_lm", "LM dims", "CTC head",
+                          " (blank included; <eos> takes the blank's place)"};
 
 }  // namespace
 }  // namespace asr
@@ -891,7 +847,7 @@ extern "C" size_t asr_ctc_beam_lm_ws_bytes(int T, int B, int V, int beam_width, 
                                            int lm_H, int lm_Y) {
   if (!beam_args_ok(T, B, V, beam_width)) return 0;
   if (lm_layers == 0) return lm_beam_ws(T, B, V, beam_width, 0, 0).total;
-  if (lm_beam_check(lm_layers, lm_H, lm_Y) != ASR_OK) return 0;
+  if (lm_net_shape_check(lm_layers, lm_H, lm_Y, kLmWho) != ASR_OK) return 0;
   return lm_beam_ws(T, B, V, beam_width, lm_layers, lm_H).total;
 }
 
@@ -900,38 +856,21 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
                                       int beam_width, int normalize, const asr_att_beam_lm_t* lm,
                                       double beta, void* ws, size_t ws_bytes, int32_t* hyps,
                                       int32_t* hyp_lens, float* scores, void* stream) {
-  ASR_REQUIRE(logits && lens && ws && hyps && hyp_lens && scores, ASR_ERR_ARG,
-              "ctc_beam_search_lm: null pointer");
-  ASR_REQUIRE(T > 0 && B > 0, ASR_ERR_ARG, "ctc_beam_search_lm: bad shape");
-  ASR_REQUIRE(V >= 2, ASR_ERR_ARG, "ctc_beam_search_lm: V = %d < 2", V);
-  ASR_REQUIRE(beam_width >= 1 && beam_width <= kMaxBeam, ASR_ERR_ARG,
-              "ctc_beam_search_lm: beam_width = %d outside [1, %d]", beam_width, kMaxBeam);
-  ASR_REQUIRE(blank >= 0 && blank < V, ASR_ERR_ARG,
-              "ctc_beam_search_lm: blank = %d outside [0, %d)", blank, V);
+  const char* who = "ctc_beam_search_lm";
+  int rc = beam_args_check(who, logits && lens && ws && hyps && hyp_lens && scores, T, B, V, blank,
+                           beam_width);
+  if (rc != ASR_OK) return rc;
   ASR_REQUIRE(beta == beta && fabs(beta) <= 3.0e38, ASR_ERR_ARG,
               "ctc_beam_search_lm: beta = %g is not finite", beta);
   if (lm) {
     ASR_REQUIRE(lm->weight >= 0.0 && lm->weight <= 3.0e38, ASR_ERR_ARG,
                 "ctc_beam_search_lm: weight = %g is negative or not finite", lm->weight);
-    ASR_REQUIRE(lm->V == V, ASR_ERR_ARG, "ctc_beam_search_lm: the LM has %d classes, the CTC "
-                "head %d (blank included; <eos> takes the blank's place)", lm->V, V);
-    const int lrc = lm_beam_check(lm->layers, lm->H, lm->Y);
-    if (lrc != ASR_OK) return lrc;
-    ASR_REQUIRE(lm->cell == ASR_ATT_BEAM_CELL_LSTM, ASR_ERR_UNSUPPORTED,
-                "ctc_beam_search_lm: only an LSTM language model runs on the device (cell %d)",
-                lm->cell);
-    ASR_REQUIRE(lm->emb && lm->w_out && lm->b_out, ASR_ERR_ARG, "ctc_beam_search_lm: null pointer");
-    for (int l = 0; l < lm->layers; ++l)
-      ASR_REQUIRE(lm->w_ih[l] && lm->w_hh[l] && lm->b_ih[l] && lm->b_hh[l], ASR_ERR_ARG,
-                  "ctc_beam_search_lm: null pointer (layer %d)", l);
+    if ((rc = lm_net_check(lm, V, kLmWho)) != ASR_OK) return rc;
     if (lm->weight == 0.0) lm = nullptr;      // the LM term is absent
   }
   const int W = beam_width;
   const LmBeamWs w = lm_beam_ws(T, B, V, W, lm ? lm->layers : 0, lm ? lm->H : 0);
-  ASR_REQUIRE(ws_bytes >= w.total, ASR_ERR_WORKSPACE,
-              "ctc_beam_search_lm: workspace %zu < %zu bytes", ws_bytes, w.total);
-  ASR_REQUIRE(((uintptr_t)ws & 15) == 0, ASR_ERR_ARG,
-              "ctc_beam_search_lm: workspace not 16-B aligned");
+  if ((rc = beam_ws_check(who, ws, ws_bytes, w.total)) != ASR_OK) return rc;
   char* base = (char*)ws;
   LmP p = {};
   p.logits = logits; p.st = stride_t; p.sb = stride_b;
@@ -939,14 +878,7 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   p.alpha = lm ? (float)lm->weight : 0.f;
   p.beta = (float)beta;
   p.has_lm = lm ? 1 : 0;
-  if (lm) {
-    p.layers = lm->layers; p.H = lm->H; p.Y = lm->Y;
-    p.emb = lm->emb; p.w_out = lm->w_out; p.b_out = lm->b_out;
-    for (int l = 0; l < lm->layers; ++l) {
-      p.w_ih[l] = lm->w_ih[l]; p.w_hh[l] = lm->w_hh[l];
-      p.b_ih[l] = lm->b_ih[l]; p.b_hh[l] = lm->b_hh[l];
-    }
-  }
+  if (lm) p.net = lm_net_from(lm);
   float* lse = (float*)(base + w.lse);
   p.lse = lse;
   p.topv = (float*)(base + w.topv); p.topc = (int32_t*)(base + w.topc);
@@ -961,21 +893,13 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   p.h = (float*)(base + w.h); p.c = (float*)(base + w.c); p.q = (float*)(base + w.q);
 
   hipStream_t s = (hipStream_t)stream;
-  const long long frames = (long long)B * T;
   // the acoustic log-sum-exp of every frame, once (K = 0: no class ranking)
-  if (V <= kWaveModeMaxV) {
-    hipLaunchKernelGGL(beam_rows_kernel<1>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s,
-                       logits, stride_t, stride_b, T, B, V, lens, blank, 0, normalize, lse,
-                       (float*)nullptr, (int32_t*)nullptr);
-  } else {
-    hipLaunchKernelGGL(beam_rows_kernel<4>, dim3((unsigned)frames), dim3(256), 0, s, logits,
-                       stride_t, stride_b, T, B, V, lens, blank, 0, normalize, lse,
-                       (float*)nullptr, (int32_t*)nullptr);
-  }
+  launch_rows(logits, stride_t, stride_b, T, B, V, lens, blank, 0, normalize, lse, nullptr, nullptr,
+              s);
   ASR_LAUNCH_CHECK();
   hipLaunchKernelGGL(lm_init_kernel, dim3(B), dim3(64), 0, s, p);
   ASR_LAUNCH_CHECK();
-  const size_t lds_step = lm ? lm_cell_lds_floats(p.Y, p.H) * 4 : 0;
+  const size_t lds_step = lm ? lm_cell_lds_floats(lm->Y, lm->H) * 4 : 0;
   if (lm) {
     hipLaunchKernelGGL(lm_step_kernel, dim3(1, B), dim3(LM_THREADS), lds_step, s, -1, p);
     ASR_LAUNCH_CHECK();

@@ -1065,6 +1065,27 @@ def att_decode_greedy(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_h
 _att_beam = {'path': None, 'ws': {}}
 
 
+def _lm_struct(lm, who):
+    """(asr_att_beam_lm_t of the lm dict -- cell, weight, emb, the per-layer lists
+    w_ih / w_hh / b_ih / b_hh, w_out, b_out --, the tensors it points into: keep
+    them until the call has been issued); who prefixes the ValueErrors."""
+    if float(lm['weight']) < 0:
+        raise ValueError('%s: lm weight = %r is negative' % (who, lm['weight']))
+    if lm['cell'] not in ('lstm', 'gru'):
+        raise ValueError("%s: lm cell = %r is not 'lstm' or 'gru'" % (who, lm['cell']))
+    nl = N.ATT_BEAM_LM_MAX_LAYERS
+    lk = [[t.contiguous().float() for t in lm[k][:nl]] for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')]
+    lo = [lm[k].contiguous().float() for k in ('emb', 'w_out', 'b_out')]
+    N.require_device(*(lo + [t for ts in lk for t in ts]))
+    arr = lambda ts: (N.c_vp * nl)(*[t.data_ptr() for t in ts])   # noqa: E731
+    lms = N.AttBeamLm(len(lm['w_ih']), int(lm['w_hh'][0].shape[1]), int(lo[0].shape[1]),
+                      int(lo[0].shape[0]),
+                      N.ATT_BEAM_CELL_GRU if lm['cell'] == 'gru' else N.ATT_BEAM_CELL_LSTM,
+                      lo[0].data_ptr(), arr(lk[0]), arr(lk[1]), arr(lk[2]), arr(lk[3]),
+                      lo[1].data_ptr(), lo[2].data_ptr(), float(lm['weight']))
+    return lms, (lk, lo)
+
+
 def last_att_beam_path():
     """'device' or 'host': what the last AttentionSeq2seq beam decode ran on
     (None before the first one); tests read it."""
@@ -1083,12 +1104,12 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     attention_seq2seq.py:1038-1237, bahdanau order): every utterance over its
     own lens[b] frames, f32 in both compute modes, no host read inside the
     step loop.  gen as att_decode_greedy.  ctc_weight > 0: the joint
-    CTC/attention search (asr_att_beam_decode_ctc) on ctc_logits [B, T, Vc],
+    CTC/attention search (the call's ex->ctc) on ctc_logits [B, T, Vc],
     the raw f32 logits of the CTC head (blank 0, attention class c is CTC class
-    c + 1); ctc_weight == 0 is the plain search.  cell: 'lstm' (w_ih [4D, .],
-    the calls above), or 'gru' for a GRUCell decoder (w_ih [3D, .], gate rows r,
-    z, n; asr_att_beam_decode_ex, plain or joint).  lm: shallow fusion with a
-    language model (asr_att_beam_decode_lm), a dict of cell ('lstm'; 'gru' is
+    c + 1); ctc_weight == 0 is the plain search.  cell: 'lstm' (w_ih [4D, .]),
+    or 'gru' for a GRUCell decoder (w_ih [3D, .], gate rows r, z, n; ex->cell,
+    plain or joint).  lm: shallow fusion with a
+    language model (ex->lm), a dict of cell ('lstm'; 'gru' is
     refused: None), weight (>= 0; 0 is the search without it), emb [V, Y], the
     per-layer lists w_ih / w_hh / b_ih / b_hh, w_out [V, H] and b_out [V], all
     f32 on the device; an LM of another V raises.  Returns (tokens int64 [B, max_len],
@@ -1126,20 +1147,16 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
             raise ValueError('att_decode_beam: ctc_logits %s is not [%d, %d, Vc]'
                              % (tuple(ctc_logits.shape), B, T))
         N.require_device(ctc_logits)
-    if lm is not None and float(lm['weight']) < 0:
-        raise ValueError('att_decode_beam: lm weight = %r is negative' % (lm['weight'],))
     if lm is not None and float(lm['weight']) == 0:
         lm = None
-    if lm is not None:
-        if lm['cell'] not in ('lstm', 'gru'):
-            raise ValueError("att_decode_beam: lm cell = %r is not 'lstm' or 'gru'" % (lm['cell'],))
-        lm_layers = len(lm['w_ih'])
-        lm_H, lm_Y = int(lm['w_hh'][0].shape[1]), int(lm['emb'].shape[1])
-        nb = N.query('asr_att_beam_lm_ws_bytes', ctypes.byref(dims), W, int(V), int(emb_dim),
-                     int(Dz), max_len, None, lm_layers, lm_H, lm_Y)
-    else:
-        nb = N.query('asr_att_beam_ctc_ws_bytes' if lam > 0 else 'asr_att_beam_ws_bytes',
-                     ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz), max_len, None)
+    lms, lm_keep = _lm_struct(lm, 'att_decode_beam') if lm is not None else (None, None)
+    ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) if lam > 0 \
+        else None
+    ex = N.AttBeamEx(N.ATT_BEAM_CELL_GRU if cell == 'gru' else N.ATT_BEAM_CELL_LSTM,
+                     ctypes.addressof(ctc) if ctc is not None else None,
+                     ctypes.addressof(lms) if lms is not None else None)
+    nb = N.query('asr_att_beam_ws_bytes', ctypes.byref(dims), W, int(V), int(emb_dim), int(Dz),
+                 max_len, ctypes.byref(ex))
     if nb == 0:
         return None
     ws = _att_beam['ws'].get(dev)
@@ -1159,43 +1176,16 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
     scores = torch.empty(B, dtype=torch.float64, device=dev)
     aw = torch.empty(B, max_len, T, dtype=torch.float32, device=dev)
     h0c = h0.contiguous().float() if h0 is not None else None
-    tail = (N.ptr(enc), N.ptr(enc_a), N.ptr(lens_d), N.ptr(h0c), N.ptr(ws), ws.numel(),
-            N.ptr(tokens), N.ptr(hl), N.ptr(scores), N.ptr(aw), N.stream_handle(dev))
-    if lm is not None:
-        fn = 'asr_att_beam_decode_lm'
-        nl = N.ATT_BEAM_LM_MAX_LAYERS
-        lk = [[t.contiguous().float() for t in lm[k][:nl]] for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')]
-        lo = [lm[k].contiguous().float() for k in ('emb', 'w_out', 'b_out')]
-        N.require_device(*(lo + [t for ts in lk for t in ts]))
-        arr = lambda ts: (N.c_vp * nl)(*[t.data_ptr() for t in ts])   # noqa: E731
-        lms = N.AttBeamLm(lm_layers, lm_H, lm_Y, int(lo[0].shape[0]),
-                          N.ATT_BEAM_CELL_GRU if lm['cell'] == 'gru' else N.ATT_BEAM_CELL_LSTM,
-                          lo[0].data_ptr(), arr(lk[0]), arr(lk[1]), arr(lk[2]), arr(lk[3]),
-                          lo[1].data_ptr(), lo[2].data_ptr(), float(lm['weight']))
-        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) \
-            if lam > 0 else None
-        ex = N.AttBeamEx(N.ATT_BEAM_CELL_GRU if cell == 'gru' else N.ATT_BEAM_CELL_LSTM,
-                         ctypes.addressof(ctc) if ctc is not None else None)
-        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ex),
-                                  ctypes.byref(lms), *tail)
-    elif cell == 'gru':
-        fn = 'asr_att_beam_decode_ex'
-        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam) \
-            if lam > 0 else None
-        ex = N.AttBeamEx(N.ATT_BEAM_CELL_GRU, ctypes.addressof(ctc) if ctc is not None else None)
-        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ex), *tail)
-    elif lam > 0:
-        fn = 'asr_att_beam_decode_ctc'
-        ctc = N.AttBeamCtc(ctc_logits.data_ptr(), int(ctc_logits.shape[2]), 0, 1, lam)
-        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ctc), *tail)
-    else:
-        fn = 'asr_att_beam_decode'
-        rc = getattr(N.lib(), fn)(ctypes.byref(dims), ctypes.byref(opts), *tail)
+    rc = N.lib().asr_att_beam_decode(
+        ctypes.byref(dims), ctypes.byref(opts), ctypes.byref(ex), N.ptr(enc), N.ptr(enc_a),
+        N.ptr(lens_d), N.ptr(h0c), N.ptr(ws), ws.numel(), N.ptr(tokens), N.ptr(hl), N.ptr(scores),
+        N.ptr(aw), N.stream_handle(dev))
+    del lm_keep
     if rc == N.ASR_ERR_UNSUPPORTED:
         return None
     if rc != N.ASR_OK:
-        raise N.NativeError('%s failed (rc=%d): %s'
-                            % (fn, rc, N.lib().asr_last_error().decode(errors='replace')))
+        raise N.NativeError('asr_att_beam_decode failed (rc=%d): %s'
+                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
     return tokens, hl, scores, aw
 
 
@@ -3041,14 +3031,10 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, 
     B, T, V = logits.shape
     dev = logits.device
     W, beta = int(beam_width), float(beta)
-    if lm is not None:
-        if float(lm['weight']) < 0:
-            raise ValueError('ctc_beam_search: lm weight = %r is negative' % (lm['weight'],))
-        if lm['cell'] not in ('lstm', 'gru'):
-            raise ValueError("ctc_beam_search: lm cell = %r is not 'lstm' or 'gru'" % (lm['cell'],))
-        if int(lm['emb'].shape[0]) != V or int(lm['w_out'].shape[0]) != V:
-            raise ValueError('ctc_beam_search: the LM has %d classes, the CTC head %d (blank '
-                             'included; <eos> takes its place)' % (lm['w_out'].shape[0], V))
+    lms, keep = _lm_struct(lm, 'ctc_beam_search') if lm is not None else (None, None)
+    if lm is not None and (int(lm['emb'].shape[0]) != V or int(lm['w_out'].shape[0]) != V):
+        raise ValueError('ctc_beam_search: the LM has %d classes, the CTC head %d (blank '
+                         'included; <eos> takes its place)' % (lm['w_out'].shape[0], V))
     if not np.isfinite(beta):
         raise ValueError('ctc_beam_search: beta = %r is not finite' % (beta,))
     hyps = torch.empty(B, T, dtype=torch.int32, device=dev)
@@ -3065,21 +3051,8 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, 
                N.ptr(scores), N.stream_handle(dev))
         _ctc_beam['path'] = 'device'
         return hyps, hl, scores
-    lms, keep = None, None
-    if lm is not None:
-        nl = N.ATT_BEAM_LM_MAX_LAYERS
-        lm_layers = len(lm['w_ih'])
-        lm_H, lm_Y = int(lm['w_hh'][0].shape[1]), int(lm['emb'].shape[1])
-        lk = [[t.contiguous().float() for t in lm[k][:nl]] for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')]
-        lo = [lm[k].contiguous().float() for k in ('emb', 'w_out', 'b_out')]
-        N.require_device(*(lo + [t for ts in lk for t in ts]))
-        keep = (lk, lo)
-        arr = lambda ts: (N.c_vp * nl)(*[t.data_ptr() for t in ts])   # noqa: E731
-        lms = N.AttBeamLm(lm_layers, lm_H, lm_Y, int(lo[0].shape[0]),
-                          N.ATT_BEAM_CELL_GRU if lm['cell'] == 'gru' else N.ATT_BEAM_CELL_LSTM,
-                          lo[0].data_ptr(), arr(lk[0]), arr(lk[1]), arr(lk[2]), arr(lk[3]),
-                          lo[1].data_ptr(), lo[2].data_ptr(), float(lm['weight']))
-        nb = N.query('asr_ctc_beam_lm_ws_bytes', T, B, V, W, lm_layers, lm_H, lm_Y)
+    if lms is not None:
+        nb = N.query('asr_ctc_beam_lm_ws_bytes', T, B, V, W, lms.layers, lms.H, lms.Y)
         if nb == 0 and 1 <= W <= 64:
             return None                  # the LM's shape is outside the kernels' limits
     else:

@@ -167,8 +167,16 @@ def test_joint_workspace_adds_the_prefix_state():
     from pytorch_end2end_speech_recognition_amd import _native as N
     B, T, W = 32, 250, 10
     d = N.AttDecDims(B, T, 640, 128, 10, 201, 320, 1, 1.0, 0)
+    ctc = N.AttBeamCtc(None, 30, 0, 1, 0.3)
+    ex = ctypes.byref(N.AttBeamEx(N.ATT_BEAM_CELL_LSTM, ctypes.addressof(ctc), None))
     plain = N.query('asr_att_beam_ws_bytes', ctypes.byref(d), W, 29, 64, 256, 100, None)
-    joint = N.query('asr_att_beam_ctc_ws_bytes', ctypes.byref(d), W, 29, 64, 256, 100, None)
+    joint = N.query('asr_att_beam_ws_bytes', ctypes.byref(d), W, 29, 64, 256, 100, ex)
     add = 2 * B * T * 4 + (4 * B * W * T + 2 * B * W + 2 * B * W * W) * 8
     assert plain > 0 and add <= joint - plain <= add + 8 * 256
-    assert N.query('asr_att_beam_ctc_ws_bytes', ctypes.byref(d), 33, 29, 64, 256, 100, None) == 0
+    assert N.query('asr_att_beam_ws_bytes', ctypes.byref(d), 33, 29, 64, 256, 100, ex) == 0
+    # the byte counts of asr_att_beam_ws_bytes / asr_att_beam_ctc_ws_bytes before the two
+    # queries became one (recorded from that build at these shapes)
+    assert (plain, joint) == (35617024, 38297344)
+    # an ex without either optional part is the plain query
+    none = ctypes.byref(N.AttBeamEx(N.ATT_BEAM_CELL_GRU, None, None))
+    assert N.query('asr_att_beam_ws_bytes', ctypes.byref(d), W, 29, 64, 256, 100, none) == plain

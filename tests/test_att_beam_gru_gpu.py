@@ -1,8 +1,8 @@
 """Attention beam search on the device for GRU decoders (beam_cell_gru in
-csrc/att_beam.hip, asr_att_beam_decode_ex, native_ops.att_decode_beam(cell='gru'))
+csrc/att_beam.hip, asr_att_beam_decode with ex->cell, native_ops.att_decode_beam(cell='gru'))
 against the host path (ASR_ATT_BEAM=host) on small random models, against a
 fixture recorded from the reference, through error_rate, the hierarchical model
-and both compute modes, and the new C entry point against the old ones.
+and both compute modes, and the C entry point with and without its ex argument.
 
 Cases, seeds, lengths and the margin rule are tests/test_att_beam_gru_cpu.py's:
 an utterance whose host-side decision margin (_gaps) is below GAP = 1e-3 is left
@@ -263,17 +263,18 @@ def _lstm_w2():
 
 
 def _through_ex(monkeypatch, cell):
-    """Route native_ops' asr_att_beam_decode calls through asr_att_beam_decode_ex
-    with `cell` and a null ctc: the same arguments otherwise, bit for bit."""
+    """Route native_ops' asr_att_beam_decode calls through the same entry point
+    with ex = {cell, NULL, NULL} (cell None: ex = NULL) in place of its ex: the
+    same arguments otherwise, bit for bit."""
     from pytorch_end2end_speech_recognition_amd import _native as N
     lib = N.lib()
-    real_ex = lib.asr_att_beam_decode_ex
+    real = lib.asr_att_beam_decode
     calls = []
 
-    def shim(dims, opts, *tail):
-        ex = N.AttBeamEx(cell, None)
+    def shim(dims, opts, _ex, *tail):
+        ex = N.AttBeamEx(cell, None, None) if cell is not None else None
         calls.append(cell)
-        return real_ex(dims, opts, ctypes.byref(ex), *tail)
+        return real(dims, opts, ctypes.byref(ex) if ex is not None else None, *tail)
     monkeypatch.setattr(lib, 'asr_att_beam_decode', shim, raising=False)
     return calls
 
@@ -284,8 +285,10 @@ def test_ex_entry_with_lstm_cell_is_bitwise_the_old_entry(monkeypatch, cuda_dev)
     native_ops.set_compute_dtype('fp32')
     L, model, o = _lstm_w2()
     enc = L._enc()
+    _through_ex(monkeypatch, None)            # ex = NULL
     h0, aw0, s0, path = L._decode(model, enc, 'device', **o)
     assert path == 'device'
+    monkeypatch.undo()
     calls = _through_ex(monkeypatch, N.ATT_BEAM_CELL_LSTM)
     h1, aw1, s1, path = L._decode(model, enc, 'device', **o)
     assert path == 'device' and calls == [N.ATT_BEAM_CELL_LSTM]

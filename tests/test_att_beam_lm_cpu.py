@@ -174,15 +174,29 @@ def test_lm_workspace_adds_state_logits_and_candidate_terms():
     from pytorch_end2end_speech_recognition_amd import _native as N
     B, T, W, V, layers, H = 32, 250, 10, 29, 2, 512
     d = N.AttDecDims(B, T, 640, 128, 10, 201, 320, 1, 1.0, 0)
-    q = (ctypes.byref(d), W, V, 64, 256, 100, None)
-    joint = N.query('asr_att_beam_ctc_ws_bytes', *q)
-    lm = N.query('asr_att_beam_lm_ws_bytes', *(q + (layers, H, 512)))
+    q = (ctypes.byref(d), W, V, 64, 256, 100)
+    ctc = N.AttBeamCtc(None, 30, 0, 1, 0.3)
+
+    def query(lm_dims, with_ctc=False):
+        """The query reads ctc != NULL, lm != NULL and the LM's layers / H / Y only."""
+        lm = N.AttBeamLm(*lm_dims) if lm_dims else None
+        ex = N.AttBeamEx(N.ATT_BEAM_CELL_LSTM, ctypes.addressof(ctc) if with_ctc else None,
+                         ctypes.addressof(lm) if lm is not None else None)
+        return N.query('asr_att_beam_ws_bytes', *(q + (ctypes.byref(ex),)))
+    joint = query(None, with_ctc=True)
+    lm = query((layers, H, 512))
     Rw = B * W
     add = (4 * Rw * layers * H + Rw * V + Rw * W) * 4
     assert joint > 0 and add <= lm - joint <= add + 4 * 256
     # the documented refusals: more than 4 layers, the cell's LDS need above 64 KiB
-    assert N.query('asr_att_beam_lm_ws_bytes', *(q + (5, H, 512))) == 0
-    assert N.query('asr_att_beam_lm_ws_bytes', *(q + (1, 6000, 512))) == 0
+    assert query((5, H, 512)) == 0
+    assert query((1, 6000, 512)) == 0
     # 2 max(Y, H) + H floats: 65 532 B fits, 65 544 B does not
-    assert N.query('asr_att_beam_lm_ws_bytes', *(q + (1, 5461, 5461))) > 0
-    assert N.query('asr_att_beam_lm_ws_bytes', *(q + (1, 5462, 5462))) == 0
+    assert query((1, 5461, 5461)) > 0
+    assert query((1, 5462, 5462)) == 0
+    # the byte counts of asr_att_beam_ws_bytes / _ctc_ws_bytes / _lm_ws_bytes before the
+    # three queries became one (recorded from that build at these shapes); the LM's size
+    # holds the joint search's part whatever lambda is
+    plain = N.query('asr_att_beam_ws_bytes', *(q + (None,)))
+    assert (plain, joint, lm) == (35617024, 38297344, 43590144)
+    assert query((layers, H, 512), with_ctc=True) == lm
