@@ -475,6 +475,44 @@ int asr_lstm_uni_backward(const float* dy, const void* whh, int w_dtype, const i
                           uint16_t* dgbf, float* db_ih, float* db_hh, void* workspace,
                           size_t ws_bytes, void* stream);
 
+/* ------------------------------------ stateful recurrence (streaming inference)
+ * One chunk of Tc frames of a unidirectional LSTM layer with the state carried
+ * in and out (csrc/lstm_stream.hip): asr_lstm_uni_forward's cell and roundings,
+ * no saved activations.
+ *   gx     [B][Tc][4H] f32, read only: x W_ih^T + b_ih + b_hh, gates i, f, g, o
+ *   whh    [4H][H], w_dtype f32 or bf16 (f32 compute needs f32; a caller that
+ *          feeds many chunks converts W_hh once and passes the bf16 copy)
+ *   lens   int32 [B]: valid frames of row b in this chunk, 0 <= lens[b] <= Tc
+ *          (values outside are clipped to that range)
+ *   h_in, c_in [B][H] f32: the state before the chunk's first frame
+ *   h_out, c_out [B][H] f32: the state after frame lens[b] - 1; h_in[b], c_in[b]
+ *          unchanged where lens[b] == 0
+ *   y      [B][Tc][H] f32: h_t for t < lens[b], 0 for t >= lens[b]
+ * For t >= lens[b] the state is frozen, not zeroed -- the one difference from
+ * asr_lstm_uni_forward -- so a row that ended early, or has no frame in this
+ * chunk, continues from its state in the next one.  The state is always f32.
+ * compute_dtype f32: exact-f32 MFMA.  bf16: h and W_hh rounded to bf16 as MFMA
+ * operands, f32 sums, state and cell math.  Feeding an utterance in chunks
+ * gives, bit for bit, what one call over the whole utterance gives.
+ * Aliasing: h_out must not overlap h_in (step 0 reads all of h_in[b] in every
+ * work-group of row b while h_out[b] is being written): ASR_ERR_ARG.  c_out
+ * may be c_in itself (each c[b][j] has one reader and writer), any other
+ * overlap of the two is ASR_ERR_ARG.  So is every other overlap of an output
+ * (y, h_out, c_out) with another output or with gx, h_in or c_in, and in bf16
+ * mode with H % 8 == 0 an h_in, y or bf16 whh that is not 16-byte aligned.
+ * whh, lens and the workspace must not overlap an output either; that is not
+ * checked.  The step launches are not recorded by the launch profiler.
+ * Accepted shapes: asr_lstm_uni_shape_ok(B, Tc, H); anything else is
+ * ASR_ERR_UNSUPPORTED before any launch, nothing written.  One launch per
+ * frame, ordered by the stream.  workspace: asr_lstm_stream_workspace_bytes(B,
+ * H, compute_dtype); read only in bf16 mode with an f32 whh (the converted
+ * copy), may be NULL otherwise; it need not be zero. */
+size_t asr_lstm_stream_workspace_bytes(int B, int H, int compute_dtype);
+int asr_lstm_stream_forward(const float* gx, const void* whh, int w_dtype, const int32_t* lens,
+                            int B, int Tc, int H, int compute_dtype, const float* h_in,
+                            const float* c_in, float* h_out, float* c_out, float* y,
+                            void* workspace, size_t ws_bytes, void* stream);
+
 /* nn.GRUCell nonlinearity (decoder cells, rnn_decoder.py:91-95): gi = x W_ih^T +
  * b_ih, gh = h W_hh^T + b_hh [B][3D] (GEMMs by the caller); act [B][3D] out =
  * r, z, n; hout = (1 - z) n + z h.  Backward: dgi, dgh [B][3D] (the gate
@@ -597,10 +635,19 @@ int asr_convert_rows_bf16_dropout(const float* src, asr_rowmap_t map, int nrows,
  * asr_row_argmax: out[r] = argmax_v x[r*V + v] (int64; first max on ties).
  * In both, a NaN never wins and the result is always in [0, V): a row / frame
  * of all NaN (or all -inf) gives 0.
+ * asr_ctc_best_path_stream: asr_ctc_best_path on one chunk [B][T] of longer
+ *   utterances.  prev int32 [B], read and written: the label of row b's last
+ *   valid frame so far, -1 before its first frame; a repeat run collapses
+ *   across the chunk boundary through it; left unchanged where lens[b] == 0.
+ *   hyps / hyp_lens hold only the labels this chunk newly emits, so the
+ *   chunks' outputs concatenated are asr_ctc_best_path's on the whole logits.
  */
 int asr_ctc_best_path(const float* logits, long long stride_t, long long stride_b, int T, int B,
                       int V, const int32_t* lens, int blank, int32_t* hyps, int32_t* hyp_lens,
                       void* stream);
+int asr_ctc_best_path_stream(const float* logits, long long stride_t, long long stride_b, int T,
+                             int B, int V, const int32_t* lens, int blank, int32_t* prev,
+                             int32_t* hyps, int32_t* hyp_lens, void* stream);
 int asr_row_argmax(const float* x, int rows, int V, long long* out, void* stream);
 /* asr_ctc_beam_search: CTC prefix beam search (beam_search_decoder.py:22-124
  *   with alpha = beta = 0): per utterance the most probable prefix among the

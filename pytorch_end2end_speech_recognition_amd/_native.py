@@ -111,6 +111,11 @@ SIGNATURES = {
                                      c_vp, c_vp, c_vp, c_size, c_vp]),
     'asr_lstm_uni_backward': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'asr_lstm_stream_workspace_bytes': (c_size, [c_int, c_int, c_int]),
+    'asr_lstm_stream_forward': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'asr_ctc_best_path_stream': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_vp,
+                                         c_vp, c_vp, c_vp]),
     'asr_gru_cell_forward': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     'asr_gru_cell_backward': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
                                       c_vp]),

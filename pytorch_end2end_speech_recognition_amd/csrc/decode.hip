@@ -8,6 +8,11 @@
 // repeats and the blank removal are a wave prefix-sum (ballot + popcount), and
 // the surviving labels are written compactly.  Output: hyps [B][T] (first
 // hyp_lens[b] entries valid), lengths [B].
+// Streaming (asr_ctc_best_path_stream): the same kernel with prev_io [B], the
+// label of the utterance's last valid frame so far (-1 before the first):
+// read as the frame left of this chunk's first one, so a repeat run collapses
+// across the chunk boundary, and written back unless the chunk holds no valid
+// frame of the utterance.
 #include "common.h"
 
 namespace asr {
@@ -21,11 +26,14 @@ __global__ void __launch_bounds__(64) best_path_kernel(const float* __restrict__
                                                        long long st, long long sb, int T, int V,
                                                        const int32_t* __restrict__ lens, int blank,
                                                        int32_t* __restrict__ hyps,
-                                                       int32_t* __restrict__ hyp_lens) {
+                                                       int32_t* __restrict__ hyp_lens,
+                                                       int32_t* __restrict__ prev_io) {
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
   const int Tb = min(lens[b], T);
-  int prev = -1;      // label of the previous frame (for collapsing repeats)
+  // label of the previous frame (for collapsing repeats); prev_io: carried
+  // over from the utterance's earlier chunks
+  int prev = prev_io ? prev_io[b] : -1;
   int count = 0;
   int32_t* out = hyps + (long long)b * T;
   for (int t0 = 0; t0 < Tb; t0 += 64) {
@@ -56,6 +64,7 @@ __global__ void __launch_bounds__(64) best_path_kernel(const float* __restrict__
     prev = __shfl(my_label, nf - 1, 64);
   }
   if (lane == 0) hyp_lens[b] = count;
+  if (prev_io && lane == 0 && Tb > 0) prev_io[b] = prev;
 }
 
 __global__ void row_argmax_kernel(const float* __restrict__ x, int rows, int V,
@@ -87,7 +96,20 @@ extern "C" int asr_ctc_best_path(const float* logits, long long stride_t, long l
   ASR_REQUIRE(logits && lens && hyps && hyp_lens, ASR_ERR_ARG, "best_path: null pointer");
   ASR_REQUIRE(T > 0 && B > 0 && V > 0, ASR_ERR_ARG, "best_path: bad shape");
   hipLaunchKernelGGL(best_path_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logits,
-                     stride_t, stride_b, T, V, lens, blank, hyps, hyp_lens);
+                     stride_t, stride_b, T, V, lens, blank, hyps, hyp_lens, (int32_t*)nullptr);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_best_path_stream(const float* logits, long long stride_t,
+                                        long long stride_b, int T, int B, int V,
+                                        const int32_t* lens, int blank, int32_t* prev,
+                                        int32_t* hyps, int32_t* hyp_lens, void* stream) {
+  ASR_REQUIRE(logits && lens && prev && hyps && hyp_lens, ASR_ERR_ARG,
+              "best_path_stream: null pointer");
+  ASR_REQUIRE(T > 0 && B > 0 && V > 0, ASR_ERR_ARG, "best_path_stream: bad shape");
+  hipLaunchKernelGGL(best_path_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logits,
+                     stride_t, stride_b, T, V, lens, blank, hyps, hyp_lens, prev);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
 }

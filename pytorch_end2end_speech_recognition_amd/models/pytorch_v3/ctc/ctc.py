@@ -42,6 +42,74 @@ def _concatenate_labels_np(ys, y_lens):
     return np.ascontiguousarray(ys[mask]).astype(np.int32)
 
 
+class CTCStream(object):
+    """Chunk-by-chunk greedy recognition with a unidirectional CTC model
+    (CTC.stream): the encoder state (RNNEncoder.forward_chunk) and the label
+    of each row's last frame stay on the device between chunks, so a chunk
+    costs O(chunk), and the chunks' labels concatenated are what
+    ``decode(beam_width=1)`` returns for the whole utterance.
+
+    ``last_logits``: the device logits [B, Tc', V] of the last chunk and
+    ``last_lens_np`` their valid lengths (kept for tests)."""
+
+    def __init__(self, model, batch_size):
+        self._model = model
+        self._state = model.encoder.init_stream(batch_size)
+        self.batch_size = self._state.batch_size
+        self._prev = torch.full((self.batch_size,), -1, dtype=torch.int32,
+                                device=self._state.device)
+        self._emitted = [[] for _ in range(self.batch_size)]
+        self.last_logits = None
+        self.last_lens_np = None
+
+    @torch.no_grad()
+    def feed(self, xs_chunk, chunk_lens, final=False):
+        """xs_chunk [B, Tc, F] (numpy or device tensor), chunk_lens [B]: each
+        row's valid frames in this chunk (0: nothing for that row); final (bool
+        or one per row): the row's utterance ends with this chunk -- required
+        for a chunk length that is no multiple of the encoder's subsampling
+        stride (RNNEncoder.forward_chunk raises ValueError otherwise).  Returns
+        a list of B int64 arrays, the labels this chunk newly emits, in
+        decode()'s index space.  One host read: the labels and their counts.
+        The model must be in eval mode (RuntimeError otherwise)."""
+        model = self._model
+        if model.training:
+            raise RuntimeError('CTCStream.feed runs in eval mode only: the model is in training '
+                               'mode (call model.eval(); after an optimizer step open a new '
+                               'session, its bf16 weight copies would be stale)')
+        xs_d = model.np2var(xs_chunk, dtype='float')
+        xs, lens_d = model.encoder.forward_chunk(xs_d, chunk_lens, self._state, final=final)
+        for i in range(len(model.fc_list)):
+            xs = getattr(model, 'fc_' + str(i))(xs)
+        logits = model.fc_out(xs)
+        if model.logits_temperature != 1:
+            logits = logits * (1.0 / model.logits_temperature)
+        hyps, hl = ops.ctc_best_path_stream(logits, lens_d, self._prev, 0)
+        packed = torch.cat([hl.view(-1, 1), hyps], dim=1).cpu().numpy()
+        self.last_logits = logits
+        self.last_lens_np = self._state.last_lens_np.copy()
+        new = [packed[b, 1:1 + packed[b, 0]].astype(np.int64) - 1 for b in range(self.batch_size)]
+        for b, n in enumerate(new):
+            if len(n):
+                self._emitted[b].append(n)
+        return new
+
+    def hyps(self):
+        """The labels emitted so far, per row (since the row's last reset)."""
+        return [np.concatenate(e) if e else np.zeros(0, np.int64) for e in self._emitted]
+
+    def reset(self, rows=None):
+        """Start a new utterance in `rows` (default: every row): zero encoder
+        state, no previous label, empty hypothesis."""
+        self._state.reset(rows)
+        rows = range(self.batch_size) if rows is None else [int(r) for r in rows]
+        if len(rows):
+            self._prev.index_fill_(0, torch.as_tensor(rows, dtype=torch.int64,
+                                                      device=self._prev.device), -1)
+        for b in rows:
+            self._emitted[b] = []
+
+
 class CTC(ModelBase):
     """The Connectionist Temporal Classification model (ctc.py:72-113)."""
 
@@ -271,6 +339,24 @@ class CTC(ModelBase):
                                              normalize=True)
         best_hyps = np.array([h - 1 for h in best_hyps] + [None], dtype=object)[:-1]
         return best_hyps, None, self.encoder.last_perm_np.copy()
+
+    def stream(self, batch_size):
+        """A CTCStream: chunk-by-chunk greedy recognition of `batch_size`
+        utterances side by side.  Single-task models with a unidirectional LSTM
+        encoder and no conv front-end (RNNEncoder.init_stream names what else
+        is refused); beam search and LM fusion are whole-utterance only.  The
+        model must be in eval mode: RuntimeError otherwise, as forward_chunk."""
+        if hasattr(self, 'main_loss_weight'):
+            raise NotImplementedError('streaming a hierarchical CTC model (its sub-task output) '
+                                      'is not supported')
+        if not hasattr(self.encoder, 'init_stream'):
+            raise NotImplementedError('streaming needs an LSTM encoder, not encoder_type=%s '
+                                      '(a conv front-end\'s context crosses chunk boundaries)'
+                                      % self.encoder_type)
+        st = CTCStream(self, batch_size)      # (refuses an unsupported encoder first)
+        if self.training:
+            raise RuntimeError('CTC.stream runs in eval mode only: call model.eval() first')
+        return st
 
     @eval_retry
     @torch.no_grad()

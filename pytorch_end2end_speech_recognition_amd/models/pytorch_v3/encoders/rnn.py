@@ -31,6 +31,49 @@ from ..linear import LinearND
 from .cnn import CNNEncoder
 
 
+class EncoderStreamState(object):
+    """What RNNEncoder.forward_chunk carries from chunk to chunk: per layer the
+    device state (h, c) [B, H] f32, per row whether its utterance has had its
+    last chunk, and the bf16 copies of W_hh bf16 mode reads (made once, dropped
+    when the model's flat parameter buffer is replaced or its version
+    changes).  ``last_lens_np``: the output lengths of the last chunk."""
+
+    def __init__(self, batch_size, num_layers, num_units, device):
+        self.batch_size = batch_size
+        self.device = device
+        self.h = [torch.zeros(batch_size, num_units, dtype=torch.float32, device=device)
+                  for _ in range(num_layers)]
+        self.c = [torch.zeros_like(h) for h in self.h]
+        self.final = np.zeros(batch_size, bool)
+        self.last_lens_np = np.zeros(batch_size, np.int32)
+        self._whh_bf = {}
+        self._whh_key = None
+
+    def reset(self, rows=None):
+        """Zero state for `rows` (default: all): they start a new utterance."""
+        if rows is None:
+            for t in self.h + self.c:
+                t.zero_()
+            self.final[:] = False
+            return
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if len(rows) and (rows.min() < 0 or rows.max() >= self.batch_size):
+            raise ValueError('reset: rows %s outside [0, %d)' % (rows.tolist(), self.batch_size))
+        idx = torch.from_numpy(rows).to(self.device)
+        for t in self.h + self.c:
+            t.index_fill_(0, idx, 0.0)
+        self.final[rows] = False
+
+    def whh_bf16(self, l, w_hh, flat):
+        key = (id(flat), flat.data_ptr(), flat._version)
+        if key != self._whh_key:
+            self._whh_bf, self._whh_key = {}, key
+        if l not in self._whh_bf:
+            H = w_hh.shape[1]
+            self._whh_bf[l] = ops.convert_rows_bf16(w_hh, ops.rowmap(H), 4 * H, H)
+        return self._whh_bf[l]
+
+
 class RNNEncoder(nn.Module):
 
     def __init__(self, input_size, rnn_type, bidirectional, num_units, num_proj, num_layers,
@@ -283,3 +326,121 @@ class RNNEncoder(nn.Module):
             lens_sub_d = ops.h2d(lens_sub, dev)
             return h, out_lens, h_sub, lens_sub_d, perm_idx
         return h, out_lens, perm_idx
+
+    # ------------------------------------------------------------- streaming
+    @property
+    def stream_stride(self):
+        """S = 2^(number of subsampling layers): input frames per output frame."""
+        return 2 ** int(sum(bool(s) for s in self.subsample_list[:self.num_layers - 1]))
+
+    def init_stream(self, batch_size):
+        """The state of a chunk-by-chunk pass over `batch_size` utterances
+        (forward_chunk), all zero.  Streaming runs unidirectional LSTM encoders
+        without a conv front-end, on either module layout, with projection
+        layers, residual / dense-residual sums and 'drop' / 'concat'
+        subsampling; anything else raises NotImplementedError here."""
+        why = []
+        if self.rnn_type != 'lstm':
+            why.append('rnn_type=%s (only lstm has a stateful recurrence kernel)' % self.rnn_type)
+        if self.bidirectional:
+            why.append('a bidirectional encoder (its reverse pass needs the whole utterance)')
+        if self.conv is not None:
+            why.append('a conv front-end (its context crosses chunk boundaries)')
+        if self.num_layers_sub >= 1:
+            why.append('a sub-task output (num_layers_sub)')
+        if why:
+            raise NotImplementedError('MI355X RNNEncoder: streaming does not support ' +
+                                      '; '.join(why))
+        if int(batch_size) < 1:
+            raise ValueError('init_stream: batch_size %r' % (batch_size,))
+        dev = self._layer_params(0)[0][0].device
+        return EncoderStreamState(int(batch_size), self.num_layers, self.num_units, dev)
+
+    @torch.no_grad()
+    def forward_chunk(self, xs, chunk_lens, state, final=False):
+        """The next chunk of every row's utterance through the encoder, state
+        carried in `state` (init_stream) and updated in place.
+
+        xs: device tensor [B, Tc, input_size]; chunk_lens [B] (host): the valid
+        frames of each row in this chunk, 0 .. Tc (0: the row has nothing in
+        this chunk and keeps its state); final: True / False or a bool per row:
+        this is the last chunk of the row's utterance.  Returns (ys [B, Tc', H]
+        device, out_lens int32 device [B]); ``state.last_lens_np`` is the host
+        copy of out_lens.  Rows keep their order: there is no length sort.
+        Eval mode only (no dropout).
+
+        With S = stream_stride, every chunk_lens[b] must be a multiple of S
+        unless the chunk is final for the row -- a frame pair of a subsampling
+        layer must not straddle two chunks -- and a row that has had its final
+        chunk takes no more frames until state.reset: ValueError before any
+        launch.  Then the chunks' outputs, concatenated per row, are what
+        forward() gives for the whole utterance, with one difference: lengths
+        propagate per row, len // 2 at each subsampling layer, where forward()
+        reproduces the reference's quirk of giving every row the padded length
+        after subsampling (rnn.py:435-439).  The two agree for a single
+        utterance and for rows of equal length."""
+        if self.training:
+            raise RuntimeError('forward_chunk runs in eval mode only (call .eval())')
+        B = state.batch_size
+        lens = np.asarray(chunk_lens).astype(np.int64).reshape(-1)
+        final = np.broadcast_to(np.asarray(final, bool), (B,))
+        S = self.stream_stride
+        if xs.dim() != 3 or xs.shape[0] != B or len(lens) != B:
+            raise ValueError('forward_chunk: xs %s / chunk_lens [%d] for a stream of %d rows'
+                             % (tuple(xs.shape), len(lens), B))
+        if lens.min() < 0 or lens.max() > xs.shape[1]:
+            raise ValueError('forward_chunk: chunk_lens %s outside [0, %d]'
+                             % (lens.tolist(), xs.shape[1]))
+        bad = np.nonzero((lens % S != 0) & ~final)[0]
+        if len(bad):
+            raise ValueError('forward_chunk: chunk_lens %s of rows %s are no multiple of the '
+                             'subsampling stride %d and the chunk is not final for them'
+                             % (lens[bad].tolist(), bad.tolist(), S))
+        bad = np.nonzero(state.final & (lens > 0))[0]
+        if len(bad):
+            raise ValueError('forward_chunk: rows %s have had their final chunk; reset them '
+                             'before feeding a new utterance' % bad.tolist())
+        dev = xs.device
+        owner = self._owner
+        bf16 = ops.compute_dtype() == ops.BF16
+        T = max(int(lens.max()), 1)
+        if xs.shape[1] < T:            # an empty chunk tensor: one padded frame
+            xs = xs.new_zeros(B, T, xs.shape[2])
+        h = xs[:, :T].contiguous()
+        t_mul, t_add, concat = 1, 0, False
+        res_outputs = []
+        lens_d = lens_key = None
+        for l in range(self.num_layers):
+            (w_ih, w_hh, b_ih, b_hh), _ = self._layer_tensors(l)
+            if lens_key is None or not np.array_equal(lens_key, lens):
+                lens_key = lens.copy()
+                lens_d = ops.h2d(lens.astype(np.int32), dev)
+            whh = state.whh_bf16(l, w_hh, owner._flat_param) if bf16 else w_hh
+            h, (state.h[l], state.c[l]) = ops.lstm_stream_layer(
+                h, lens_d, T, w_ih, whh, b_ih, b_hh, (state.h[l], state.c[l]), t_mul=t_mul,
+                t_add=t_add, concat=concat)
+            t_mul, t_add, concat = 1, 0, False
+            if l == self.num_layers - 1 or not (self.residual or self.dense_residual or
+                                                self.num_proj > 0 or self.subsample_list[l]):
+                continue
+            if self.num_proj > 0:
+                h = ops.tanh(getattr(self, 'proj_l%d' % l)(h))
+            if self.subsample_list[l]:
+                # as forward(): read in place by the next layer's input GEMM
+                T, lens = T // 2, lens // 2
+                if T == 0:
+                    # a final chunk shorter than the stride: one padded frame,
+                    # read from a source wide enough for the row map
+                    T = 1
+                    h = torch.cat([h, torch.zeros_like(h)], dim=1)
+                if self.subsample_type == 'drop':
+                    t_mul, t_add = 2, 1
+                else:
+                    t_mul, t_add, concat = 2, 0, True
+            elif (self.residual or self.dense_residual) and l >= self.residual_start_layer - 1:
+                for lower in res_outputs:
+                    h = ops.add(h, lower)
+                res_outputs = [h] if self.residual else res_outputs + [h]
+        state.final = state.final | final
+        state.last_lens_np = lens.astype(np.int32)
+        return h, ops.h2d(state.last_lens_np, dev)

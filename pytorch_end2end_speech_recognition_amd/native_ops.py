@@ -2299,6 +2299,50 @@ def lstm_layer(x_src, lens, T, w_ih, w_hh, b_ih, b_hh, perm=None, t_mul=1, t_add
                              w_ih, w_hh, b_ih, b_hh, *graph_params)
 
 
+@torch.no_grad()
+def lstm_stream_layer(x, lens, Tc, w_ih, w_hh, b_ih, b_hh, state, t_mul=1, t_add=0, concat=False):
+    """One chunk of a unidirectional LSTM layer with carried state (inference;
+    csrc/lstm_stream.hip).  x [B, T_src, Dsrc] f32: row (b, t), t < Tc, of the
+    layer input is x[b, t * t_mul + t_add] (concat: followed by the next frame),
+    LSTMLayerFn.forward's input-projection GEMM and row map without a perm.
+    lens int32 [B] on the device: valid frames of each row in this chunk (0 ..
+    Tc).  state = (h, c), [B, H] f32, the state before the chunk; w_hh f32, or
+    in bf16 mode a bf16 copy made once by the caller.  Returns (y [B, Tc, H],
+    (h, c) after each row's last valid frame): y is 0 and the state frozen for
+    t >= lens[b], so feeding an utterance in chunks gives what feeding it
+    whole gives.  The returned state never shares memory with `state`."""
+    h_in, c_in = (s.contiguous() for s in state)
+    N.require_device(x, lens, w_ih, w_hh, b_ih, b_hh, h_in, c_in)
+    x = x.contiguous()
+    dev = x.device
+    B, T_src, Dsrc = x.shape
+    Din = 2 * Dsrc if concat else Dsrc
+    H = w_hh.shape[1]
+    Tc = int(Tc)
+    assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
+    assert tuple(h_in.shape) == tuple(c_in.shape) == (B, H) and lens.dtype == torch.int32
+    cd = compute_dtype()
+    if N.query('asr_lstm_uni_shape_ok', int(B), Tc, int(H)) != 1:
+        raise N.NativeError('asr_lstm_stream_forward refused (rc=%d): B %d Tc %d H %d is outside '
+                            'the shapes the unidirectional recurrence accepts'
+                            % (N.ASR_ERR_UNSUPPORTED, B, Tc, H))
+    w_dt = BF16 if w_hh.dtype == torch.bfloat16 else F32
+    nb, ws = 0, None
+    if cd == BF16 and w_dt == F32:
+        nb = int(N.query('asr_lstm_stream_workspace_bytes', B, H, cd))
+        ws = _ws(nb, dev)
+    in_map = _InputMap(None, t_mul, t_add, Tc, T_src, Dsrc, Din)
+    gx = torch.empty(B, Tc, 4 * H, dtype=torch.float32, device=dev)
+    y = torch.empty(B, Tc, H, dtype=torch.float32, device=dev)
+    h_out, c_out = torch.empty_like(h_in), torch.empty_like(c_in)
+    run_gemm([gemm_problem(operand(x, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
+                           rowmap(4 * H), B * Tc, 4 * H, Din, bias=b_ih, bias2=b_hh)], dev)
+    N.call('asr_lstm_stream_forward', N.ptr(gx), N.ptr(w_hh), w_dt, N.ptr(lens), B, Tc, H, cd,
+           N.ptr(h_in), N.ptr(c_in), N.ptr(h_out), N.ptr(c_out),
+           N.ptr(y), N.ptr(ws), nb, N.stream_handle(dev))
+    return y, (h_out, c_out)
+
+
 def _act_h_on():
     """Fused bf16 forward: keep the gate activations as packed fp16
     (asr_lstm_forward_xh; ASR_XG_ACT_H=0 keeps f32)."""
@@ -2999,6 +3043,24 @@ def ctc_best_path(logits, lens, blank=0):
     hl = torch.empty(B, dtype=torch.int32, device=logits.device)
     N.call('asr_ctc_best_path', N.ptr(logits), V, T * V, T, B, V, N.ptr(lens.int().contiguous()),
            int(blank), N.ptr(hyps), N.ptr(hl), N.stream_handle(logits.device))
+    return hyps, hl
+
+
+def ctc_best_path_stream(logits, lens, prev, blank=0):
+    """CTC best path of one chunk [B, Tc, V] of longer utterances.  lens int32
+    [B]: the chunk's valid frames per row; prev int32 [B] on the device, updated
+    in place: the label of each row's last valid frame so far (-1 before the
+    first), through which repeats collapse across chunk boundaries.  Returns
+    (hyps int32 [B, Tc], hyp_lens int32 [B]): the labels this chunk newly emits."""
+    N.require_device(logits, lens, prev)
+    logits = logits.contiguous()
+    B, T, V = logits.shape
+    assert prev.dtype == torch.int32 and prev.is_contiguous() and tuple(prev.shape) == (B,)
+    lens = lens.int().contiguous()
+    hyps = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    hl = torch.empty(B, dtype=torch.int32, device=logits.device)
+    N.call('asr_ctc_best_path_stream', N.ptr(logits), V, T * V, T, B, V, N.ptr(lens), int(blank),
+           N.ptr(prev), N.ptr(hyps), N.ptr(hl), N.stream_handle(logits.device))
     return hyps, hl
 
 
