@@ -707,6 +707,80 @@ int asr_ctc_beam_search_lm(const float* logits, long long stride_t, long long st
                            int normalize, const struct asr_att_beam_lm_s* lm, double beta, void* ws,
                            size_t ws_bytes, int32_t* hyps, int32_t* hyp_lens, float* scores,
                            void* stream);
+/* asr_ctc_beam_stream_*: the two searches above chunk by chunk, their state
+ * kept on the device between calls (csrc/ctc_beam.hip, "chunk by chunk").  A
+ * session is (max_frames, B, V, beam_width, blank, normalize, lm, beta): every
+ * call on one state passes the same values.  lm null or lm->weight == 0: the LM
+ * term is absent; with beta == 0 too the plain search runs.
+ * Bitwise contract: for any split of a row's frames into feeds -- one-frame
+ * chunks, feeds in which lens[b] == 0, ragged rows -- the hyps, hyp_lens and
+ * scores of the feed that carries the row's `final` flag are bit for bit those
+ * of asr_ctc_beam_search (asr_ctc_beam_search_lm with an LM or beta != 0) on
+ * the concatenated logits.
+ * asr_ctc_beam_stream_state_bytes: the persistent state.  Per row the beam in
+ *   rank order (n, the next node id, and per entry node, parent, last label,
+ *   depth, LM slot, p_b, p_nb, hash, parent hash), a pool of max_frames *
+ *   beam_width + 1 nodes, the frames consumed and a status word; with an LM
+ *   (lm_layers > 0) the 2 beam_width slots of h, c and the cached log-softmax
+ *   rows.  0 for refused shapes (max_frames outside [1, (2^31 - 2) / 64], the
+ *   refusals of asr_ctc_beam_ws_bytes and asr_ctc_beam_lm_ws_bytes).
+ * asr_ctc_beam_stream_ws_bytes: one feed's scratch (the chunk's log-sum-exps
+ *   and class lists).  It needs no initialisation and keeps no meaning between
+ *   calls.
+ * asr_ctc_beam_stream_reset: the rows whose rows[b] != 0 (rows: device int32
+ *   [B]; null: every row) at the empty prefix -- p_b = 0, p_nb = -inf, pool
+ *   node 0, no frames, status 0 -- and with an LM the root's LM state made from
+ *   the zero state and <eos>.  Other rows keep their search state.  A state
+ *   must be reset before its first feed.  1 + (lm ? 1 : 0) launches.
+ * asr_ctc_beam_stream_feed: advances row b by its lens[b] (clipped to [0, Tc])
+ *   frames of logits [B][Tc] (strides as asr_ctc_beam_search); lens[b] == 0
+ *   leaves the row's state untouched.  Then per row: the best prefix (rank 0)
+ *   in hyps[b * ld_hyp ...], its length in hyp_lens[b], its score S_t (no
+ *   <eos> term) in scores[b], and in stable_lens[b] (nullable: not computed)
+ *   the length of the longest common prefix of the label sequences of all
+ *   beam entries: every later hypothesis descends from a beam entry, so these
+ *   first labels never change again.  final: device int32 [B], nullable; for a
+ *   row whose flag is set the output is the whole-utterance search's -- with
+ *   an LM the entries re-ranked with alpha log p_lm(<eos> | l) added, that
+ *   value as the score -- and stable_lens[b] = hyp_lens[b]; the re-ranking is
+ *   for the output only, the state is not altered.
+ *   Capacity: a row never consumes more than max_frames frames; the frames
+ *   past it are dropped and bit 0 of the row's status word is set (bit 1: the
+ *   row's counters are not ones a reset or a feed left -- the state was never
+ *   reset; the row consumes nothing and reports an empty hypothesis, score
+ *   -inf).  The pool is never written past its end.
+ *   Launches: 1 (the rows' frame counts), then without LM and bonus the
+ *   chunk's pass 1 and one search launch (one wave per utterance: the beam
+ *   from the state into LDS, lens[b] frames, back), else the chunk's
+ *   log-sum-exps and per chunk frame 2 + (lm ? 1 : 0); then 1 (the output).
+ *   No host read, synchronisation or allocation; graph-capture safe.
+ *   Refused before any launch: the refusals of asr_ctc_beam_search /
+ *   asr_ctc_beam_search_lm (ASR_ERR_UNSUPPORTED: a GRU LM, layers >
+ *   ASR_ATT_BEAM_LM_MAX_LAYERS, the LM cell's LDS need above 64 KiB), ld_hyp <
+ *   max_frames, a state or workspace that is misaligned (ASR_ERR_ARG) or too
+ *   small (ASR_ERR_WORKSPACE).
+ * asr_ctc_beam_stream_nbest: every beam entry in rank order: hyps int32
+ *   [B][beam_width][ld_hyp], lens and scores [B][beam_width] (S_t,
+ *   non-increasing; unused entries: length 0, -inf), counts [B].  lm_layers /
+ *   lm_H: those of the state's layout (0, 0 without an LM).  One launch.
+ * asr_ctc_beam_stream_status: the rows' status words into status (device int32
+ *   [B]); one device-to-device copy on the stream. */
+size_t asr_ctc_beam_stream_state_bytes(int max_frames, int B, int V, int beam_width, int lm_layers,
+                                       int lm_H, int lm_Y);
+size_t asr_ctc_beam_stream_ws_bytes(int Tc, int B, int V, int beam_width);
+int asr_ctc_beam_stream_reset(void* state, size_t state_bytes, int max_frames, int B, int V,
+                              int beam_width, const struct asr_att_beam_lm_s* lm,
+                              const int32_t* rows, void* stream);
+int asr_ctc_beam_stream_feed(const float* logits, long long stride_t, long long stride_b, int Tc,
+                             int B, int V, const int32_t* lens, int blank, int beam_width,
+                             int normalize, const struct asr_att_beam_lm_s* lm, double beta,
+                             const int32_t* final, void* state, size_t state_bytes, int max_frames,
+                             void* ws, size_t ws_bytes, int32_t* hyps, int ld_hyp,
+                             int32_t* hyp_lens, float* scores, int32_t* stable_lens, void* stream);
+int asr_ctc_beam_stream_nbest(const void* state, size_t state_bytes, int max_frames, int B, int V,
+                              int beam_width, int lm_layers, int lm_H, int32_t* hyps, int ld_hyp,
+                              int32_t* lens, float* scores, int32_t* counts, void* stream);
+int asr_ctc_beam_stream_status(const void* state, int B, int32_t* status, void* stream);
 
 /* ------------------------------------------------------ hypothesis scoring
  * asr_edit_distance: per utterance pair the edit distance between a decoded

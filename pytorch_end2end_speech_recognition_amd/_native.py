@@ -151,6 +151,16 @@ SIGNATURES = {
     'asr_ctc_beam_search_lm': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int,
                                        c_int, c_vp, ctypes.c_double, c_vp, c_size, c_vp, c_vp,
                                        c_vp, c_vp]),
+    'asr_ctc_beam_stream_state_bytes': (c_size, [c_int] * 7),
+    'asr_ctc_beam_stream_ws_bytes': (c_size, [c_int] * 4),
+    'asr_ctc_beam_stream_reset': (c_int, [c_vp, c_size, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                          c_vp]),
+    'asr_ctc_beam_stream_feed': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                         c_int, c_vp, ctypes.c_double, c_vp, c_vp, c_size, c_int,
+                                         c_vp, c_size, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'asr_ctc_beam_stream_nbest': (c_int, [c_vp, c_size, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'asr_ctc_beam_stream_status': (c_int, [c_vp, c_int, c_vp, c_vp]),
     'asr_edit_distance_ws_bytes': (c_size, [c_int, c_int, c_int]),
     'asr_edit_distance': (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp,
                                   c_vp, c_vp, c_vp, c_size, c_vp]),

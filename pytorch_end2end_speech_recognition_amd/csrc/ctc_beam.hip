@@ -247,11 +247,32 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   return v;
 }
 
-__global__ void __launch_bounds__(64) beam_search_kernel(
+// A streaming session's search state (asr_ctc_beam_stream_*): per row the beam
+// between calls in rank order, the node pool of max_frames * W + 1 nodes, the
+// frames consumed and a status word; with an LM the 2 W slots of h, c and q.
+struct BeamState {
+  int32_t *frames, *status;      // [B]
+  int32_t *n, *nnodes;           // [B]
+  int32_t *node, *par, *last, *depth, *slot;   // [B][W]
+  int32_t *src, *tok;            // [B][W] lm_step's work list (no meaning between calls)
+  float *pb, *pnb;
+  unsigned long long *hash, *phash;
+  Node* pools;                   // [B][max_frames * W + 1]
+  float *h, *c, *q;
+  int max_frames;
+};
+
+// The search over one row's Tb = min(lens[b], T) frames.  STREAM == false: from
+// the empty prefix, the best entry's labels and score out.  STREAM == true
+// (beam_stream_kernel): the beam comes from the session state S and goes back
+// to it, one coalesced pass per array each way; lens[b] == 0 touches nothing.
+template <bool STREAM>
+__device__ __forceinline__ void beam_search_body(
     const float* __restrict__ logits, long long st, long long sb, int T, int V,
     const int32_t* __restrict__ lens, int blank, int W, const float* __restrict__ lse_in,
     const float* __restrict__ topv, const int32_t* __restrict__ topc, Node* __restrict__ pools,
-    int32_t* __restrict__ hyps, int32_t* __restrict__ hyp_lens, float* __restrict__ scores) {
+    const BeamState* S, int32_t* __restrict__ hyps, int32_t* __restrict__ hyp_lens,
+    float* __restrict__ scores) {
   // beam entry i < n, best first
   __shared__ int s_node[kMaxBeam], s_par[kMaxBeam], s_last[kMaxBeam], s_depth[kMaxBeam];
   __shared__ float s_pb[kMaxBeam], s_pnb[kMaxBeam], s_tot[kMaxBeam];
@@ -265,16 +286,28 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
   const int b = blockIdx.x, lane = threadIdx.x;
   const int K = W + 1;
   const int Tb = max(0, min(lens[b], T));
-  Node* pool = pools + (long long)b * ((long long)T * W + 1);
-
-  if (lane == 0) {
-    pool[0].parent = 0;
-    pool[0].label = -1;
-    s_node[0] = 0; s_par[0] = 0; s_last[0] = -1; s_depth[0] = 0;
-    s_pb[0] = 0.f; s_pnb[0] = neg_inf();
-    s_hash[0] = 0; s_phash[0] = 0;
-  }
+  Node* pool = pools + (long long)b * ((long long)(STREAM ? S->max_frames : T) * W + 1);
+  const long long r = (long long)b * W;
   int n = 1, nnodes = 1;
+  if constexpr (STREAM) {
+    if (Tb == 0) return;
+    n = S->n[b];
+    nnodes = S->nnodes[b];
+    if (lane < n) {
+      s_node[lane] = S->node[r + lane]; s_par[lane] = S->par[r + lane];
+      s_last[lane] = S->last[r + lane]; s_depth[lane] = S->depth[r + lane];
+      s_pb[lane] = S->pb[r + lane]; s_pnb[lane] = S->pnb[r + lane];
+      s_hash[lane] = S->hash[r + lane]; s_phash[lane] = S->phash[r + lane];
+    }
+  } else {
+    if (lane == 0) {
+      pool[0].parent = 0;
+      pool[0].label = -1;
+      s_node[0] = 0; s_par[0] = 0; s_last[0] = -1; s_depth[0] = 0;
+      s_pb[0] = 0.f; s_pnb[0] = neg_inf();
+      s_hash[0] = 0; s_phash[0] = 0;
+    }
+  }
   __syncthreads();
 
   for (int t = 0; t < Tb; ++t) {
@@ -386,7 +419,15 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
     __syncthreads();           // also orders the pool stores before the next frame's walks
   }
 
-  if (lane == 0) {
+  if constexpr (STREAM) {
+    if (lane < n) {
+      S->node[r + lane] = s_node[lane]; S->par[r + lane] = s_par[lane];
+      S->last[r + lane] = s_last[lane]; S->depth[r + lane] = s_depth[lane];
+      S->pb[r + lane] = s_pb[lane]; S->pnb[r + lane] = s_pnb[lane];
+      S->hash[r + lane] = s_hash[lane]; S->phash[r + lane] = s_phash[lane];
+    }
+    if (lane == 0) { S->n[b] = n; S->nnodes[b] = nnodes; }
+  } else if (lane == 0) {
     const int d = s_depth[0];
     int node = s_node[0];
     int32_t* out = hyps + (long long)b * T;
@@ -400,12 +441,22 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
   }
 }
 
+__global__ void __launch_bounds__(64) beam_search_kernel(
+    const float* __restrict__ logits, long long st, long long sb, int T, int V,
+    const int32_t* __restrict__ lens, int blank, int W, const float* __restrict__ lse_in,
+    const float* __restrict__ topv, const int32_t* __restrict__ topc, Node* __restrict__ pools,
+    int32_t* __restrict__ hyps, int32_t* __restrict__ hyp_lens, float* __restrict__ scores) {
+  beam_search_body<false>(logits, st, sb, T, V, lens, blank, W, lse_in, topv, topc, pools,
+                          nullptr, hyps, hyp_lens, scores);
+}
+
 // ------------------------------------------- the search with a language model
 struct LmP {
   // the call
   const float* logits;
   long long st, sb;
   int T, B, V, blank, W;
+  int poolT;                     // the frames a row's node pool is sized for (T; a session's max_frames)
   const int32_t* lens;
   float alpha, beta;
   int has_lm;                    // 0: no LM term anywhere, q / h / c are not touched
@@ -436,7 +487,7 @@ __global__ void __launch_bounds__(64) lm_init_kernel(LmP p) {
     p.src[r + lane] = -1;
   }
   if (lane == 0) {
-    Node* pool = p.pools + (long long)b * ((long long)p.T * p.W + 1);
+    Node* pool = p.pools + (long long)b * ((long long)p.poolT * p.W + 1);
     pool[0].parent = 0;
     pool[0].label = -1;
     p.n[b] = 1; p.nnodes[b] = 1;
@@ -505,7 +556,7 @@ __global__ void __launch_bounds__(64) lm_select_kernel(int t, LmP p) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int W = p.W, K = W + 1;
   if (t >= min(p.lens[b], p.T)) return;
-  Node* pool = p.pools + (long long)b * ((long long)p.T * W + 1);
+  Node* pool = p.pools + (long long)b * ((long long)p.poolT * W + 1);
   const long long r = (long long)b * W;
   const int n = p.n[b], nnodes = p.nnodes[b];
   const float* topv = p.topv + r * K;
@@ -680,7 +731,7 @@ __global__ void __launch_bounds__(64) lm_final_kernel(LmP p, int32_t* __restrict
   }
   const unsigned long long best = wave_max_u64(key);
   if (lane < n && key == best) {           // keys are distinct: one lane
-    const Node* pool = p.pools + (long long)b * ((long long)p.T * p.W + 1);
+    const Node* pool = p.pools + (long long)b * ((long long)p.poolT * p.W + 1);
     const int d = p.depth[r + lane];
     int node = p.node[r + lane];
     int32_t* out = hyps + (long long)b * p.T;
@@ -874,7 +925,7 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   char* base = (char*)ws;
   LmP p = {};
   p.logits = logits; p.st = stride_t; p.sb = stride_b;
-  p.T = T; p.B = B; p.V = V; p.blank = blank; p.W = W; p.lens = lens;
+  p.T = T; p.B = B; p.V = V; p.blank = blank; p.W = W; p.poolT = T; p.lens = lens;
   p.alpha = lm ? (float)lm->weight : 0.f;
   p.beta = (float)beta;
   p.has_lm = lm ? 1 : 0;
@@ -917,5 +968,434 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   }
   hipLaunchKernelGGL(lm_final_kernel, dim3(B), dim3(64), 0, s, p, hyps, hyp_lens, scores);
   ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+
+// ------------------------------------------------- the search, chunk by chunk
+// asr_ctc_beam_stream_*: the two searches above with their state kept between
+// calls, so that a call costs O(chunk).  The result of the call that carries a
+// row's `final` flag equals, bit for bit, the whole-utterance search on the
+// concatenated frames, for any chunking:
+//   * pass 1 (log-sum-exp, class lists) is per frame;
+//   * a frame of the search is the same f32 operations in the same order, on
+//     the previous beam in rank order (the state holds it in rank order, with
+//     both hashes, the depths, the LM slots and the pool's node numbering);
+//   * the order on equal scores depends on the previous beam's rank order and
+//     the frame's lists only.
+// Plain search (no LM, beta == 0): beam_stream_prep_kernel, pass 1 of the chunk,
+// beam_stream_kernel (beam_search_kernel's frame loop between a load and a
+// store of the state), beam_stream_out_kernel.  Otherwise: prep, the chunk's
+// log-sum-exps, per chunk frame lm_topk / lm_select / lm_step on the state's
+// arrays (the kernels above, unchanged), out.
+namespace asr {
+namespace {
+
+constexpr int kStreamFull = 1;       // status: frames were dropped at max_frames
+constexpr int kStreamInvalid = 2;    // status: the row's state is not one reset / feed left
+
+struct StreamLayout {
+  size_t frames, status, n, nnodes, node, par, last, depth, slot, src, tok, pb, pnb, hash, phash,
+      pool, h, c, q, total;
+};
+
+// layers == 0: no language model, no h / c / q
+inline StreamLayout stream_layout(int max_frames, int B, int V, int W, int layers, int H) {
+  StreamLayout w;
+  const size_t R = (size_t)B * W;
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += align16(bytes); return at; };
+  w.frames = take((size_t)B * sizeof(int32_t));
+  w.status = take((size_t)B * sizeof(int32_t));
+  w.n = take((size_t)B * sizeof(int32_t));
+  w.nnodes = take((size_t)B * sizeof(int32_t));
+  w.node = take(R * sizeof(int32_t));
+  w.par = take(R * sizeof(int32_t));
+  w.last = take(R * sizeof(int32_t));
+  w.depth = take(R * sizeof(int32_t));
+  w.slot = take(R * sizeof(int32_t));
+  w.src = take(R * sizeof(int32_t));
+  w.tok = take(R * sizeof(int32_t));
+  w.pb = take(R * sizeof(float));
+  w.pnb = take(R * sizeof(float));
+  w.hash = take(R * sizeof(unsigned long long));
+  w.phash = take(R * sizeof(unsigned long long));
+  w.pool = take((size_t)B * ((size_t)max_frames * W + 1) * sizeof(Node));
+  w.h = take(2 * R * (size_t)layers * H * sizeof(float));
+  w.c = take(2 * R * (size_t)layers * H * sizeof(float));
+  w.q = take(layers > 0 ? 2 * R * (size_t)V * sizeof(float) : 0);
+  w.total = o;
+  return w;
+}
+
+inline BeamState stream_state(void* state, const StreamLayout& w, int max_frames) {
+  char* base = (char*)state;
+  BeamState S;
+  S.frames = (int32_t*)(base + w.frames); S.status = (int32_t*)(base + w.status);
+  S.n = (int32_t*)(base + w.n); S.nnodes = (int32_t*)(base + w.nnodes);
+  S.node = (int32_t*)(base + w.node); S.par = (int32_t*)(base + w.par);
+  S.last = (int32_t*)(base + w.last); S.depth = (int32_t*)(base + w.depth);
+  S.slot = (int32_t*)(base + w.slot); S.src = (int32_t*)(base + w.src);
+  S.tok = (int32_t*)(base + w.tok);
+  S.pb = (float*)(base + w.pb); S.pnb = (float*)(base + w.pnb);
+  S.hash = (unsigned long long*)(base + w.hash); S.phash = (unsigned long long*)(base + w.phash);
+  S.pools = (Node*)(base + w.pool);
+  S.h = (float*)(base + w.h); S.c = (float*)(base + w.c); S.q = (float*)(base + w.q);
+  S.max_frames = max_frames;
+  return S;
+}
+
+// the per-frame kernels' view of a session: the beam and the LM slots are the state's
+inline LmP stream_lmp(const BeamState& S, int B, int V, int blank, int W,
+                      const asr_att_beam_lm_t* lm, double beta) {
+  LmP p = {};
+  p.B = B; p.V = V; p.blank = blank; p.W = W; p.poolT = S.max_frames;
+  p.alpha = lm ? (float)lm->weight : 0.f;
+  p.beta = (float)beta;
+  p.has_lm = lm ? 1 : 0;
+  if (lm) p.net = lm_net_from(lm);
+  p.n = S.n; p.nnodes = S.nnodes;
+  p.node = S.node; p.par = S.par; p.last = S.last; p.depth = S.depth; p.slot = S.slot;
+  p.src = S.src; p.tok = S.tok;
+  p.pb = S.pb; p.pnb = S.pnb; p.hash = S.hash; p.phash = S.phash;
+  p.pools = S.pools;
+  p.h = S.h; p.c = S.c; p.q = S.q;
+  return p;
+}
+
+struct StreamWs { size_t lens, lse, topv, topc, total; };
+
+// the class lists of the plain search ([B][Tc][W + 1]) and of the LM search
+// ([B][W][W + 1]) share one region
+inline StreamWs stream_ws(int Tc, int B, int V, int W) {
+  StreamWs w;
+  const size_t K = (size_t)W + 1;
+  const size_t lists = (size_t)B * ((size_t)Tc > (size_t)W ? (size_t)Tc : (size_t)W) * K;
+  w.lens = 0;
+  w.lse = align16((size_t)B * sizeof(int32_t));
+  w.topv = w.lse + align16((size_t)B * Tc * sizeof(float));
+  w.topc = w.topv + align16(lists * sizeof(float));
+  w.total = w.topc + align16(lists * sizeof(int32_t));
+  return w;
+}
+
+inline bool stream_args_ok(int max_frames, int B, int V, int W) {
+  return max_frames > 0 && max_frames <= (INT_MAX - 1) / kMaxBeam && beam_args_ok(1, B, V, W);
+}
+
+// The rows of `rows` (null: all) at the empty prefix; with an LM, lm_step(t =
+// -1) then makes the root's LM state from the zero state and <eos>.  tok is the
+// work list of that step: no token for the rows left alone.
+__global__ void __launch_bounds__(64) beam_stream_reset_kernel(BeamState S, int W, int V,
+                                                               const int32_t* __restrict__ rows) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r = (long long)b * W;
+  const bool sel = !rows || rows[b] != 0;
+  if (lane < W) {
+    S.tok[r + lane] = sel && lane == 0 ? V - 1 : -1;
+    S.src[r + lane] = -1;
+  }
+  if (sel && lane == 0) {
+    Node* pool = S.pools + (long long)b * ((long long)S.max_frames * W + 1);
+    pool[0].parent = 0;
+    pool[0].label = -1;
+    S.frames[b] = 0; S.status[b] = 0;
+    S.n[b] = 1; S.nnodes[b] = 1;
+    S.node[r] = 0; S.par[r] = 0; S.last[r] = -1; S.depth[r] = 0; S.slot[r] = 0;
+    S.pb[r] = 0.f; S.pnb[r] = neg_inf();
+    S.hash[r] = 0; S.phash[r] = 0;
+  }
+}
+
+// Per row the frames this call consumes: lens[b] clipped to the chunk and to
+// what max_frames leaves (status |= kStreamFull where that drops frames), 0 for
+// a row whose counters are not ones a reset or a feed can have left (status |=
+// kStreamInvalid: an uninitialised state must not index the pool).
+__global__ void __launch_bounds__(256) beam_stream_prep_kernel(BeamState S, int B, int W, int Tc,
+                                                               const int32_t* __restrict__ lens,
+                                                               int32_t* __restrict__ eff_lens) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int frames = S.frames[b], n = S.n[b], nnodes = S.nnodes[b];
+  int eff = max(0, min(lens[b], Tc));
+  const bool ok = frames >= 0 && frames <= S.max_frames && n >= 1 && n <= W && nnodes >= 1 &&
+                  (long long)nnodes <= (long long)frames * W + 1;
+  if (!ok) {
+    S.status[b] |= kStreamInvalid;
+    eff = 0;
+  } else if (eff > S.max_frames - frames) {
+    eff = S.max_frames - frames;
+    S.status[b] |= kStreamFull;
+  }
+  eff_lens[b] = eff;
+  if (eff > 0) S.frames[b] = frames + eff;
+}
+
+__global__ void __launch_bounds__(64) beam_stream_kernel(
+    const float* __restrict__ logits, long long st, long long sb, int T, int V,
+    const int32_t* __restrict__ lens, int blank, int W, const float* __restrict__ lse_in,
+    const float* __restrict__ topv, const int32_t* __restrict__ topc, BeamState S) {
+  beam_search_body<true>(logits, st, sb, T, V, lens, blank, W, lse_in, topv, topc, S.pools,
+                         &S, nullptr, nullptr, nullptr);
+}
+
+// One wave per row, entry i in lane i.  The best entry's labels and score: rank
+// 0 and S_t, or for a row whose `final` flag is set lm_final_kernel's choice
+// and value (the entries re-ranked with alpha lp_lm(<eos> | l) added; the state
+// is only read).  stable_lens (nullable): the length of the longest common
+// prefix of the n entries' label sequences -- every later hypothesis descends
+// from a beam entry, so these labels are final.  The chains are first brought
+// to the smallest depth, then walked up in lock step: a level at which all
+// lanes hold one node ends the walk (the prefixes below are one prefix); a
+// level at which the labels differ caps the length below it.  Labels are
+// compared, not node ids: two ids can denote the same prefix.
+__global__ void __launch_bounds__(64) beam_stream_out_kernel(
+    BeamState S, int W, int V, int has_lm, float alpha, const int32_t* __restrict__ final,
+    int32_t* __restrict__ hyps, int ld, int32_t* __restrict__ hyp_lens,
+    float* __restrict__ scores, int32_t* __restrict__ stable_lens) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r = (long long)b * W;
+  const int n = S.n[b];
+  if ((S.status[b] & kStreamInvalid) || n < 1 || n > W) {
+    if (lane == 0) {
+      hyp_lens[b] = 0;
+      scores[b] = neg_inf();
+      if (stable_lens) stable_lens[b] = 0;
+    }
+    return;
+  }
+  const Node* pool = S.pools + (long long)b * ((long long)S.max_frames * W + 1);
+  const bool fin = final && final[b] != 0;
+  const bool act = lane < n;
+  int node = 0, d = INT_MAX;
+  float s = neg_inf();
+  unsigned long long key = 0;
+  if (act) {
+    node = S.node[r + lane];
+    d = S.depth[r + lane];
+    s = logaddexp_(S.pb[r + lane], S.pnb[r + lane]);
+    if (fin && has_lm) s += alpha * S.q[((long long)b * 2 * W + S.slot[r + lane]) * V + (V - 1)];
+    key = make_key(s, lane);
+  }
+  const unsigned long long best = fin ? wave_max_u64(key) : 0ull;
+  const bool win = act && (fin ? key == best : lane == 0);   // keys are distinct: one lane
+  if (win) {
+    int nd_ = node;
+    int32_t* out = hyps + (long long)b * ld;
+    for (int k = d - 1; k >= 0; --k) {       // d <= frames <= max_frames <= ld
+      const Node nd = pool[nd_];
+      out[k] = nd.label;
+      nd_ = nd.parent;
+    }
+    hyp_lens[b] = d;
+    scores[b] = s;
+    if (stable_lens && fin) stable_lens[b] = d;
+  }
+  if (!stable_lens || fin) return;
+
+  int dmin = d;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dmin = min(dmin, __shfl_xor(dmin, o, 64));
+  if (act)
+    for (int k = d; k > dmin; --k) node = pool[node].parent;
+  int L = dmin;
+  for (int lev = dmin; lev > 0; --lev) {
+    const int node0 = __shfl(node, 0, 64);
+    if (__ballot(act && node != node0) == 0ull) break;
+    const Node nd = act ? pool[node] : Node{0, 0};
+    const int lab0 = __shfl(nd.label, 0, 64);
+    if (__ballot(act && nd.label != lab0) != 0ull) L = lev - 1;
+    node = nd.parent;
+  }
+  if (lane == 0) stable_lens[b] = L;
+}
+
+// every entry of the beam in rank order: labels, length, S_t
+__global__ void __launch_bounds__(64) beam_stream_nbest_kernel(
+    BeamState S, int W, int32_t* __restrict__ hyps, int ld, int32_t* __restrict__ lens,
+    float* __restrict__ scores, int32_t* __restrict__ counts) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r = (long long)b * W;
+  int n = S.n[b];
+  if ((S.status[b] & kStreamInvalid) || n < 1 || n > W) n = 0;
+  if (lane == 0) counts[b] = n;
+  if (lane >= W) return;
+  if (lane >= n) {
+    lens[r + lane] = 0;
+    scores[r + lane] = neg_inf();
+    return;
+  }
+  const Node* pool = S.pools + (long long)b * ((long long)S.max_frames * W + 1);
+  const int d = S.depth[r + lane];
+  int node = S.node[r + lane];
+  int32_t* out = hyps + (r + lane) * ld;
+  for (int k = d - 1; k >= 0; --k) {         // d <= max_frames <= ld
+    const Node nd = pool[node];
+    out[k] = nd.label;
+    node = nd.parent;
+  }
+  lens[r + lane] = d;
+  scores[r + lane] = logaddexp_(S.pb[r + lane], S.pnb[r + lane]);
+}
+
+constexpr LmWho kStreamLmWho = {"ctc_beam_stream", "ctc_beam_stream", "LM dims", "CTC head",
+                                " (blank included; <eos> takes the blank's place)"};
+
+}  // namespace
+}  // namespace asr
+
+extern "C" size_t asr_ctc_beam_stream_state_bytes(int max_frames, int B, int V, int beam_width,
+                                                  int lm_layers, int lm_H, int lm_Y) {
+  if (!stream_args_ok(max_frames, B, V, beam_width)) return 0;
+  if (lm_layers == 0) return stream_layout(max_frames, B, V, beam_width, 0, 0).total;
+  if (lm_net_shape_check(lm_layers, lm_H, lm_Y, kStreamLmWho) != ASR_OK) return 0;
+  return stream_layout(max_frames, B, V, beam_width, lm_layers, lm_H).total;
+}
+
+extern "C" size_t asr_ctc_beam_stream_ws_bytes(int Tc, int B, int V, int beam_width) {
+  if (!beam_args_ok(Tc, B, V, beam_width)) return 0;
+  return stream_ws(Tc, B, V, beam_width).total;
+}
+
+// What every session call asks of the session's shape, its LM and its state;
+// on ASR_OK *lm is null where the LM term is absent and S is the state's view.
+static int stream_check(const char* who, bool pointers, int max_frames, int B, int V, int blank,
+                        int beam_width, const asr_att_beam_lm_t** lm, const void* state,
+                        size_t state_bytes, BeamState* S) {
+  int rc = beam_args_check(who, pointers && state, 1, B, V, blank, beam_width);
+  if (rc != ASR_OK) return rc;
+  ASR_REQUIRE(stream_args_ok(max_frames, B, V, beam_width), ASR_ERR_ARG,
+              "%s: max_frames = %d outside [1, %d]", who, max_frames, (INT_MAX - 1) / kMaxBeam);
+  if (*lm) {
+    ASR_REQUIRE((*lm)->weight >= 0.0 && (*lm)->weight <= 3.0e38, ASR_ERR_ARG,
+                "%s: weight = %g is negative or not finite", who, (*lm)->weight);
+    if ((rc = lm_net_check(*lm, V, kStreamLmWho)) != ASR_OK) return rc;
+    if ((*lm)->weight == 0.0) *lm = nullptr;  // the LM term is absent
+  }
+  const StreamLayout w = stream_layout(max_frames, B, V, beam_width, *lm ? (*lm)->layers : 0,
+                                       *lm ? (*lm)->H : 0);
+  ASR_REQUIRE(state_bytes >= w.total, ASR_ERR_WORKSPACE, "%s: state %zu < %zu bytes", who,
+              state_bytes, w.total);
+  ASR_REQUIRE(((uintptr_t)state & 15) == 0, ASR_ERR_ARG, "%s: state not 16-B aligned", who);
+  *S = stream_state((void*)state, w, max_frames);
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_reset(void* state, size_t state_bytes, int max_frames, int B,
+                                         int V, int beam_width, const asr_att_beam_lm_t* lm,
+                                         const int32_t* rows, void* stream) {
+  BeamState S;
+  const int rc = stream_check("ctc_beam_stream_reset", true, max_frames, B, V, 0, beam_width, &lm,
+                              state, state_bytes, &S);
+  if (rc != ASR_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B), dim3(64), 0, s, S, beam_width, V, rows);
+  ASR_LAUNCH_CHECK();
+  if (lm) {
+    const LmP p = stream_lmp(S, B, V, 0, beam_width, lm, 0.0);
+    hipLaunchKernelGGL(lm_step_kernel, dim3(1, B), dim3(LM_THREADS),
+                       lm_cell_lds_floats(lm->Y, lm->H) * 4, s, -1, p);
+    ASR_LAUNCH_CHECK();
+  }
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_feed(const float* logits, long long stride_t, long long stride_b,
+                                        int Tc, int B, int V, const int32_t* lens, int blank,
+                                        int beam_width, int normalize, const asr_att_beam_lm_t* lm,
+                                        double beta, const int32_t* final, void* state,
+                                        size_t state_bytes, int max_frames, void* ws,
+                                        size_t ws_bytes, int32_t* hyps, int ld_hyp,
+                                        int32_t* hyp_lens, float* scores, int32_t* stable_lens,
+                                        void* stream) {
+  const char* who = "ctc_beam_stream_feed";
+  int rc = beam_args_check(who, logits && lens && ws && hyps && hyp_lens && scores, Tc, B, V, blank,
+                           beam_width);
+  if (rc != ASR_OK) return rc;
+  ASR_REQUIRE(beta == beta && fabs(beta) <= 3.0e38, ASR_ERR_ARG, "%s: beta = %g is not finite", who,
+              beta);
+  BeamState S;
+  if ((rc = stream_check(who, true, max_frames, B, V, blank, beam_width, &lm, state, state_bytes,
+                         &S)) != ASR_OK)
+    return rc;
+  ASR_REQUIRE(ld_hyp >= max_frames, ASR_ERR_ARG, "%s: ld_hyp = %d < max_frames = %d", who, ld_hyp,
+              max_frames);
+  const int W = beam_width;
+  const StreamWs w = stream_ws(Tc, B, V, W);
+  if ((rc = beam_ws_check(who, ws, ws_bytes, w.total)) != ASR_OK) return rc;
+  char* base = (char*)ws;
+  int32_t* eff = (int32_t*)(base + w.lens);
+  float* lse = (float*)(base + w.lse);
+  float* topv = (float*)(base + w.topv);
+  int32_t* topc = (int32_t*)(base + w.topc);
+
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(beam_stream_prep_kernel, dim3((B + 255) / 256), dim3(256), 0, s, S, B, W, Tc,
+                     lens, eff);
+  ASR_LAUNCH_CHECK();
+  const bool plain = !lm && beta == 0.0;
+  if (plain) {
+    launch_rows(logits, stride_t, stride_b, Tc, B, V, eff, blank, W + 1, normalize, lse, topv, topc,
+                s);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_stream_kernel, dim3(B), dim3(64), 0, s, logits, stride_t, stride_b, Tc,
+                       V, eff, blank, W, lse, topv, topc, S);
+    ASR_LAUNCH_CHECK();
+  } else {
+    LmP p = stream_lmp(S, B, V, blank, W, lm, beta);
+    p.logits = logits; p.st = stride_t; p.sb = stride_b;
+    p.T = Tc; p.lens = eff; p.lse = lse; p.topv = topv; p.topc = topc;
+    launch_rows(logits, stride_t, stride_b, Tc, B, V, eff, blank, 0, normalize, lse, nullptr,
+                nullptr, s);
+    ASR_LAUNCH_CHECK();
+    const size_t lds_step = lm ? lm_cell_lds_floats(lm->Y, lm->H) * 4 : 0;
+    const long long entries = (long long)B * W;
+    for (int t = 0; t < Tc; ++t) {
+      if (V <= kWaveModeMaxV)
+        hipLaunchKernelGGL(lm_topk_kernel<1>, dim3((unsigned)((entries + 3) / 4)), dim3(256), 0, s,
+                           t, p);
+      else
+        hipLaunchKernelGGL(lm_topk_kernel<4>, dim3((unsigned)entries), dim3(256), 0, s, t, p);
+      hipLaunchKernelGGL(lm_select_kernel, dim3(B), dim3(64), 0, s, t, p);
+      if (lm) hipLaunchKernelGGL(lm_step_kernel, dim3(W, B), dim3(LM_THREADS), lds_step, s, t, p);
+      ASR_LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL(beam_stream_out_kernel, dim3(B), dim3(64), 0, s, S, W, V, lm ? 1 : 0,
+                     lm ? (float)lm->weight : 0.f, final, hyps, ld_hyp, hyp_lens, scores,
+                     stable_lens);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_nbest(const void* state, size_t state_bytes, int max_frames,
+                                         int B, int V, int beam_width, int lm_layers, int lm_H,
+                                         int32_t* hyps, int ld_hyp, int32_t* lens, float* scores,
+                                         int32_t* counts, void* stream) {
+  const char* who = "ctc_beam_stream_nbest";
+  const int rc = beam_args_check(who, state && hyps && lens && scores && counts, 1, B, V, 0,
+                                 beam_width);
+  if (rc != ASR_OK) return rc;
+  ASR_REQUIRE(stream_args_ok(max_frames, B, V, beam_width), ASR_ERR_ARG,
+              "%s: max_frames = %d outside [1, %d]", who, max_frames, (INT_MAX - 1) / kMaxBeam);
+  ASR_REQUIRE(lm_layers >= 0 && lm_H >= 0, ASR_ERR_ARG, "%s: bad LM dims", who);
+  ASR_REQUIRE(ld_hyp >= max_frames, ASR_ERR_ARG, "%s: ld_hyp = %d < max_frames = %d", who, ld_hyp,
+              max_frames);
+  const StreamLayout w = stream_layout(max_frames, B, V, beam_width, lm_layers, lm_H);
+  ASR_REQUIRE(state_bytes >= w.total, ASR_ERR_WORKSPACE, "%s: state %zu < %zu bytes", who,
+              state_bytes, w.total);
+  ASR_REQUIRE(((uintptr_t)state & 15) == 0, ASR_ERR_ARG, "%s: state not 16-B aligned", who);
+  const BeamState S = stream_state((void*)state, w, max_frames);
+  hipLaunchKernelGGL(beam_stream_nbest_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, S,
+                     beam_width, hyps, ld_hyp, lens, scores, counts);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_status(const void* state, int B, int32_t* status, void* stream) {
+  ASR_REQUIRE(state && status && B > 0, ASR_ERR_ARG, "ctc_beam_stream_status: bad argument");
+  // the status words follow the frame counts: stream_layout's first two arrays
+  const char* at = (const char*)state + align16((size_t)B * sizeof(int32_t));
+  ASR_CHECK_HIP(hipMemcpyAsync(status, at, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
   return ASR_OK;
 }

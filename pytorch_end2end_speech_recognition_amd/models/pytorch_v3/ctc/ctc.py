@@ -62,6 +62,24 @@ class CTCStream(object):
         self.last_logits = None
         self.last_lens_np = None
 
+    def _chunk_logits(self, xs_chunk, chunk_lens, final):
+        """The chunk through the encoder and the output layers: (logits [B,
+        Tc', V], their valid lengths int32 [B]), both on the device."""
+        model = self._model
+        if model.training:
+            raise RuntimeError('%s.feed runs in eval mode only: the model is in training '
+                               'mode (call model.eval(); after an optimizer step open a new '
+                               'session, its bf16 weight copies would be stale)'
+                               % type(self).__name__)
+        xs_d = model.np2var(xs_chunk, dtype='float')
+        xs, lens_d = model.encoder.forward_chunk(xs_d, chunk_lens, self._state, final=final)
+        for i in range(len(model.fc_list)):
+            xs = getattr(model, 'fc_' + str(i))(xs)
+        logits = model.fc_out(xs)
+        if model.logits_temperature != 1:
+            logits = logits * (1.0 / model.logits_temperature)
+        return logits, lens_d
+
     @torch.no_grad()
     def feed(self, xs_chunk, chunk_lens, final=False):
         """xs_chunk [B, Tc, F] (numpy or device tensor), chunk_lens [B]: each
@@ -72,18 +90,7 @@ class CTCStream(object):
         a list of B int64 arrays, the labels this chunk newly emits, in
         decode()'s index space.  One host read: the labels and their counts.
         The model must be in eval mode (RuntimeError otherwise)."""
-        model = self._model
-        if model.training:
-            raise RuntimeError('CTCStream.feed runs in eval mode only: the model is in training '
-                               'mode (call model.eval(); after an optimizer step open a new '
-                               'session, its bf16 weight copies would be stale)')
-        xs_d = model.np2var(xs_chunk, dtype='float')
-        xs, lens_d = model.encoder.forward_chunk(xs_d, chunk_lens, self._state, final=final)
-        for i in range(len(model.fc_list)):
-            xs = getattr(model, 'fc_' + str(i))(xs)
-        logits = model.fc_out(xs)
-        if model.logits_temperature != 1:
-            logits = logits * (1.0 / model.logits_temperature)
+        logits, lens_d = self._chunk_logits(xs_chunk, chunk_lens, final)
         hyps, hl = ops.ctc_best_path_stream(logits, lens_d, self._prev, 0)
         packed = torch.cat([hl.view(-1, 1), hyps], dim=1).cpu().numpy()
         self.last_logits = logits
@@ -108,6 +115,109 @@ class CTCStream(object):
                                                       device=self._prev.device), -1)
         for b in rows:
             self._emitted[b] = []
+
+
+class CTCBeamStream(CTCStream):
+    """Chunk-by-chunk prefix beam search with a unidirectional CTC model
+    (CTC.stream with beam_width > 1, an LM weight or an insertion bonus): the
+    encoder state and the search state (the beam in rank order, its node pool,
+    with an LM the entries' LM states) stay on the device between chunks.  The
+    hypotheses and scores of a row's final chunk are what the whole-utterance
+    search (native_ops.ctc_beam_search) gives on the session's concatenated
+    logits, bit for bit.
+
+    After a feed: ``stable_lens`` int [B] -- that many first labels of each
+    row's hypothesis are final: every beam entry starts with them, and every
+    later hypothesis descends from a beam entry -- and ``scores`` float32 [B]:
+    the hypothesis' score S_t, which carries the LM's <eos> term only on the
+    row's final chunk.  ``max_frames``: the encoder output frames one utterance
+    may hold between resets (the search's node pool is sized for them)."""
+
+    def __init__(self, model, batch_size, beam_width, rnnlm, alpha, beta, max_frames):
+        self._model = model
+        self._state = model.encoder.init_stream(batch_size)
+        self.batch_size = B = self._state.batch_size
+        if model.training:
+            raise RuntimeError('CTC.stream runs in eval mode only: call model.eval() first')
+        self.max_frames = int(max_frames)
+        if self.max_frames < 1:
+            raise ValueError('CTC.stream: max_frames = %r' % (max_frames,))
+        # the LM weights are read once per session
+        lm = dict(rnnlm.device_weights(), weight=float(alpha)) if alpha > 0 else None
+        self._search = ops.ctc_beam_stream_state(B, model.num_classes, beam_width, self.max_frames,
+                                                 self._state.device, blank=0, normalize=True,
+                                                 lm=lm, beta=beta)
+        self._frames = np.zeros(B, np.int64)      # encoder output frames per row so far
+        self._hyps = [np.zeros(0, np.int64) for _ in range(B)]
+        self.stable_lens = np.zeros(B, np.int64)
+        self.scores = np.zeros(B, np.float32)
+        self.last_logits = None
+        self.last_lens_np = None
+
+    @torch.no_grad()
+    def feed(self, xs_chunk, chunk_lens, final=False):
+        """xs_chunk, chunk_lens, final as CTCStream.feed.  Returns a list of B
+        int64 arrays: each row's current best hypothesis IN FULL, in decode()'s
+        index space -- not an increment: the best beam entry can change from
+        chunk to chunk (``stable()`` is the part that cannot).  From a row's
+        final chunk until its reset the row reports the whole-utterance
+        search's result.  A feed that would take a row past max_frames raises ValueError before any launch.
+        One host read: lengths, stable lengths, scores and labels together."""
+        B = self.batch_size
+        lens = np.asarray(chunk_lens).astype(np.int64).reshape(-1)
+        if len(lens) == B:
+            after = self._frames + lens // self._model.encoder.stream_stride
+            bad = np.nonzero(after > self.max_frames)[0]
+            if len(bad):
+                raise ValueError('CTCBeamStream.feed: rows %s would hold %s encoder frames, '
+                                 'max_frames = %d (reset the row, or open the session with a '
+                                 'larger max_frames)' % (bad.tolist(), after[bad].tolist(),
+                                                         self.max_frames))
+        logits, lens_d = self._chunk_logits(xs_chunk, chunk_lens, final)
+        self._frames += self._state.last_lens_np
+        # a row that has had its final chunk keeps reporting its final result until reset
+        fin = self._state.final
+        fin_d = ops.h2d(fin.astype(np.int32), logits.device) if fin.any() else None
+        hyps, hl, scores, sl = ops.ctc_beam_stream_feed(self._search, logits, lens_d, fin_d)
+        longest = max(int(self._frames.max()), 1)
+        packed = torch.cat([hl.view(-1, 1), sl.view(-1, 1), scores.view(torch.int32).view(-1, 1),
+                            hyps[:, :longest]], dim=1).cpu().numpy()
+        self.last_logits = logits
+        self.last_lens_np = self._state.last_lens_np.copy()
+        self.stable_lens = packed[:, 1].astype(np.int64)
+        self.scores = np.ascontiguousarray(packed[:, 2]).view(np.float32).copy()
+        self._hyps = [packed[b, 3:3 + packed[b, 0]].astype(np.int64) - 1 for b in range(B)]
+        return self.hyps()
+
+    def hyps(self):
+        """The last feed's result: each row's current best hypothesis."""
+        return [h.copy() for h in self._hyps]
+
+    def stable(self):
+        """Per row the labels that can no longer change."""
+        return [h[:n].copy() for h, n in zip(self._hyps, self.stable_lens)]
+
+    def nbest(self):
+        """Per row the beam's entries, best first: a list of (labels int64 in
+        decode()'s index space, score S_t)."""
+        hyps, lens, scores, counts = [t.cpu().numpy() for t in
+                                      ops.ctc_beam_stream_nbest(self._search)]
+        return [[(hyps[b, i, :lens[b, i]].astype(np.int64) - 1, float(scores[b, i]))
+                 for i in range(counts[b])] for b in range(self.batch_size)]
+
+    def reset(self, rows=None):
+        """Start a new utterance in `rows` (default: every row): zero encoder
+        state, the search at the empty prefix.  Other rows go on."""
+        self._state.reset(rows)
+        rows = list(range(self.batch_size)) if rows is None else [int(r) for r in rows]
+        if not rows:
+            return
+        ops.ctc_beam_stream_reset(self._search, rows)
+        for b in rows:
+            self._frames[b] = 0
+            self._hyps[b] = np.zeros(0, np.int64)
+            self.stable_lens[b] = 0
+            self.scores[b] = 0.0
 
 
 class CTC(ModelBase):
@@ -340,12 +450,19 @@ class CTC(ModelBase):
         best_hyps = np.array([h - 1 for h in best_hyps] + [None], dtype=object)[:-1]
         return best_hyps, None, self.encoder.last_perm_np.copy()
 
-    def stream(self, batch_size):
-        """A CTCStream: chunk-by-chunk greedy recognition of `batch_size`
-        utterances side by side.  Single-task models with a unidirectional LSTM
-        encoder and no conv front-end (RNNEncoder.init_stream names what else
-        is refused); beam search and LM fusion are whole-utterance only.  The
-        model must be in eval mode: RuntimeError otherwise, as forward_chunk."""
+    def stream(self, batch_size, beam_width=1, rnnlm=None, lm_weight=0, insertion_bonus=0,
+               max_frames=4096):
+        """Chunk-by-chunk recognition of `batch_size` utterances side by side.
+        beam_width == 1 without an LM term or a bonus: a CTCStream (greedy).
+        Otherwise a CTCBeamStream: the prefix beam search of decode() with its
+        state kept on the device, rnnlm / lm_weight / insertion_bonus as in
+        decode(), max_frames the encoder output frames an utterance may hold
+        between resets.  Single-task models with a unidirectional LSTM encoder
+        and no conv front-end (RNNEncoder.init_stream names what else is
+        refused).  ValueError: decode()'s LM preconditions, beam_width outside
+        [1, 64].  NotImplementedError: a GRU LM or one deeper than the kernels'
+        limit -- a session has no host search.  The model must be in eval
+        mode: RuntimeError otherwise, as forward_chunk."""
         if hasattr(self, 'main_loss_weight'):
             raise NotImplementedError('streaming a hierarchical CTC model (its sub-task output) '
                                       'is not supported')
@@ -353,10 +470,15 @@ class CTC(ModelBase):
             raise NotImplementedError('streaming needs an LSTM encoder, not encoder_type=%s '
                                       '(a conv front-end\'s context crosses chunk boundaries)'
                                       % self.encoder_type)
-        st = CTCStream(self, batch_size)      # (refuses an unsupported encoder first)
-        if self.training:
-            raise RuntimeError('CTC.stream runs in eval mode only: call model.eval() first')
-        return st
+        alpha, beta = self._check_lm(rnnlm, lm_weight, insertion_bonus, 0)
+        if not 1 <= int(beam_width) <= 64:
+            raise ValueError('CTC.stream: beam_width = %r outside [1, 64]' % (beam_width,))
+        if int(beam_width) == 1 and alpha == 0 and beta == 0:
+            st = CTCStream(self, batch_size)      # (refuses an unsupported encoder first)
+            if self.training:
+                raise RuntimeError('CTC.stream runs in eval mode only: call model.eval() first')
+            return st
+        return CTCBeamStream(self, batch_size, int(beam_width), rnnlm, alpha, beta, max_frames)
 
     @eval_retry
     @torch.no_grad()

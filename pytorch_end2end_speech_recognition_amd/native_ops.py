@@ -3071,8 +3071,9 @@ _ctc_beam = {'path': None}
 def last_ctc_beam_path():
     """Where the last CTC prefix beam search ran (None before the first one):
     'device' (asr_ctc_beam_search, no LM and no insertion bonus), 'device_lm'
-    (asr_ctc_beam_search_lm) or 'host' (the decoder's numpy search: the kernels
-    refused the LM, or ASR_CTC_BEAM=host)."""
+    (asr_ctc_beam_search_lm), 'host' (the decoder's numpy search: the kernels
+    refused the LM, or ASR_CTC_BEAM=host), or after a session's feed
+    (asr_ctc_beam_stream_feed) 'stream' (no LM and no bonus) / 'stream_lm'."""
     return _ctc_beam['path']
 
 
@@ -3134,6 +3135,121 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, 
                             % (rc, N.lib().asr_last_error().decode(errors='replace')))
     _ctc_beam['path'] = 'device_lm'
     return hyps, hl, scores
+
+
+class CtcBeamStreamState(object):
+    """One streaming prefix-search session (ctc_beam_stream_state): the device
+    state buffer, the session's constants and the LM struct with the tensors
+    it points into."""
+    __slots__ = ('buf', 'ws', 'B', 'V', 'W', 'max_frames', 'blank', 'normalize', 'beta', 'lms',
+                 'keep', 'device')
+
+    @property
+    def lm_dims(self):
+        """(layers, H, Y) of the state's layout: zeros where the LM term is absent."""
+        if self.lms is None or self.lms.weight == 0:
+            return 0, 0, 0
+        return self.lms.layers, self.lms.H, self.lms.Y
+
+
+def _beam_stream_rows(st, rows):
+    if rows is None:
+        return None
+    mask = np.zeros(st.B, np.int32)
+    mask[[int(r) for r in rows]] = 1
+    return torch.from_numpy(mask).to(st.device)
+
+
+def ctc_beam_stream_state(batch_size, num_classes, beam_width, max_frames, device, blank=0,
+                          normalize=True, lm=None, beta=0.0):
+    """A streaming CTC prefix-search session of `batch_size` rows over
+    `num_classes` classes (asr_ctc_beam_stream_*; include/asr_hip.h states the
+    contract), every row reset.  lm / beta as in ctc_beam_search; max_frames:
+    the frames one utterance may hold between resets.  Raises
+    NotImplementedError where the kernels refuse the LM (a GRU LM, more layers
+    than the limit): a session has no host search."""
+    st = CtcBeamStreamState()
+    st.B, st.V, st.W, st.max_frames = int(batch_size), int(num_classes), int(beam_width), \
+        int(max_frames)
+    st.blank, st.normalize, st.beta, st.device = int(blank), bool(normalize), float(beta), device
+    st.lms, st.keep = _lm_struct(lm, 'ctc_beam_stream') if lm is not None else (None, None)
+    st.ws = None
+    if lm is not None and (int(lm['emb'].shape[0]) != st.V or int(lm['w_out'].shape[0]) != st.V):
+        raise ValueError('ctc_beam_stream: the LM has %d classes, the CTC head %d (blank '
+                         'included; <eos> takes its place)' % (lm['w_out'].shape[0], st.V))
+    if not np.isfinite(st.beta):
+        raise ValueError('ctc_beam_stream: beta = %r is not finite' % (beta,))
+    nb = N.query('asr_ctc_beam_stream_state_bytes', st.max_frames, st.B, st.V, st.W, *st.lm_dims)
+    # (a refused shape: the reset below names it)
+    st.buf = _ws(max(nb, 16), device)
+    ctc_beam_stream_reset(st)
+    return st
+
+
+def ctc_beam_stream_reset(st, rows=None):
+    """The rows of `rows` (default: all) of a session at the empty prefix."""
+    mask = _beam_stream_rows(st, rows)
+    rc = N.lib().asr_ctc_beam_stream_reset(
+        N.ptr(st.buf), st.buf.numel(), st.max_frames, st.B, st.V, st.W, N.ptr_struct(st.lms),
+        N.ptr(mask), N.stream_handle(st.device))
+    msg = N.lib().asr_last_error().decode(errors='replace') if rc != N.ASR_OK else ''
+    if rc == N.ASR_ERR_UNSUPPORTED:
+        raise NotImplementedError('asr_ctc_beam_stream_reset refused the LM: %s' % msg)
+    if rc != N.ASR_OK:
+        raise N.NativeError('asr_ctc_beam_stream_reset failed (rc=%d): %s' % (rc, msg))
+
+
+def ctc_beam_stream_feed(st, logits, lens, final=None, stable=True):
+    """One chunk [B, Tc, V] of a session: lens int32 [B] valid frames per row,
+    final int32 [B] device tensor (or None).  Returns (hyps int32 [B,
+    max_frames], hyp_lens int32 [B], scores float32 [B], stable_lens int32 [B]
+    or None with stable=False): each row's current best prefix in full."""
+    N.require_device(logits, lens, final)
+    logits = logits.contiguous().float()
+    B, T, V = logits.shape
+    assert (B, V) == (st.B, st.V), 'the chunk is [%d, ., %d], the session [%d, ., %d]' % (
+        B, V, st.B, st.V)
+    dev = logits.device
+    nb = N.query('asr_ctc_beam_stream_ws_bytes', T, B, V, st.W)
+    if st.ws is None or st.ws.numel() < nb:
+        st.ws = _ws(nb, dev)
+    hyps = torch.empty(B, st.max_frames, dtype=torch.int32, device=dev)
+    hl = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, dtype=torch.float32, device=dev)
+    sl = torch.empty(B, dtype=torch.int32, device=dev) if stable else None
+    if final is not None:
+        final = final.int().contiguous()
+    N.call('asr_ctc_beam_stream_feed', N.ptr(logits), V, T * V, T, B, V,
+           N.ptr(lens.int().contiguous()), st.blank, st.W, int(st.normalize), N.ptr_struct(st.lms),
+           st.beta, N.ptr(final), N.ptr(st.buf), st.buf.numel(), st.max_frames, N.ptr(st.ws),
+           st.ws.numel(), N.ptr(hyps), st.max_frames, N.ptr(hl), N.ptr(scores), N.ptr(sl),
+           N.stream_handle(dev))
+    _ctc_beam['path'] = 'stream' if st.lm_dims[0] == 0 and st.beta == 0 else 'stream_lm'
+    return hyps, hl, scores, sl
+
+
+def ctc_beam_stream_nbest(st):
+    """Every beam entry of a session in rank order: (hyps int32 [B, W,
+    max_frames], lens int32 [B, W], scores float32 [B, W], counts int32 [B])."""
+    dev = st.device
+    hyps = torch.empty(st.B, st.W, st.max_frames, dtype=torch.int32, device=dev)
+    lens = torch.empty(st.B, st.W, dtype=torch.int32, device=dev)
+    scores = torch.empty(st.B, st.W, dtype=torch.float32, device=dev)
+    counts = torch.empty(st.B, dtype=torch.int32, device=dev)
+    layers, H, _ = st.lm_dims
+    N.call('asr_ctc_beam_stream_nbest', N.ptr(st.buf), st.buf.numel(), st.max_frames, st.B, st.V,
+           st.W, layers, H, N.ptr(hyps), st.max_frames, N.ptr(lens), N.ptr(scores), N.ptr(counts),
+           N.stream_handle(dev))
+    return hyps, lens, scores, counts
+
+
+def ctc_beam_stream_status(st):
+    """The rows' status words, int32 [B] on the device: bit 0: frames were
+    dropped at max_frames; bit 1: the row was fed before any reset."""
+    out = torch.empty(st.B, dtype=torch.int32, device=st.device)
+    N.call('asr_ctc_beam_stream_status', N.ptr(st.buf), st.B, N.ptr(out),
+           N.stream_handle(st.device))
+    return out
 
 
 # ---------------------------------------------------------------------------
