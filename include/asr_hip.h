@@ -1261,6 +1261,16 @@ int asr_conv3x3_c1_forward_xs(const float* xs, int round_bf16, int B, int T, int
  * The f32 sums are asr_gemm's (same k order).  Cin, Cout in {64, 128};
  * ASR_ERR_UNSUPPORTED otherwise (asr_conv3x3_tr_supported says which). */
 int asr_conv3x3_tr_supported(int Cin, int Cout, int Fp);
+/* The plan asr_conv3x3_tr launches with (host only, no GPU): out = {wpx (pixels
+ * per wave; a tile is 4 wpx pixel rows), nw (weight-ring slots, 0 = the whole
+ * weight image resident in LDS), RC (pixel rows of the LDS input ring), LDS
+ * bytes}; returns 1, or 0 where asr_conv3x3_tr_supported is 0.  The plan only
+ * names (Cin, Cout, wpx, nw) combinations asr_conv3x3_tr_has_kernel reports,
+ * the list the launcher dispatches over.  asr_conv3x3_tr_wgrad_plan: the same
+ * for asr_conv3x3_tr_wgrad, out = {RC, LDS bytes}. */
+int asr_conv3x3_tr_plan(int Cin, int Cout, int Fp, int out[4]);
+int asr_conv3x3_tr_has_kernel(int Cin, int Cout, int wpx, int nw);
+int asr_conv3x3_tr_wgrad_plan(int Cin, int Cout, int Fp, int out[2]);
 int asr_conv3x3_tr(const void* in, long long P, int Cin, int Fp, int sign, const void* w,
                    int Cout, const float* bias, void* out, int out_dtype, void* stream);
 /* Weight-gradient image of the same convolution (csrc/conv.hip, replaces the

@@ -67,6 +67,9 @@ SIGNATURES = {
     'asr_conv3x3_c1_forward_xs': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                           c_vp, c_int, c_vp]),
     'asr_conv3x3_tr_supported': (c_int, [c_int, c_int, c_int]),
+    'asr_conv3x3_tr_plan': (c_int, [c_int, c_int, c_int, c_vp]),
+    'asr_conv3x3_tr_has_kernel': (c_int, [c_int, c_int, c_int, c_int]),
+    'asr_conv3x3_tr_wgrad_plan': (c_int, [c_int, c_int, c_int, c_vp]),
     'asr_conv3x3_tr': (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int,
                                c_vp]),
     'asr_vgg_zero_halo': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
@@ -371,6 +374,25 @@ def ctc_grad_plan(T, B, V, gld, max_label_len, acts_addr, stride_t, stride_b, wi
     call('asr_ctc_grad_plan', T, B, V, gld, max_label_len, ctypes.c_void_p(acts_addr), stride_t,
          stride_b, int(bool(with_bias)), cus, ctypes.byref(plan))
     return plan
+
+
+def conv3x3_tr_plan(cin, cout, fp):
+    """asr_conv3x3_tr_plan: (wpx, nw, RC, LDS bytes) of the tap-resident
+    convolution at this channel pair and row pitch (host only), or None where
+    the kernel does not take the shape."""
+    out = (c_int * 4)()
+    if not query('asr_conv3x3_tr_plan', int(cin), int(cout), int(fp), out):
+        return None
+    return tuple(out)
+
+
+def conv3x3_tr_wgrad_plan(cin, cout, fp):
+    """asr_conv3x3_tr_wgrad_plan: (RC, LDS bytes) of the tap-resident weight
+    gradient (host only), or None where the kernel does not take the shape."""
+    out = (c_int * 2)()
+    if not query('asr_conv3x3_tr_wgrad_plan', int(cin), int(cout), int(fp), out):
+        return None
+    return tuple(out)
 
 
 class AttBeamOpts(ctypes.Structure):

@@ -567,6 +567,25 @@ struct TrPlan {
   int RC;
 };
 
+// The conv3x3_tr instantiations that exist, X(CIN, COUT, WPX, NW): the plan
+// chooses among them and the launcher dispatches over them, so a shape the
+// plan takes always has a kernel.
+#define TR_KERNELS(X) \
+  X(64, 64, 64, 0)    \
+  X(64, 64, 64, 4)    \
+  X(64, 128, 32, 4)   \
+  X(128, 64, 32, 4)   \
+  X(128, 128, 32, 4)  \
+  X(128, 128, 32, 3)
+
+bool tr_has_kernel(int Cin, int Cout, int wpx, int nw) {
+#define TR_HAS(CI, CO, WPX, NW) \
+  if (Cin == CI && Cout == CO && wpx == WPX && nw == NW) return true;
+  TR_KERNELS(TR_HAS)
+#undef TR_HAS
+  return false;
+}
+
 template <int CIN, int COUT, int WPX, int NW>
 int tr_launch(const TrArgs& a0, int out_bf16, hipStream_t s, size_t lds) {
   TrArgs a = a0;
@@ -596,22 +615,29 @@ int tr_launch(const TrArgs& a0, int out_bf16, hipStream_t s, size_t lds) {
 }
 
 // (wpx, nw) per channel pair: 64 x 64 waves for Cout = 64 at Cin = 64, 128 x 32
-// otherwise; four weight slots where the LDS allows, else three.
+// otherwise; the resident weight image (nw = 0) where the pair has that kernel
+// and the image fits, else the most weight slots (four, then three) that fit
+// in LDS and have a kernel.  A pitch at which three slots would fit but only
+// the four-slot kernel exists is refused (the callers take the tap GEMM).
 bool tr_plan(int Cin, int Cout, int Fp, TrPlan* pl) {
   if (!((Cin == 64 || Cin == 128) && (Cout == 64 || Cout == 128)) || Fp < 3) return false;
   pl->wpx = (Cin == 64 && Cout == 64) ? 64 : 32;
   const int BM = 4 * pl->wpx;
-  pl->RC = ((2 * BM + 2 * Fp + 16) + 15) / 16 * 16;
+  pl->RC = (int)((2LL * BM + 2LL * Fp + 16 + 15) / 16 * 16);
   const size_t halo = (size_t)(Cin / 64) * pl->RC * 128;
   const size_t wslot = (size_t)Cout * 128;
   const size_t cap = 160 * 1024;
   const char* wr = getenv("ASR_CONV_TR_WRES");   // A/B: 0 keeps the weight ring
-  if (Cin == 64 && Cout == 64 && halo + 9 * wslot <= cap && !(wr && wr[0] == '0')) pl->nw = 0;
-  else if (halo + 4 * wslot <= cap) pl->nw = 4;
-  else if (halo + 3 * wslot <= cap) pl->nw = 3;
-  else return false;
-  pl->lds = halo + (pl->nw ? pl->nw : 9 * (Cin / 64)) * wslot;
-  return true;
+  const int try_nw[3] = {(wr && wr[0] == '0') ? -1 : 0, 4, 3};
+  for (int nw : try_nw) {
+    if (nw < 0 || !tr_has_kernel(Cin, Cout, pl->wpx, nw)) continue;
+    const size_t lds = halo + (nw ? nw : 9 * (Cin / 64)) * wslot;
+    if (lds > cap) continue;
+    pl->nw = nw;
+    pl->lds = lds;
+    return true;
+  }
+  return false;
 }
 
 }  // namespace
@@ -622,6 +648,28 @@ using namespace asr;
 extern "C" int asr_conv3x3_tr_supported(int Cin, int Cout, int Fp) {
   TrPlan pl;
   return tr_plan(Cin, Cout, Fp, &pl) ? 1 : 0;
+}
+
+extern "C" int asr_conv3x3_tr_plan(int Cin, int Cout, int Fp, int out[4]) {
+  TrPlan pl;
+  if (!out || !tr_plan(Cin, Cout, Fp, &pl)) return 0;
+  out[0] = pl.wpx;
+  out[1] = pl.nw;
+  out[2] = pl.RC;
+  out[3] = (int)pl.lds;
+  return 1;
+}
+
+extern "C" int asr_conv3x3_tr_has_kernel(int Cin, int Cout, int wpx, int nw) {
+  return tr_has_kernel(Cin, Cout, wpx, nw) ? 1 : 0;
+}
+
+extern "C" int asr_conv3x3_tr_wgrad_plan(int Cin, int Cout, int Fp, int out[2]) {
+  TrwPlan pl;
+  if (!out || !trw_plan(Cin, Cout, Fp, &pl)) return 0;
+  out[0] = pl.RC;
+  out[1] = (int)pl.lds;
+  return 1;
 }
 
 extern "C" int asr_conv3x3_tr(const void* in, long long P, int Cin, int Fp, int sign,
@@ -659,14 +707,10 @@ extern "C" int asr_conv3x3_tr(const void* in, long long P, int Cin, int Fp, int 
                                      4 * ASR_PTAG_CONV_TR);
   const int bf = out_dtype == ASR_DT_BF16;
   int rc = ASR_ERR_UNSUPPORTED;
-#define TR_CASE(CI, CO, WPX, NW)                                                         \
-  if (Cin == CI && Cout == CO && pl.wpx == WPX && pl.nw == NW) rc = tr_launch<CI, CO, WPX, NW>(a, bf, s, pl.lds)
-  TR_CASE(64, 64, 64, 0);
-  else TR_CASE(64, 64, 64, 4);
-  else TR_CASE(64, 128, 32, 4);
-  else TR_CASE(128, 64, 32, 4);
-  else TR_CASE(128, 128, 32, 4);
-  else TR_CASE(128, 128, 32, 3);
+#define TR_CASE(CI, CO, WPX, NW)                                 \
+  if (Cin == CI && Cout == CO && pl.wpx == WPX && pl.nw == NW)   \
+    rc = tr_launch<CI, CO, WPX, NW>(a, bf, s, pl.lds);
+  TR_KERNELS(TR_CASE)
 #undef TR_CASE
   prof_end_launch(ASR_PROF_GEMM, slot, s);
   if (rc != ASR_OK) {
