@@ -103,13 +103,20 @@ __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x)
 __device__ __forceinline__ float lg2(float x) { return __builtin_amdgcn_logf(x); }
 
 // Online log-sum-exp accumulator (running max m, sum s of exp(x - m)).
+// While m is still -inf the values seen so far are -inf (masked classes) or
+// NaN: they add 0, or a NaN to keep -- exp(-inf - -inf) would turn a run of
+// masked classes into a NaN log-sum-exp.  lse_none(t): that term, from the
+// plain sum t of the values (-inf, or NaN).
+__device__ __forceinline__ float lse_none(float t) { return t == neg_inf() ? 0.f : t; }
 __device__ __forceinline__ void lse_acc4(float& m, float& s, float4 v) {
   const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
   if (mx > m) { s *= __expf(m - mx); m = mx; }
+  if (m == neg_inf()) { s += lse_none((v.x + v.y) + (v.z + v.w)); return; }
   s += __expf(v.x - m) + __expf(v.y - m) + __expf(v.z - m) + __expf(v.w - m);
 }
 __device__ __forceinline__ void lse_acc1(float& m, float& s, float x) {
   if (x > m) { s *= __expf(m - x); m = x; }
+  if (m == neg_inf()) { s += lse_none(x); return; }
   s += __expf(x - m);
 }
 
@@ -196,6 +203,11 @@ __global__ void __launch_bounds__(256) ctc_emit_wide(const float* __restrict__ a
                            fmaxf(fmaxf(fmaxf(v2.x, v2.y), fmaxf(v2.z, v2.w)),
                                  fmaxf(fmaxf(v3.x, v3.y), fmaxf(v3.z, v3.w))));
     const float mn = fmaxf(m, mx);
+    if (mn == neg_inf()) {  // sixteen masked classes and nothing finite before them
+      s += lse_none((((v0.x + v0.y) + (v0.z + v0.w)) + ((v1.x + v1.y) + (v1.z + v1.w))) +
+                    (((v2.x + v2.y) + (v2.z + v2.w)) + ((v3.x + v3.y) + (v3.z + v3.w))));
+      continue;
+    }
     s *= __expf(m - mn);  // m = -inf on the first chunk: 0 * 0
     m = mn;
     s += (__expf(v0.x - m) + __expf(v0.y - m) + __expf(v0.z - m) + __expf(v0.w - m)) +
