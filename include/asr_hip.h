@@ -782,6 +782,49 @@ int asr_ctc_beam_stream_nbest(const void* state, size_t state_bytes, int max_fra
                               int32_t* lens, float* scores, int32_t* counts, void* stream);
 int asr_ctc_beam_stream_status(const void* state, int B, int32_t* status, void* stream);
 
+/* asr_ctc_align: CTC forced alignment (csrc/ctc_align.hip): for each utterance
+ *   the best (Viterbi) path of its KNOWN labels through the blank-interleaved
+ *   lattice.  Tb = min(act_lens[b], T); labels l_0..l_{L-1} in [0, V), none
+ *   equal to `blank` (labels_flat / label_lens as for asr_ctc_forward);
+ *   S = 2 L + 1 states, state s of class c(s) = blank (s even) or l_{(s-1)/2}.
+ *   The path is chosen on the RAW logits x (a per-frame normaliser moves no
+ *   argmax), in float32 adds and compares only:
+ *     v_0(0) = x_0[blank], v_0(1) = x_0[l_0], -inf elsewhere;
+ *     v_t(s) = fl32(m + x_t[c(s)]), m = the max over the predecessors in the
+ *       order s, s-1, s-2 (s-2 only for odd s >= 3 with c(s) != c(s-2)); the
+ *       backpointer is the FIRST predecessor in that order that attains m;
+ *     end state S-1 if v_{Tb-1}(S-1) >= v_{Tb-1}(S-2), else S-2 (L = 0: 0).
+ *   A row is feasible iff the end value is > -inf (not so: Tb = 0 with L > 0,
+ *   L + repeats > Tb, a -inf logit on a needed column); a label outside
+ *   [0, V), one equal to blank, or a label_len outside [0, max_label_len]
+ *   also leaves the row infeasible.
+ *   ali int32 [B][T]: c(s_t) for t < Tb, -1 for t >= Tb and for every frame of
+ *     an infeasible row.  starts / ends int32 [B][max_label_len] (both may be
+ *     NULL): first / last frame (inclusive) in label j's state; -1 for
+ *     j >= L and for infeasible rows.  scores f32 [B]: normalize != 0: the
+ *     path's log-probability sum_t (x_t[c(s_t)] - lse_t), lse_t over all V
+ *     classes (-inf classes add 0), summed per 64-frame chunk by a fixed
+ *     lane tree and over the chunks from the last to the first;
+ *     normalize == 0: the end value v, bitwise; -inf for an infeasible row;
+ *     0 for Tb = 0 with L = 0.
+ *   Frames t >= act_lens[b] are never read.  NaN at a blank or label column
+ *   is outside the contract (memory-safe, ASR_OK, values unspecified).
+ *   Stream work only: no host read, no allocation, no synchronisation; the
+ *   workspace need not be zero.  Strides as for asr_ctc_forward (time-major
+ *   or batch-major).  max_label_len > 511 (more than 1024 lattice states) or
+ *   an operand of 2 GiB or more: ASR_ERR_UNSUPPORTED before any launch, with
+ *   nothing written (asr_ctc_align_ws_bytes is then 0).
+ * asr_ctc_align_limits: frames per backtrace chunk, and the frames whose
+ *   backpointer words stay in LDS (later frames' words pass through the
+ *   workspace). */
+size_t asr_ctc_align_ws_bytes(int T, int B, int V, int max_label_len);
+int asr_ctc_align(const float* logits, long long stride_t, long long stride_b, int T, int B, int V,
+                  const int32_t* labels_flat, const int32_t* label_lens, const int32_t* act_lens,
+                  int max_label_len, int blank, int normalize,
+                  int32_t* ali, int32_t* starts, int32_t* ends, float* scores,
+                  void* workspace, size_t ws_bytes, void* stream);
+int asr_ctc_align_limits(int* chunk_frames, int* lds_frames);
+
 /* ------------------------------------------------------ hypothesis scoring
  * asr_edit_distance: per utterance pair the edit distance between a decoded
  *   hypothesis and its transcript with the substitution / insertion / deletion

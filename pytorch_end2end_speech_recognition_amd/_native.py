@@ -24,6 +24,7 @@ c_vp = ctypes.c_void_p
 c_str = ctypes.c_char_p
 
 ASR_OK = 0
+ASR_ERR_WORKSPACE = -2
 ASR_ERR_UNSUPPORTED = -4
 ASR_DT_F32 = 0
 ASR_DT_BF16 = 1
@@ -164,6 +165,10 @@ SIGNATURES = {
     'asr_ctc_beam_stream_nbest': (c_int, [c_vp, c_size, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'asr_ctc_beam_stream_status': (c_int, [c_vp, c_int, c_vp, c_vp]),
+    'asr_ctc_align_ws_bytes': (c_size, [c_int] * 4),
+    'asr_ctc_align': (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                              c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'asr_ctc_align_limits': (c_int, [c_vp, c_vp]),
     'asr_edit_distance_ws_bytes': (c_size, [c_int, c_int, c_int]),
     'asr_edit_distance': (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp,
                                   c_vp, c_vp, c_vp, c_size, c_vp]),

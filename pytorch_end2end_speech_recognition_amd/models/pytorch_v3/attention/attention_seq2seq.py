@@ -32,6 +32,7 @@ from .attention_layer import AttentionMechanism
 from .ctc_prefix_score import CtcPrefixScorer, log_softmax_f32
 from ..ctc.ctc import _concatenate_labels_np
 from ..ctc.decoders.greedy_decoder import GreedyDecoder
+from ..ctc.align import align_logits, check_align_labels
 
 
 class AttentionSeq2seq(ModelBase):
@@ -520,6 +521,26 @@ class AttentionSeq2seq(ModelBase):
             hyps = self._decode_ctc_greedy_np(logits, enc_lens_d)
         best = np.array([h - 1 for h in hyps] + [None], dtype=object)[:-1]
         return best, self.encoder.last_perm_np.copy()
+
+    @eval_retry
+    @torch.no_grad()
+    def align_ctc(self, xs, x_lens, ys, y_lens):
+        """CTC forced alignment on fc_ctc_0's logits (CTC.align's contract:
+        ys [B, L] padded in decode_ctc()'s index space, reordered by the
+        encoder's perm_idx).  Returns (alignments, spans, scores, perm_idx).
+        ValueError: a model built without a CTC loss weight, or CTC.align's
+        label checks, before the encoder runs."""
+        if getattr(self, 'fc_ctc_0', None) is None:
+            raise ValueError('align_ctc needs the CTC head fc_ctc_0 (a model built with a CTC '
+                             'loss weight > 0)')
+        ys, y_lens = check_align_labels(ys, y_lens, self.num_classes - 1)
+        self.eval()
+        xs_d = self.np2var(xs, dtype='float')
+        enc_out, enc_lens_d, _ = self._encode(xs_d, x_lens)
+        logits = self.fc_ctc_0(enc_out)
+        check_recurrences(self)
+        perm = self.encoder.last_perm_np.copy()
+        return align_logits(logits, enc_lens_d, ys, y_lens, perm) + (perm,)
 
     @eval_retry
     @torch.no_grad()

@@ -23,6 +23,7 @@ from ..encoders.load_encoder import load
 from ..criterion import cross_entropy_label_smoothing
 from .decoders.beam_search_decoder import BeamSearchDecoder
 from .decoders.greedy_decoder import GreedyDecoder
+from .align import align_logits, check_align_labels
 
 
 class _Head(object):
@@ -449,6 +450,31 @@ class CTC(ModelBase):
                                              normalize=True)
         best_hyps = np.array([h - 1 for h in best_hyps] + [None], dtype=object)[:-1]
         return best_hyps, None, self.encoder.last_perm_np.copy()
+
+    @eval_retry
+    @torch.no_grad()
+    def align(self, xs, x_lens, ys, y_lens, task_index=0):
+        """CTC forced alignment of known transcripts (csrc/ctc_align.hip): the
+        best path of ys through the lattice of the head `task_index` selects
+        (as in decode()).  ys [B, L] padded, in the index space decode()
+        returns (labels from 0), y_lens [B]; both are reordered by the
+        encoder's perm_idx, as in error_rate().  Returns (alignments, spans,
+        scores, perm_idx): alignments[b] int32 [output frames of b], the label
+        of every encoder OUTPUT frame with blank = -1; spans[b] int32 [L_b, 2]
+        the first and last frame of every label; scores float32 [B] the path's
+        log-probability.  A row with no alignment (more labels plus repeats
+        than frames): an empty alignment, [0, 2] spans, -inf.  ValueError
+        before the encoder runs: a label outside [0, num_classes), y_lens[b] >
+        ys.shape[1], a negative length.  One host read, after the search."""
+        sub = hasattr(self, 'main_loss_weight') and task_index == 1
+        ys, y_lens = check_align_labels(
+            ys, y_lens, (self.num_classes_sub if sub else self.num_classes) - 1)
+        self.eval()
+        xs_d = self.np2var(xs, dtype='float')
+        logits, out_lens_d, _ = self._task_logits(xs_d, x_lens, task_index)
+        check_recurrences(self)
+        perm = self.encoder.last_perm_np.copy()
+        return align_logits(logits, out_lens_d, ys, y_lens, perm) + (perm,)
 
     def stream(self, batch_size, beam_width=1, rnnlm=None, lm_weight=0, insertion_bonus=0,
                max_frames=4096):

@@ -3416,6 +3416,154 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, unit='token', eos=None, space=No
     return out
 
 
+# ---------------------------------------------------------------------------
+# CTC forced alignment (csrc/ctc_align.hip)
+# ---------------------------------------------------------------------------
+_align = {'path': None, 'ws': {}}   # ws: device -> workspace of the largest call so far
+
+
+def last_ctc_align_path():
+    """'device' or 'host': where the last ctc_align ran (None before the first
+    one).  'host': the kernel refused the shape (ASR_ERR_UNSUPPORTED)."""
+    return _align['path']
+
+
+def ctc_align_limits():
+    """(frames per backtrace chunk, frames whose backpointers stay in LDS) of
+    asr_ctc_align (asr_ctc_align_limits)."""
+    c, r = ctypes.c_int(0), ctypes.c_int(0)
+    N.call('asr_ctc_align_limits', ctypes.byref(c), ctypes.byref(r))
+    return c.value, r.value
+
+
+def ctc_align_host(logits, lens, labels_flat, label_lens, max_label_len, blank=0, normalize=True,
+                   spans=True):
+    """asr_ctc_align restated on host arrays in numpy float32 (the recurrence
+    of include/asr_hip.h: raw logits, one rounding per add, first predecessor
+    in the order s, s-1, s-2 on ties).  logits [B, T, V]; returns numpy
+    (ali int32 [B, T], starts, ends int32 [B, max_label_len] or None, scores
+    float32 [B]); the normalised score is summed in float64 and rounded once."""
+    x = np.asarray(logits, dtype=np.float32)
+    B, T, V = x.shape
+    lens = np.asarray(lens).reshape(-1).astype(np.int64)
+    label_lens = np.asarray(label_lens).reshape(-1).astype(np.int64)
+    flat = np.asarray(labels_flat).reshape(-1).astype(np.int64)
+    M = int(max_label_len)
+    ninf = np.float32(-np.inf)
+    ali = np.full((B, T), -1, np.int32)
+    starts = np.full((B, M), -1, np.int32)
+    ends = np.full((B, M), -1, np.int32)
+    scores = np.full(B, ninf, np.float32)
+    off = 0
+    for b in range(B):
+        L = int(label_lens[b])
+        lab = flat[off:off + max(L, 0)]
+        off += max(L, 0)
+        Tb = max(min(int(lens[b]), T), 0)
+        if L < 0 or L > M or len(lab) != L or ((lab < 0) | (lab >= V) | (lab == blank)).any():
+            continue
+        if Tb == 0:
+            if L == 0:
+                scores[b] = 0
+            continue
+        S = 2 * L + 1
+        cls = np.full(S, blank, np.int64)
+        cls[1::2] = lab
+        skip = np.zeros(S, bool)
+        skip[3::2] = lab[1:] != lab[:-1]
+        g = x[b, :Tb][:, cls]
+        v = np.full(S, ninf, np.float32)
+        v[:min(S, 2)] = g[0, :2]
+        bp = np.zeros((Tb, S), np.int8)
+        with np.errstate(invalid='ignore'):
+            for t in range(1, Tb):
+                a1 = np.concatenate(([ninf], v[:-1]))
+                a2 = np.where(skip, np.concatenate(([ninf, ninf], v[:-2]))[:S], ninf)
+                m, d = v.copy(), bp[t]
+                k = a1 > m
+                m[k], d[k] = a1[k], 1
+                k = a2 > m
+                m[k], d[k] = a2[k], 2
+                v = (m + g[t]).astype(np.float32)
+        s = S - 1 if L == 0 or v[S - 1] >= v[S - 2] else S - 2
+        if not v[s] > ninf:
+            continue
+        end_value = v[s]
+        path = np.empty(Tb, np.int64)
+        for t in range(Tb - 1, -1, -1):
+            path[t] = s
+            s -= int(bp[t, s])
+        ali[b, :Tb] = cls[path]
+        for j in range(L):
+            at = np.nonzero(path == 2 * j + 1)[0]
+            starts[b, j], ends[b, j] = at[0], at[-1]
+        if normalize:
+            rows = x[b, :Tb].astype(np.float64)
+            mx = rows.max(axis=1, keepdims=True)
+            lse = mx[:, 0] + np.log(np.exp(rows - mx).sum(axis=1))
+            scores[b] = np.float32((g[np.arange(Tb), path].astype(np.float64) - lse).sum())
+        else:
+            scores[b] = end_value
+    return ali, (starts if spans else None), (ends if spans else None), scores
+
+
+@torch.no_grad()
+def ctc_align(logits, lens, labels_flat, label_lens, max_label_len, blank=0, normalize=True,
+              spans=True):
+    """CTC forced alignment on the device (asr_ctc_align): logits [B, T, V]
+    (any strides with a unit class stride: a transposed time-major tensor is
+    read in place), lens [B], labels_flat / label_lens as for ctc_loss.
+    Returns device tensors (ali int32 [B, T]: the class of every frame of the
+    best path, -1 beyond the length and on infeasible rows; starts, ends int32
+    [B, max_label_len]: first / last frame of every label, or None without
+    `spans`; scores float32 [B]: the path's log-probability, or with
+    normalize=False the sum of its raw logits).  No host synchronisation.  A
+    shape the kernel refuses (max_label_len > 511) runs ctc_align_host on host
+    copies instead and last_ctc_align_path() says so."""
+    N.require_device(logits, lens, labels_flat, label_lens)
+    dev = logits.device
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    if logits.dim() != 3:
+        raise ValueError('ctc_align: [B, T, V] logits expected, got %r' % (tuple(logits.shape),))
+    if logits.stride(2) != 1 or logits.stride(0) <= 0 or logits.stride(1) <= 0:
+        logits = logits.contiguous()
+    B, T, V = logits.shape
+    M = int(max_label_len)
+    lens = lens.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    label_lens = label_lens.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    labels_flat = labels_flat.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if lens.numel() != B or label_lens.numel() != B:
+        raise ValueError('ctc_align: batch sizes differ')
+    if labels_flat.numel() == 0:    # no storage to point at
+        labels_flat = torch.zeros(1, dtype=torch.int32, device=dev)
+    ali = torch.empty(B, T, dtype=torch.int32, device=dev)
+    starts = torch.empty(B, M, dtype=torch.int32, device=dev) if spans else None
+    ends = torch.empty(B, M, dtype=torch.int32, device=dev) if spans else None
+    scores = torch.empty(B, dtype=torch.float32, device=dev)
+    if B == 0 or T == 0:
+        raise ValueError('ctc_align: empty batch or no frames')
+    nb = N.query('asr_ctc_align_ws_bytes', T, B, V, M)
+    ws = _align['ws'].get(dev)
+    if ws is None or ws.numel() < nb:
+        ws = _align['ws'][dev] = _ws(nb, dev)
+    rc = getattr(N.lib(), 'asr_ctc_align')(
+        N.ptr(logits), logits.stride(1), logits.stride(0), T, B, V, N.ptr(labels_flat),
+        N.ptr(label_lens), N.ptr(lens), M, int(blank), int(bool(normalize)), N.ptr(ali),
+        N.ptr(starts) if spans and M else None, N.ptr(ends) if spans and M else None,
+        N.ptr(scores), N.ptr(ws), ws.numel(), N.stream_handle(dev))
+    if rc == N.ASR_OK:
+        _align['path'] = 'device'
+        return ali, starts, ends, scores
+    if rc != N.ASR_ERR_UNSUPPORTED:
+        raise N.NativeError('asr_ctc_align failed (rc=%d): %s'
+                            % (rc, N.lib().asr_last_error().decode(errors='replace')))
+    _align['path'] = 'host'
+    res = ctc_align_host(logits.cpu().numpy(), lens.cpu().numpy(), labels_flat.cpu().numpy(),
+                         label_lens.cpu().numpy(), M, blank, normalize, spans)
+    return tuple(None if r is None else torch.from_numpy(r).to(dev) for r in res)
+
+
 def row_argmax(x):
     N.require_device(x)
     x = x.contiguous()
