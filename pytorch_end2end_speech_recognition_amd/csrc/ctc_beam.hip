@@ -247,18 +247,37 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   return v;
 }
 
-// A streaming session's search state (asr_ctc_beam_stream_*): per row the beam
-// between calls in rank order, the node pool of max_frames * W + 1 nodes, the
-// frames consumed and a status word; with an LM the 2 W slots of h, c and q.
-struct BeamState {
-  int32_t *frames, *status;      // [B]
+// A beam in global memory: per row the entries in rank order, the node pool and,
+// with an LM, the 2 W slots of h, c and q.  The LM search keeps it in its
+// workspace between frames, a streaming session in its state between calls.
+struct Beam {
   int32_t *n, *nnodes;           // [B]
   int32_t *node, *par, *last, *depth, *slot;   // [B][W]
-  int32_t *src, *tok;            // [B][W] lm_step's work list (no meaning between calls)
+  int32_t *src, *tok;            // [B][W] lm_step's work: parent slot (-1: zero state), LM token (-1: none)
   float *pb, *pnb;
   unsigned long long *hash, *phash;
-  Node* pools;                   // [B][max_frames * W + 1]
-  float *h, *c, *q;
+  Node* pools;                   // [B][pool frames * W + 1]
+  float *h, *c;                  // [B][2W][layers][H] by slot
+  float* q;                      // [B][2W][V] by slot: the LM's log-softmax after the entry's prefix
+};
+
+// the root: the empty prefix, alone in row b's beam, in LM slot 0
+__device__ __forceinline__ void beam_root(const Beam& m, int b, int W, int pool_frames) {
+  const long long r = (long long)b * W;
+  Node* pool = m.pools + (long long)b * ((long long)pool_frames * W + 1);
+  pool[0].parent = 0;
+  pool[0].label = -1;
+  m.n[b] = 1; m.nnodes[b] = 1;
+  m.node[r] = 0; m.par[r] = 0; m.last[r] = -1; m.depth[r] = 0; m.slot[r] = 0;
+  m.pb[r] = 0.f; m.pnb[r] = neg_inf();
+  m.hash[r] = 0; m.phash[r] = 0;
+}
+
+// A streaming session's search state (asr_ctc_beam_stream_*): the beam between
+// calls, its node pools of max_frames * W + 1 nodes, and per row the frames
+// consumed and a status word.
+struct BeamState : Beam {
+  int32_t *frames, *status;      // [B]
   int max_frames;
 };
 
@@ -451,7 +470,7 @@ __global__ void __launch_bounds__(64) beam_search_kernel(
 }
 
 // ------------------------------------------- the search with a language model
-struct LmP {
+struct LmP : Beam {              // the beam between frames
   // the call
   const float* logits;
   long long st, sb;
@@ -465,14 +484,6 @@ struct LmP {
   const float* lse;              // [B][T]
   float* topv;                   // [B][W][W + 1] per parent: lp + alpha q, best first
   int32_t* topc;
-  int32_t *n, *nnodes;           // [B]
-  int32_t *node, *par, *last, *depth, *slot;   // [B][W] the beam between frames
-  float *pb, *pnb;
-  unsigned long long *hash, *phash;
-  int32_t *src, *tok;            // [B][W] lm_step's work: parent slot (-1: zero state), LM token (-1: none)
-  Node* pools;
-  float *h, *c;                  // [B][2W][layers][H] by slot
-  float* q;                      // [B][2W][V] by slot: the LM's log-softmax after the entry's prefix
 };
 
 __device__ __forceinline__ int lm_class(int c, int blank) { return c - (c > blank ? 1 : 0); }
@@ -486,15 +497,7 @@ __global__ void __launch_bounds__(64) lm_init_kernel(LmP p) {
     p.tok[r + lane] = lane == 0 ? p.V - 1 : -1;
     p.src[r + lane] = -1;
   }
-  if (lane == 0) {
-    Node* pool = p.pools + (long long)b * ((long long)p.poolT * p.W + 1);
-    pool[0].parent = 0;
-    pool[0].label = -1;
-    p.n[b] = 1; p.nnodes[b] = 1;
-    p.node[r] = 0; p.par[r] = 0; p.last[r] = -1; p.depth[r] = 0; p.slot[r] = 0;
-    p.pb[r] = 0.f; p.pnb[r] = neg_inf();
-    p.hash[r] = 0; p.phash[r] = 0;
-  }
+  if (lane == 0) beam_root(p, b, p.W, p.poolT);
 }
 
 // Per beam entry (parent) the W + 1 best non-blank classes by lp_t[c] + alpha
@@ -853,39 +856,112 @@ extern "C" int asr_ctc_beam_rows(const float* logits, long long stride_t, long l
 namespace asr {
 namespace {
 
-struct LmBeamWs {
-  size_t lse, topv, topc, n, nnodes, node, par, last, depth, slot, src, tok, pb, pnb, hash, phash,
-      pool, h, c, q, total;
+// `bytes` more from the running offset o, the next array 16-B aligned: where they start
+inline size_t take(size_t& o, size_t bytes) {
+  const size_t at = o;
+  o += align16(bytes);
+  return at;
+}
+
+// Where the arrays of a Beam lie from their base.  The order and the alignment
+// are part of a session state's format.
+struct BeamLayout {
+  size_t n, nnodes, node, par, last, depth, slot, src, tok, pb, pnb, hash, phash, pool, h, c, q;
 };
 
-// layers == 0: no language model, no state and no row cache
+// from the running offset o; layers == 0: no language model, no h / c / q
+inline BeamLayout beam_layout(size_t& o, int pool_frames, int B, int V, int W, int layers, int H) {
+  BeamLayout w;
+  const size_t R = (size_t)B * W;
+  w.n = take(o, (size_t)B * sizeof(int32_t));
+  w.nnodes = take(o, (size_t)B * sizeof(int32_t));
+  w.node = take(o, R * sizeof(int32_t));
+  w.par = take(o, R * sizeof(int32_t));
+  w.last = take(o, R * sizeof(int32_t));
+  w.depth = take(o, R * sizeof(int32_t));
+  w.slot = take(o, R * sizeof(int32_t));
+  w.src = take(o, R * sizeof(int32_t));
+  w.tok = take(o, R * sizeof(int32_t));
+  w.pb = take(o, R * sizeof(float));
+  w.pnb = take(o, R * sizeof(float));
+  w.hash = take(o, R * sizeof(unsigned long long));
+  w.phash = take(o, R * sizeof(unsigned long long));
+  w.pool = take(o, (size_t)B * ((size_t)pool_frames * W + 1) * sizeof(Node));
+  w.h = take(o, 2 * R * (size_t)layers * H * sizeof(float));
+  w.c = take(o, 2 * R * (size_t)layers * H * sizeof(float));
+  w.q = take(o, layers > 0 ? 2 * R * (size_t)V * sizeof(float) : 0);
+  return w;
+}
+
+inline void beam_bind(Beam& m, void* mem, const BeamLayout& w) {
+  char* base = (char*)mem;
+  m.n = (int32_t*)(base + w.n); m.nnodes = (int32_t*)(base + w.nnodes);
+  m.node = (int32_t*)(base + w.node); m.par = (int32_t*)(base + w.par);
+  m.last = (int32_t*)(base + w.last); m.depth = (int32_t*)(base + w.depth);
+  m.slot = (int32_t*)(base + w.slot); m.src = (int32_t*)(base + w.src);
+  m.tok = (int32_t*)(base + w.tok);
+  m.pb = (float*)(base + w.pb); m.pnb = (float*)(base + w.pnb);
+  m.hash = (unsigned long long*)(base + w.hash); m.phash = (unsigned long long*)(base + w.phash);
+  m.pools = (Node*)(base + w.pool);
+  m.h = (float*)(base + w.h); m.c = (float*)(base + w.c); m.q = (float*)(base + w.q);
+}
+
+struct LmBeamWs {
+  size_t lse, topv, topc;
+  BeamLayout beam;
+  size_t total;
+};
+
 inline LmBeamWs lm_beam_ws(int T, int B, int V, int W, int layers, int H) {
   LmBeamWs w;
   const size_t frames = (size_t)B * T, K = (size_t)W + 1, R = (size_t)B * W;
   size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o += align16(bytes); return at; };
-  w.lse = take(frames * sizeof(float));
-  w.topv = take(R * K * sizeof(float));
-  w.topc = take(R * K * sizeof(int32_t));
-  w.n = take((size_t)B * sizeof(int32_t));
-  w.nnodes = take((size_t)B * sizeof(int32_t));
-  w.node = take(R * sizeof(int32_t));
-  w.par = take(R * sizeof(int32_t));
-  w.last = take(R * sizeof(int32_t));
-  w.depth = take(R * sizeof(int32_t));
-  w.slot = take(R * sizeof(int32_t));
-  w.src = take(R * sizeof(int32_t));
-  w.tok = take(R * sizeof(int32_t));
-  w.pb = take(R * sizeof(float));
-  w.pnb = take(R * sizeof(float));
-  w.hash = take(R * sizeof(unsigned long long));
-  w.phash = take(R * sizeof(unsigned long long));
-  w.pool = take((size_t)B * ((size_t)T * W + 1) * sizeof(Node));
-  w.h = take(2 * R * (size_t)layers * H * sizeof(float));
-  w.c = take(2 * R * (size_t)layers * H * sizeof(float));
-  w.q = take(layers > 0 ? 2 * R * (size_t)V * sizeof(float) : 0);
+  w.lse = take(o, frames * sizeof(float));
+  w.topv = take(o, R * K * sizeof(float));
+  w.topc = take(o, R * K * sizeof(int32_t));
+  w.beam = beam_layout(o, T, B, V, W, layers, H);
   w.total = o;
   return w;
+}
+
+// What the searches with an LM ask of it; on ASR_OK *lm is null where the LM
+// term is absent (no LM, or weight 0).
+int lm_args_check(const char* who, const asr_att_beam_lm_t** lm, int V, const LmWho& lw) {
+  if (!*lm) return ASR_OK;
+  ASR_REQUIRE((*lm)->weight >= 0.0 && (*lm)->weight <= 3.0e38, ASR_ERR_ARG,
+              "%s: weight = %g is negative or not finite", who, (*lm)->weight);
+  const int rc = lm_net_check(*lm, V, lw);
+  if (rc != ASR_OK) return rc;
+  if ((*lm)->weight == 0.0) *lm = nullptr;
+  return ASR_OK;
+}
+
+// The frames [0, T) of the search on p's beam, three launches per frame (two
+// without an LM): the per-parent class lists, the new beam, the LM's step for
+// the entries that were extended.
+int lm_launch_frames(const LmP& p, int T, const asr_att_beam_lm_t* lm, hipStream_t s) {
+  const size_t lds_step = lm ? lm_cell_lds_floats(lm->Y, lm->H) * 4 : 0;
+  const long long entries = (long long)p.B * p.W;
+  for (int t = 0; t < T; ++t) {
+    if (p.V <= kWaveModeMaxV)
+      hipLaunchKernelGGL(lm_topk_kernel<1>, dim3((unsigned)((entries + 3) / 4)), dim3(256), 0, s,
+                         t, p);
+    else
+      hipLaunchKernelGGL(lm_topk_kernel<4>, dim3((unsigned)entries), dim3(256), 0, s, t, p);
+    hipLaunchKernelGGL(lm_select_kernel, dim3(p.B), dim3(64), 0, s, t, p);
+    if (lm)
+      hipLaunchKernelGGL(lm_step_kernel, dim3(p.W, p.B), dim3(LM_THREADS), lds_step, s, t, p);
+    ASR_LAUNCH_CHECK();
+  }
+  return ASR_OK;
+}
+
+// the root's LM state, from the zero state and <eos> (lm_step at t = -1)
+int lm_launch_root(const LmP& p, const asr_att_beam_lm_t* lm, hipStream_t s) {
+  hipLaunchKernelGGL(lm_step_kernel, dim3(1, p.B), dim3(LM_THREADS),
+                     lm_cell_lds_floats(lm->Y, lm->H) * 4, s, -1, p);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
 }
 
 constexpr LmWho kLmWho = {"ctc_beam_search_lm", "ctc_beam_search_lm", "LM dims", "CTC head",
@@ -913,12 +989,7 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   if (rc != ASR_OK) return rc;
   ASR_REQUIRE(beta == beta && fabs(beta) <= 3.0e38, ASR_ERR_ARG,
               "ctc_beam_search_lm: beta = %g is not finite", beta);
-  if (lm) {
-    ASR_REQUIRE(lm->weight >= 0.0 && lm->weight <= 3.0e38, ASR_ERR_ARG,
-                "ctc_beam_search_lm: weight = %g is negative or not finite", lm->weight);
-    if ((rc = lm_net_check(lm, V, kLmWho)) != ASR_OK) return rc;
-    if (lm->weight == 0.0) lm = nullptr;      // the LM term is absent
-  }
+  if ((rc = lm_args_check(who, &lm, V, kLmWho)) != ASR_OK) return rc;
   const int W = beam_width;
   const LmBeamWs w = lm_beam_ws(T, B, V, W, lm ? lm->layers : 0, lm ? lm->H : 0);
   if ((rc = beam_ws_check(who, ws, ws_bytes, w.total)) != ASR_OK) return rc;
@@ -933,15 +1004,7 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   float* lse = (float*)(base + w.lse);
   p.lse = lse;
   p.topv = (float*)(base + w.topv); p.topc = (int32_t*)(base + w.topc);
-  p.n = (int32_t*)(base + w.n); p.nnodes = (int32_t*)(base + w.nnodes);
-  p.node = (int32_t*)(base + w.node); p.par = (int32_t*)(base + w.par);
-  p.last = (int32_t*)(base + w.last); p.depth = (int32_t*)(base + w.depth);
-  p.slot = (int32_t*)(base + w.slot); p.src = (int32_t*)(base + w.src);
-  p.tok = (int32_t*)(base + w.tok);
-  p.pb = (float*)(base + w.pb); p.pnb = (float*)(base + w.pnb);
-  p.hash = (unsigned long long*)(base + w.hash); p.phash = (unsigned long long*)(base + w.phash);
-  p.pools = (Node*)(base + w.pool);
-  p.h = (float*)(base + w.h); p.c = (float*)(base + w.c); p.q = (float*)(base + w.q);
+  beam_bind(p, base, w.beam);
 
   hipStream_t s = (hipStream_t)stream;
   // the acoustic log-sum-exp of every frame, once (K = 0: no class ranking)
@@ -950,22 +1013,8 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, long long stride_t, l
   ASR_LAUNCH_CHECK();
   hipLaunchKernelGGL(lm_init_kernel, dim3(B), dim3(64), 0, s, p);
   ASR_LAUNCH_CHECK();
-  const size_t lds_step = lm ? lm_cell_lds_floats(lm->Y, lm->H) * 4 : 0;
-  if (lm) {
-    hipLaunchKernelGGL(lm_step_kernel, dim3(1, B), dim3(LM_THREADS), lds_step, s, -1, p);
-    ASR_LAUNCH_CHECK();
-  }
-  const long long entries = (long long)B * W;
-  for (int t = 0; t < T; ++t) {
-    if (V <= kWaveModeMaxV)
-      hipLaunchKernelGGL(lm_topk_kernel<1>, dim3((unsigned)((entries + 3) / 4)), dim3(256), 0, s,
-                         t, p);
-    else
-      hipLaunchKernelGGL(lm_topk_kernel<4>, dim3((unsigned)entries), dim3(256), 0, s, t, p);
-    hipLaunchKernelGGL(lm_select_kernel, dim3(B), dim3(64), 0, s, t, p);
-    if (lm) hipLaunchKernelGGL(lm_step_kernel, dim3(W, B), dim3(LM_THREADS), lds_step, s, t, p);
-    ASR_LAUNCH_CHECK();
-  }
+  if (lm && (rc = lm_launch_root(p, lm, s)) != ASR_OK) return rc;
+  if ((rc = lm_launch_frames(p, T, lm, s)) != ASR_OK) return rc;
   hipLaunchKernelGGL(lm_final_kernel, dim3(B), dim3(64), 0, s, p, hyps, hyp_lens, scores);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
@@ -993,72 +1042,33 @@ namespace {
 constexpr int kStreamFull = 1;       // status: frames were dropped at max_frames
 constexpr int kStreamInvalid = 2;    // status: the row's state is not one reset / feed left
 
+// the state buffer: the frame counts, the status words, the beam
 struct StreamLayout {
-  size_t frames, status, n, nnodes, node, par, last, depth, slot, src, tok, pb, pnb, hash, phash,
-      pool, h, c, q, total;
+  size_t frames, status;
+  BeamLayout beam;
+  size_t total;
 };
 
-// layers == 0: no language model, no h / c / q
 inline StreamLayout stream_layout(int max_frames, int B, int V, int W, int layers, int H) {
   StreamLayout w;
-  const size_t R = (size_t)B * W;
   size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o += align16(bytes); return at; };
-  w.frames = take((size_t)B * sizeof(int32_t));
-  w.status = take((size_t)B * sizeof(int32_t));
-  w.n = take((size_t)B * sizeof(int32_t));
-  w.nnodes = take((size_t)B * sizeof(int32_t));
-  w.node = take(R * sizeof(int32_t));
-  w.par = take(R * sizeof(int32_t));
-  w.last = take(R * sizeof(int32_t));
-  w.depth = take(R * sizeof(int32_t));
-  w.slot = take(R * sizeof(int32_t));
-  w.src = take(R * sizeof(int32_t));
-  w.tok = take(R * sizeof(int32_t));
-  w.pb = take(R * sizeof(float));
-  w.pnb = take(R * sizeof(float));
-  w.hash = take(R * sizeof(unsigned long long));
-  w.phash = take(R * sizeof(unsigned long long));
-  w.pool = take((size_t)B * ((size_t)max_frames * W + 1) * sizeof(Node));
-  w.h = take(2 * R * (size_t)layers * H * sizeof(float));
-  w.c = take(2 * R * (size_t)layers * H * sizeof(float));
-  w.q = take(layers > 0 ? 2 * R * (size_t)V * sizeof(float) : 0);
+  w.frames = take(o, (size_t)B * sizeof(int32_t));
+  w.status = take(o, (size_t)B * sizeof(int32_t));
+  w.beam = beam_layout(o, max_frames, B, V, W, layers, H);
   w.total = o;
   return w;
 }
 
-inline BeamState stream_state(void* state, const StreamLayout& w, int max_frames) {
-  char* base = (char*)state;
-  BeamState S;
-  S.frames = (int32_t*)(base + w.frames); S.status = (int32_t*)(base + w.status);
-  S.n = (int32_t*)(base + w.n); S.nnodes = (int32_t*)(base + w.nnodes);
-  S.node = (int32_t*)(base + w.node); S.par = (int32_t*)(base + w.par);
-  S.last = (int32_t*)(base + w.last); S.depth = (int32_t*)(base + w.depth);
-  S.slot = (int32_t*)(base + w.slot); S.src = (int32_t*)(base + w.src);
-  S.tok = (int32_t*)(base + w.tok);
-  S.pb = (float*)(base + w.pb); S.pnb = (float*)(base + w.pnb);
-  S.hash = (unsigned long long*)(base + w.hash); S.phash = (unsigned long long*)(base + w.phash);
-  S.pools = (Node*)(base + w.pool);
-  S.h = (float*)(base + w.h); S.c = (float*)(base + w.c); S.q = (float*)(base + w.q);
-  S.max_frames = max_frames;
-  return S;
-}
-
-// the per-frame kernels' view of a session: the beam and the LM slots are the state's
+// the per-frame kernels' view of a session: the beam is the state's
 inline LmP stream_lmp(const BeamState& S, int B, int V, int blank, int W,
                       const asr_att_beam_lm_t* lm, double beta) {
   LmP p = {};
+  static_cast<Beam&>(p) = S;
   p.B = B; p.V = V; p.blank = blank; p.W = W; p.poolT = S.max_frames;
   p.alpha = lm ? (float)lm->weight : 0.f;
   p.beta = (float)beta;
   p.has_lm = lm ? 1 : 0;
   if (lm) p.net = lm_net_from(lm);
-  p.n = S.n; p.nnodes = S.nnodes;
-  p.node = S.node; p.par = S.par; p.last = S.last; p.depth = S.depth; p.slot = S.slot;
-  p.src = S.src; p.tok = S.tok;
-  p.pb = S.pb; p.pnb = S.pnb; p.hash = S.hash; p.phash = S.phash;
-  p.pools = S.pools;
-  p.h = S.h; p.c = S.c; p.q = S.q;
   return p;
 }
 
@@ -1095,14 +1105,8 @@ __global__ void __launch_bounds__(64) beam_stream_reset_kernel(BeamState S, int 
     S.src[r + lane] = -1;
   }
   if (sel && lane == 0) {
-    Node* pool = S.pools + (long long)b * ((long long)S.max_frames * W + 1);
-    pool[0].parent = 0;
-    pool[0].label = -1;
     S.frames[b] = 0; S.status[b] = 0;
-    S.n[b] = 1; S.nnodes[b] = 1;
-    S.node[r] = 0; S.par[r] = 0; S.last[r] = -1; S.depth[r] = 0; S.slot[r] = 0;
-    S.pb[r] = 0.f; S.pnb[r] = neg_inf();
-    S.hash[r] = 0; S.phash[r] = 0;
+    beam_root(S, b, W, S.max_frames);
   }
 }
 
@@ -1256,28 +1260,35 @@ extern "C" size_t asr_ctc_beam_stream_ws_bytes(int Tc, int B, int V, int beam_wi
   return stream_ws(Tc, B, V, beam_width).total;
 }
 
-// What every session call asks of the session's shape, its LM and its state;
-// on ASR_OK *lm is null where the LM term is absent and S is the state's view.
+// What every session call asks of max_frames and of the state buffer of a
+// session with (layers, H) of LM state per slot; on ASR_OK S is the state's view.
+static int stream_state_check(const char* who, int max_frames, int B, int V, int beam_width,
+                              int layers, int H, const void* state, size_t state_bytes,
+                              BeamState* S) {
+  ASR_REQUIRE(stream_args_ok(max_frames, B, V, beam_width), ASR_ERR_ARG,
+              "%s: max_frames = %d outside [1, %d]", who, max_frames, (INT_MAX - 1) / kMaxBeam);
+  const StreamLayout w = stream_layout(max_frames, B, V, beam_width, layers, H);
+  ASR_REQUIRE(state_bytes >= w.total, ASR_ERR_WORKSPACE, "%s: state %zu < %zu bytes", who,
+              state_bytes, w.total);
+  ASR_REQUIRE(((uintptr_t)state & 15) == 0, ASR_ERR_ARG, "%s: state not 16-B aligned", who);
+  char* base = (char*)state;
+  S->frames = (int32_t*)(base + w.frames);
+  S->status = (int32_t*)(base + w.status);
+  S->max_frames = max_frames;
+  beam_bind(*S, base, w.beam);
+  return ASR_OK;
+}
+
+// What reset and feed ask of the session's shape, its LM and its state; on
+// ASR_OK *lm is null where the LM term is absent and S is the state's view.
 static int stream_check(const char* who, bool pointers, int max_frames, int B, int V, int blank,
                         int beam_width, const asr_att_beam_lm_t** lm, const void* state,
                         size_t state_bytes, BeamState* S) {
   int rc = beam_args_check(who, pointers && state, 1, B, V, blank, beam_width);
   if (rc != ASR_OK) return rc;
-  ASR_REQUIRE(stream_args_ok(max_frames, B, V, beam_width), ASR_ERR_ARG,
-              "%s: max_frames = %d outside [1, %d]", who, max_frames, (INT_MAX - 1) / kMaxBeam);
-  if (*lm) {
-    ASR_REQUIRE((*lm)->weight >= 0.0 && (*lm)->weight <= 3.0e38, ASR_ERR_ARG,
-                "%s: weight = %g is negative or not finite", who, (*lm)->weight);
-    if ((rc = lm_net_check(*lm, V, kStreamLmWho)) != ASR_OK) return rc;
-    if ((*lm)->weight == 0.0) *lm = nullptr;  // the LM term is absent
-  }
-  const StreamLayout w = stream_layout(max_frames, B, V, beam_width, *lm ? (*lm)->layers : 0,
-                                       *lm ? (*lm)->H : 0);
-  ASR_REQUIRE(state_bytes >= w.total, ASR_ERR_WORKSPACE, "%s: state %zu < %zu bytes", who,
-              state_bytes, w.total);
-  ASR_REQUIRE(((uintptr_t)state & 15) == 0, ASR_ERR_ARG, "%s: state not 16-B aligned", who);
-  *S = stream_state((void*)state, w, max_frames);
-  return ASR_OK;
+  if ((rc = lm_args_check(who, lm, V, kStreamLmWho)) != ASR_OK) return rc;
+  return stream_state_check(who, max_frames, B, V, beam_width, *lm ? (*lm)->layers : 0,
+                            *lm ? (*lm)->H : 0, state, state_bytes, S);
 }
 
 extern "C" int asr_ctc_beam_stream_reset(void* state, size_t state_bytes, int max_frames, int B,
@@ -1290,13 +1301,7 @@ extern "C" int asr_ctc_beam_stream_reset(void* state, size_t state_bytes, int ma
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B), dim3(64), 0, s, S, beam_width, V, rows);
   ASR_LAUNCH_CHECK();
-  if (lm) {
-    const LmP p = stream_lmp(S, B, V, 0, beam_width, lm, 0.0);
-    hipLaunchKernelGGL(lm_step_kernel, dim3(1, B), dim3(LM_THREADS),
-                       lm_cell_lds_floats(lm->Y, lm->H) * 4, s, -1, p);
-    ASR_LAUNCH_CHECK();
-  }
-  return ASR_OK;
+  return lm ? lm_launch_root(stream_lmp(S, B, V, 0, beam_width, lm, 0.0), lm, s) : ASR_OK;
 }
 
 extern "C" int asr_ctc_beam_stream_feed(const float* logits, long long stride_t, long long stride_b,
@@ -1347,18 +1352,7 @@ extern "C" int asr_ctc_beam_stream_feed(const float* logits, long long stride_t,
     launch_rows(logits, stride_t, stride_b, Tc, B, V, eff, blank, 0, normalize, lse, nullptr,
                 nullptr, s);
     ASR_LAUNCH_CHECK();
-    const size_t lds_step = lm ? lm_cell_lds_floats(lm->Y, lm->H) * 4 : 0;
-    const long long entries = (long long)B * W;
-    for (int t = 0; t < Tc; ++t) {
-      if (V <= kWaveModeMaxV)
-        hipLaunchKernelGGL(lm_topk_kernel<1>, dim3((unsigned)((entries + 3) / 4)), dim3(256), 0, s,
-                           t, p);
-      else
-        hipLaunchKernelGGL(lm_topk_kernel<4>, dim3((unsigned)entries), dim3(256), 0, s, t, p);
-      hipLaunchKernelGGL(lm_select_kernel, dim3(B), dim3(64), 0, s, t, p);
-      if (lm) hipLaunchKernelGGL(lm_step_kernel, dim3(W, B), dim3(LM_THREADS), lds_step, s, t, p);
-      ASR_LAUNCH_CHECK();
-    }
+    if ((rc = lm_launch_frames(p, Tc, lm, s)) != ASR_OK) return rc;
   }
   hipLaunchKernelGGL(beam_stream_out_kernel, dim3(B), dim3(64), 0, s, S, W, V, lm ? 1 : 0,
                      lm ? (float)lm->weight : 0.f, final, hyps, ld_hyp, hyp_lens, scores,
@@ -1372,19 +1366,15 @@ extern "C" int asr_ctc_beam_stream_nbest(const void* state, size_t state_bytes, 
                                          int32_t* hyps, int ld_hyp, int32_t* lens, float* scores,
                                          int32_t* counts, void* stream) {
   const char* who = "ctc_beam_stream_nbest";
-  const int rc = beam_args_check(who, state && hyps && lens && scores && counts, 1, B, V, 0,
-                                 beam_width);
+  int rc = beam_args_check(who, state && hyps && lens && scores && counts, 1, B, V, 0, beam_width);
   if (rc != ASR_OK) return rc;
-  ASR_REQUIRE(stream_args_ok(max_frames, B, V, beam_width), ASR_ERR_ARG,
-              "%s: max_frames = %d outside [1, %d]", who, max_frames, (INT_MAX - 1) / kMaxBeam);
   ASR_REQUIRE(lm_layers >= 0 && lm_H >= 0, ASR_ERR_ARG, "%s: bad LM dims", who);
   ASR_REQUIRE(ld_hyp >= max_frames, ASR_ERR_ARG, "%s: ld_hyp = %d < max_frames = %d", who, ld_hyp,
               max_frames);
-  const StreamLayout w = stream_layout(max_frames, B, V, beam_width, lm_layers, lm_H);
-  ASR_REQUIRE(state_bytes >= w.total, ASR_ERR_WORKSPACE, "%s: state %zu < %zu bytes", who,
-              state_bytes, w.total);
-  ASR_REQUIRE(((uintptr_t)state & 15) == 0, ASR_ERR_ARG, "%s: state not 16-B aligned", who);
-  const BeamState S = stream_state((void*)state, w, max_frames);
+  BeamState S;
+  if ((rc = stream_state_check(who, max_frames, B, V, beam_width, lm_layers, lm_H, state,
+                               state_bytes, &S)) != ASR_OK)
+    return rc;
   hipLaunchKernelGGL(beam_stream_nbest_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, S,
                      beam_width, hyps, ld_hyp, lens, scores, counts);
   ASR_LAUNCH_CHECK();
@@ -1393,8 +1383,8 @@ extern "C" int asr_ctc_beam_stream_nbest(const void* state, size_t state_bytes, 
 
 extern "C" int asr_ctc_beam_stream_status(const void* state, int B, int32_t* status, void* stream) {
   ASR_REQUIRE(state && status && B > 0, ASR_ERR_ARG, "ctc_beam_stream_status: bad argument");
-  // the status words follow the frame counts: stream_layout's first two arrays
-  const char* at = (const char*)state + align16((size_t)B * sizeof(int32_t));
+  // (frames and status lead the state: their offsets depend on B alone)
+  const char* at = (const char*)state + stream_layout(1, B, 2, 1, 0, 0).status;
   ASR_CHECK_HIP(hipMemcpyAsync(status, at, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                (hipStream_t)stream));
   return ASR_OK;

@@ -26,50 +26,20 @@
 //
 // Work-group (256 threads): 4 hidden units x 4 gates = 16 gate columns x 32
 // utterances, the 4 waves split K = H and combine through LDS (8 KB), then 128
-// threads do the (scalar) cell math.  grid = (ceil(H/4), ceil(B/32)).
-#include "mfma.h"
+// threads do the (scalar) cell math.  grid = (ceil(H/4), ceil(B/32)).  The
+// product, the combine and the gate pre-activations are not a copy of
+// lstm_uni.hip's: both steps call lstm_uni_step.h's uni_gate_partials and
+// uni_gate_pre, so the two cannot drift apart.  This kernel's own: where
+// h_{t-1} is read from, the cell update, the frozen state and the stores.
+#include "lstm_uni_step.h"
 
 extern "C" int asr_lstm_uni_shape_ok(int B, int T, int H);
 
 namespace asr {
 namespace {
 
-constexpr int SFU = 4;     // units per work-group (16 gate columns)
-constexpr int SFB = 32;    // utterances per work-group
-
-__device__ __forceinline__ float sldw(const float* p, long long i) { return p[i]; }
-__device__ __forceinline__ float sldw(const uint16_t* p, long long i) { return bf2f(p[i]); }
-
-// 8 consecutive elements [k, k + 8) of a row as a bf16 fragment, zeros from K
-// on and for a nullptr row.  vec (H % 8 == 0 and 16-B aligned rows: a fragment
-// is whole or empty): vector loads.
-__device__ __forceinline__ bf16x8 sfrag8_tail(const float* row, int k, int K) {
-  u16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (k + j < K) ? f2bf(row[k + j]) : (uint16_t)0;
-  return as_bf16x8(r);
-}
-__device__ __forceinline__ bf16x8 sfrag8_tail(const uint16_t* row, int k, int K) {
-  u16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (k + j < K) ? row[k + j] : (uint16_t)0;
-  return as_bf16x8(r);
-}
-__device__ __forceinline__ bf16x8 sfrag8(const float* row, int k, int K, bool vec) {
-  if (row == nullptr || k >= K) return as_bf16x8(u16x8{0, 0, 0, 0, 0, 0, 0, 0});
-  return vec ? load_bf16x8_from_f32(row + k) : sfrag8_tail(row, k, K);
-}
-__device__ __forceinline__ bf16x8 sfrag8(const uint16_t* row, int k, int K, bool vec) {
-  if (row == nullptr || k >= K) return as_bf16x8(u16x8{0, 0, 0, 0, 0, 0, 0, 0});
-  return vec ? load_bf16x8(row + k) : sfrag8_tail(row, k, K);
-}
-template <typename T>
-__device__ __forceinline__ float sfrag1(const T* row, int k, int K) {
-  return (row != nullptr && k < K) ? sldw(row, k) : 0.f;
-}
-
 // ---------------------------------------------------------------------------
-// step t of a chunk of Tc frames.  grid = (ceil(H / SFU), ceil(B / SFB)),
+// step t of a chunk of Tc frames.  grid = (ceil(H / UFU), ceil(B / UFB)),
 // block = 256.  c_in / c_out may be one buffer (see the head of the file), so
 // neither is __restrict__.
 // ---------------------------------------------------------------------------
@@ -78,49 +48,23 @@ __global__ void __launch_bounds__(256) lstm_stream_step(
     int t, int B, int Tc, int H, const int32_t* __restrict__ lens, const TW* __restrict__ whh,
     const float* __restrict__ gx, float* __restrict__ y, const float* __restrict__ h_in,
     const float* c_in, float* __restrict__ h_out, float* c_out) {
-  __shared__ float part[4][SFB][16];
-  const int u0 = blockIdx.x * SFU;
-  const int b0 = blockIdx.y * SFB;
+  __shared__ float part[4][UFB][16];
+  const int u0 = blockIdx.x * UFU;
+  const int b0 = blockIdx.y * UFB;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool vec = (H & 7) == 0;
-
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  {
-    // A rows: h_{t-1} of utterances b0 + (l & 15) and b0 + 16 + (l & 15);
-    // B rows: W_hh row g*H + u of gate column n = l & 15 (g = n >> 2, u = u0 + (n & 3))
-    const int ra = b0 + (lane & 15), rb = ra + 16;
-    const float* hp = t > 0 ? y + (long long)(t - 1) * H : h_in;
-    const long long hs = t > 0 ? (long long)Tc * H : (long long)H;
-    const float* a0 = ra < B ? hp + ra * hs : nullptr;
-    const float* a1 = rb < B ? hp + rb * hs : nullptr;
-    const int n = lane & 15, u = u0 + (n & 3);
-    const TW* br = u < H ? whh + ((long long)(n >> 2) * H + u) * H : nullptr;
-    if constexpr (BF16) {
-      for (int k0 = wave * 32; k0 < H; k0 += 4 * 32) {
-        const int k = k0 + 8 * (lane >> 4);
-        const bf16x8 b = sfrag8(br, k, H, vec);
-        acc0 = mfma_bf16(sfrag8(a0, k, H, vec), b, acc0);
-        acc1 = mfma_bf16(sfrag8(a1, k, H, vec), b, acc1);
-      }
-    } else {
-      for (int k0 = wave * 4; k0 < H; k0 += 4 * 4) {
-        const int k = k0 + (lane >> 4);
-        const float b = sfrag1(br, k, H);
-        acc0 = mfma_f32(sfrag1(a0, k, H), b, acc0);
-        acc1 = mfma_f32(sfrag1(a1, k, H), b, acc1);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    part[wave][4 * (lane >> 4) + r][lane & 15] = acc0[r];
-    part[wave][16 + 4 * (lane >> 4) + r][lane & 15] = acc1[r];
-  }
-  __syncthreads();
-  if (tid >= SFB * SFU) return;
-  const int row = tid >> 2, uu = tid & 3;
-  const int b = b0 + row, j = u0 + uu;
+  // A rows: h_{t-1} of utterances b0 + (l & 15) and b0 + 16 + (l & 15), from
+  // h_in at t = 0 and from y[.][t-1] after; B rows: W_hh row g*H + u of gate
+  // column n = l & 15 (g = n >> 2, u = u0 + (n & 3))
+  const int ra = b0 + (lane & 15), rb = ra + 16;
+  const float* hp = t > 0 ? y + (long long)(t - 1) * H : h_in;
+  const long long hs = t > 0 ? (long long)Tc * H : (long long)H;
+  const float* a0 = ra < B ? hp + ra * hs : nullptr;
+  const float* a1 = rb < B ? hp + rb * hs : nullptr;
+  const int n = lane & 15, u = u0 + (n & 3);
+  const TW* br = u < H ? whh + ((long long)(n >> 2) * H + u) * H : nullptr;
+  uni_gate_partials<BF16>(a0, a1, br, false, H, part);
+  if (tid >= UFB * UFU) return;
+  const int b = b0 + (tid >> 2), j = u0 + (tid & 3);
   if (b >= B || j >= H) return;
   const int lb = min(max(lens[b], 0), Tc);
   const long long yidx = ((long long)b * Tc + t) * H + j;
@@ -134,13 +78,8 @@ __global__ void __launch_bounds__(256) lstm_stream_step(
     }
     return;
   }
-  const long long gbase = ((long long)b * Tc + t) * 4 * H + j;
   float pre[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    pre[q] = ((part[0][row][q * 4 + uu] + part[1][row][q * 4 + uu]) +
-              (part[2][row][q * 4 + uu] + part[3][row][q * 4 + uu])) +
-             gx[gbase + (long long)q * H];
+  uni_gate_pre(part, gx + ((long long)b * Tc + t) * 4 * H + j, H, pre);
   const float cprev = t > 0 ? c_out[sidx] : c_in[sidx];
   const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]);
   const float gg = tanhf_(pre[2]), og = sigmoidf_(pre[3]);
@@ -149,12 +88,6 @@ __global__ void __launch_bounds__(256) lstm_stream_step(
   y[yidx] = h;
   c_out[sidx] = c;
   if (t == lb - 1) h_out[sidx] = h;
-}
-
-__global__ void __launch_bounds__(256) stream_to_bf16(const float* __restrict__ x,
-                                                      uint16_t* __restrict__ o, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = f2bf(x[i]);
 }
 
 size_t stream_ws(int H, int cdt) {
@@ -231,12 +164,12 @@ extern "C" int asr_lstm_stream_forward(const float* gx, const void* whh, int w_d
   if (convert) {
     // a caller that streams many chunks passes a bf16 W_hh instead (w_dtype)
     const long long n = 4LL * H * H;
-    hipLaunchKernelGGL(stream_to_bf16, dim3(ceil_div(n, 256)), dim3(256), 0, s, (const float*)whh,
+    hipLaunchKernelGGL(uni_to_bf16, dim3(ceil_div(n, 256)), dim3(256), 0, s, (const float*)whh,
                        (uint16_t*)workspace, n);
     ASR_LAUNCH_CHECK();
     wbf = (const uint16_t*)workspace;
   }
-  const dim3 grid(ceil_div(H, SFU), ceil_div(B, SFB));
+  const dim3 grid(ceil_div(H, UFU), ceil_div(B, UFB));
   for (int t = 0; t < Tc; ++t) {
     // (not recorded by the launch profiler: its per-step slot is the training
     // forward's, and a process may train and stream)

@@ -19,11 +19,14 @@
 // Forward work-group (256 threads): 4 hidden units x 4 gates = 16 gate columns
 // x 32 utterances; its 4 waves split K = H and combine through LDS (8 KB), so
 // the 16x16 MFMA tile holds all four gates of its units and the cell update
-// runs in the same kernel.  grid = (ceil(H/4), ceil(B/32)).
+// runs in the same kernel.  grid = (ceil(H/4), ceil(B/32)).  The product, the
+// combine and the gate pre-activations are lstm_uni_step.h's uni_gate_partials
+// and uni_gate_pre, which lstm_stream.hip's step calls too; the fragment
+// loaders are there as well.
 // Backward work-group (512 threads): 16 units x 16 utterances, its 8 waves
 // split K = 4H over dG_{t+1} times a transposed copy of W_hh (each lane's
 // 8-element fragment contiguous), LDS 8 KB.  grid = (ceil(H/16), ceil(B/16)).
-#include "mfma.h"
+#include "lstm_uni_step.h"
 #include "prof.h"
 
 extern "C" size_t asr_colsum_workspace_bytes(int M, int N);
@@ -34,44 +37,11 @@ extern "C" int asr_colsum_accumulate(const float* g, long long ld, int M, int N,
 namespace asr {
 namespace {
 
-constexpr int UFU = 4;     // forward: units per work-group (16 gate columns)
-constexpr int UFB = 32;    // forward: utterances per work-group
 constexpr int UBU = 16;    // backward: units per work-group
 constexpr int UBB = 16;    // backward: utterances per work-group
 constexpr int UNI_MAX_H = 1024;
 constexpr int UNI_MAX_B = 8192;
 constexpr int UNI_MAX_T = 65536;
-
-__device__ __forceinline__ float ldw(const float* p, long long i) { return p[i]; }
-__device__ __forceinline__ float ldw(const uint16_t* p, long long i) { return bf2f(p[i]); }
-
-// 8 consecutive elements [k, k + 8) of a row as a bf16 fragment, zeros from K
-// on and for a nullptr row.  vec (H % 8 == 0: rows 16-B aligned, K a multiple
-// of 8, so a fragment is whole or empty): vector loads.
-__device__ __forceinline__ bf16x8 ufrag8_tail(const float* row, int k, int K) {
-  u16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (k + j < K) ? f2bf(row[k + j]) : (uint16_t)0;
-  return as_bf16x8(r);
-}
-__device__ __forceinline__ bf16x8 ufrag8_tail(const uint16_t* row, int k, int K) {
-  u16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (k + j < K) ? row[k + j] : (uint16_t)0;
-  return as_bf16x8(r);
-}
-__device__ __forceinline__ bf16x8 ufrag8(const float* row, int k, int K, bool vec) {
-  if (row == nullptr || k >= K) return as_bf16x8(u16x8{0, 0, 0, 0, 0, 0, 0, 0});
-  return vec ? load_bf16x8_from_f32(row + k) : ufrag8_tail(row, k, K);
-}
-__device__ __forceinline__ bf16x8 ufrag8(const uint16_t* row, int k, int K, bool vec) {
-  if (row == nullptr || k >= K) return as_bf16x8(u16x8{0, 0, 0, 0, 0, 0, 0, 0});
-  return vec ? load_bf16x8(row + k) : ufrag8_tail(row, k, K);
-}
-template <typename T>
-__device__ __forceinline__ float ufrag1(const T* row, int k, int K) {
-  return (row != nullptr && k < K) ? ldw(row, k) : 0.f;
-}
 
 // ---------------------------------------------------------------------------
 // forward step t.  grid = (ceil(H / UFU), ceil(B / UFB)), block = 256
@@ -85,53 +55,24 @@ __global__ void __launch_bounds__(256) lstm_uni_fwd_step(
   const int u0 = blockIdx.x * UFU;
   const int b0 = blockIdx.y * UFB;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool vec = (H & 7) == 0;
-
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  if (t > 0) {
-    // A rows: h_{t-1} of utterances b0 + (l & 15) and b0 + 16 + (l & 15);
-    // B rows: W_hh row g*H + u of gate column n = l & 15 (g = n >> 2, u = u0 + (n & 3))
-    const int ra = b0 + (lane & 15), rb = ra + 16;
-    const float* a0 = ra < B ? y + ((long long)ra * T + (t - 1)) * H : nullptr;
-    const float* a1 = rb < B ? y + ((long long)rb * T + (t - 1)) * H : nullptr;
-    const int n = lane & 15, u = u0 + (n & 3);
-    const TW* br = u < H ? whh + ((long long)(n >> 2) * H + u) * H : nullptr;
-    if constexpr (BF16) {
-      for (int k0 = wave * 32; k0 < H; k0 += 4 * 32) {
-        const int k = k0 + 8 * (lane >> 4);
-        const bf16x8 b = ufrag8(br, k, H, vec);
-        acc0 = mfma_bf16(ufrag8(a0, k, H, vec), b, acc0);
-        acc1 = mfma_bf16(ufrag8(a1, k, H, vec), b, acc1);
-      }
-    } else {
-      for (int k0 = wave * 4; k0 < H; k0 += 4 * 4) {
-        const int k = k0 + (lane >> 4);
-        const float b = ufrag1(br, k, H);
-        acc0 = mfma_f32(ufrag1(a0, k, H), b, acc0);
-        acc1 = mfma_f32(ufrag1(a1, k, H), b, acc1);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    part[wave][4 * (lane >> 4) + r][lane & 15] = acc0[r];
-    part[wave][16 + 4 * (lane >> 4) + r][lane & 15] = acc1[r];
-  }
-  __syncthreads();
+  // A rows: h_{t-1} = y[.][t-1] of utterances b0 + (l & 15) and b0 + 16 +
+  // (l & 15) (t = 0 has none: the product is skipped, the rows are not read);
+  // B rows: W_hh row g*H + u of gate column n = l & 15 (g = n >> 2, u = u0 +
+  // (n & 3))
+  const int ra = b0 + (lane & 15), rb = ra + 16, tp = max(t - 1, 0);
+  const float* a0 = ra < B ? y + ((long long)ra * T + tp) * H : nullptr;
+  const float* a1 = rb < B ? y + ((long long)rb * T + tp) * H : nullptr;
+  const int n = lane & 15, u = u0 + (n & 3);
+  const TW* br = u < H ? whh + ((long long)(n >> 2) * H + u) * H : nullptr;
+  uni_gate_partials<BF16>(a0, a1, br, t == 0, H, part);
   if (tid >= UFB * UFU) return;
-  const int row = tid >> 2, uu = tid & 3;
-  const int b = b0 + row, j = u0 + uu;
+  const int b = b0 + (tid >> 2), j = u0 + (tid & 3);
   if (b >= B || j >= H) return;
   const bool active = t < lens[b];
   const long long gbase = ((long long)b * T + t) * 4 * H + j;
   const long long sidx = ((long long)b * T + t) * H + j;
   float pre[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    pre[q] = ((part[0][row][q * 4 + uu] + part[1][row][q * 4 + uu]) +
-              (part[2][row][q * 4 + uu] + part[3][row][q * 4 + uu])) +
-             gx_act[gbase + (long long)q * H];
+  uni_gate_pre(part, gx_act + gbase, H, pre);
   const float cprev = t > 0 ? cst[sidx - H] : 0.f;
   const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]);
   const float gg = tanhf_(pre[2]), og = sigmoidf_(pre[3]);
@@ -240,12 +181,6 @@ __global__ void __launch_bounds__(256) uni_transpose_whh(const TW* __restrict__ 
     const int c = c0 + i, r = r0 + tx;
     if (c < C && r < R) st(out, (long long)c * R + r, tile[tx][i]);
   }
-}
-
-__global__ void __launch_bounds__(256) uni_to_bf16(const float* __restrict__ x,
-                                                   uint16_t* __restrict__ o, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = f2bf(x[i]);
 }
 
 size_t al256(size_t n) { return (n + 255) & ~size_t(255); }

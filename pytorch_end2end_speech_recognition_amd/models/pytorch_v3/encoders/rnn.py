@@ -233,7 +233,7 @@ class RNNEncoder(nn.Module):
         res_outputs = []
         pending = None   # (p, seed): this layer's dropout, fused into the next layer's staging
         self.pending_output_drop = None
-        lens_d, lens_key = None, None
+        lens_c = None
         uni = self.num_directions == 1
         if self.rnn_type != 'gru' and not uni:
             # one fill for the recurrence workspaces of every layer's forward and
@@ -241,11 +241,8 @@ class RNNEncoder(nn.Module):
             ops.rec_arena_begin(dev, int(h.shape[0]), self.num_units, 2 * self.num_layers)
         for l in range(self.num_layers):
             (w_ih, w_hh, b_ih, b_hh), gbufs = self._layer_tensors(l)
-            # one H2D copy per distinct length vector (they change only where a
-            # layer subsamples), not one per layer on the compute stream
-            if lens_key is None or not np.array_equal(lens_key, lens):
-                lens_key = lens.copy()
-                lens_d = ops.h2d(lens.astype(np.int32), dev)
+            lens_c = self._lens_h2d(lens, lens_c, dev)
+            lens_d = lens_c[1]
             graph = tuple(p for pair in self._layer_params(l) for p in pair)
             if uni:
                 # the unidirectional op (csrc/lstm_uni.hip): dropout between
@@ -259,14 +256,16 @@ class RNNEncoder(nn.Module):
                 h = ops.bgru_layer(h, lens_d, T, w_ih, w_hh, b_ih, b_hh, perm=pm, t_mul=t_mul,
                                    t_add=t_add, gbufs=tuple(gbufs), graph_params=graph,
                                    concat=concat)
-            # this layer's output feeds only the next BLSTM layer, through an
-            # identity row map: bf16 mode hands it over as that layer's staged
-            # bf16 input (dropout applied) instead of an f32 tensor
+            # this layer's output feeds only the next recurrent layer's input
+            # rows: no sub-task tap, residual sum or projection reads it
+            feeds_next_only = (l < self.num_layers - 1 and
+                               not (self.num_layers_sub >= 1 and l == self.num_layers_sub - 1) and
+                               not (self.residual or self.dense_residual or self.num_proj > 0))
+            # ... the next BLSTM layer, through an identity row map: bf16 mode
+            # hands it over as that layer's staged bf16 input (dropout applied)
+            # instead of an f32 tensor
             handoff = (self.rnn_type != 'gru' and not uni and ops.fuse_dropout_ok() and
-                       l < self.num_layers - 1 and
-                       not (self.num_layers_sub >= 1 and l == self.num_layers_sub - 1) and
-                       not (self.residual or self.dense_residual or self.num_proj > 0) and
-                       not self.subsample_list[l])
+                       feeds_next_only and not self.subsample_list[l])
             drop_out = self.training and self.dropout_hidden_p > 0
             # same seed stream either way (one seed per layer, drawn in order)
             seed = ops.next_seed() if drop_out and handoff else None
@@ -280,12 +279,11 @@ class RNNEncoder(nn.Module):
             pending = None
             if drop_out:
                 # fused when the next consumer is the next layer's input staging
-                # and nothing else reads the dropped h
+                # and nothing else reads the dropped h ('drop' subsampling's row
+                # map is allowed here, unlike for the hand-off)
                 if seed is None:
                     seed = ops.next_seed()
-                if (not uni and ops.fuse_dropout_ok() and l < self.num_layers - 1 and
-                        not (self.num_layers_sub >= 1 and l == self.num_layers_sub - 1) and
-                        not (self.residual or self.dense_residual or self.num_proj > 0) and
+                if (not uni and ops.fuse_dropout_ok() and feeds_next_only and
                         not (self.subsample_list[l] and self.subsample_type != 'drop')):
                     pending = (self.dropout_hidden_p, seed)
                 elif (l == self.num_layers - 1 and self.defer_output_dropout and
@@ -297,25 +295,11 @@ class RNNEncoder(nn.Module):
                     h = ops.dropout(h, self.dropout_hidden_p, seed=seed)
             if self.num_layers_sub >= 1 and l == self.num_layers_sub - 1:   # rnn.py:400-407
                 h_sub, lens_sub = h, lens.astype(np.int32)
-            pm, t_mul, t_add, concat = None, 1, 0, False
-            if l == self.num_layers - 1 or not (self.residual or self.dense_residual or
-                                                self.num_proj > 0 or self.subsample_list[l]):
-                continue
-            if self.num_proj > 0:                                    # rnn.py:409-411
-                h = ops.tanh(getattr(self, 'proj_l%d' % l)(h))
-            if self.subsample_list[l]:                               # rnn.py:413-439
-                # fused into the next layer's input GEMM: 'drop' reads frame 2t+1,
-                # 'concat' reads frames 2t and 2t+1 as one row of twice the width
+            pm = None
+            h, res_outputs, (t_mul, t_add, concat) = self._between_layers(l, h, res_outputs)
+            if t_mul == 2:         # every row gets the padded length (rnn.py:435-439)
                 T = T // 2
-                if self.subsample_type == 'drop':
-                    t_mul, t_add = 2, 1
-                else:
-                    t_mul, t_add, concat = 2, 0, True
                 lens = np.full_like(lens, T)
-            elif (self.residual or self.dense_residual) and l >= self.residual_start_layer - 1:
-                for lower in res_outputs:                            # rnn.py:454-462
-                    h = ops.add(h, lower)
-                res_outputs = [h] if self.residual else res_outputs + [h]
         assert t_mul == 1
         self.last_lens_np = lens.astype(np.int32)
         self.last_perm_np = perm.astype(np.int64)
@@ -326,6 +310,38 @@ class RNNEncoder(nn.Module):
             lens_sub_d = ops.h2d(lens_sub, dev)
             return h, out_lens, h_sub, lens_sub_d, perm_idx
         return h, out_lens, perm_idx
+
+    @staticmethod
+    def _lens_h2d(lens, cached, dev):
+        """(lens, its int32 device copy): `cached` while the vector is the one
+        it holds, so there is one H2D copy per distinct length vector (they
+        change only where a layer subsamples), not one per layer on the
+        compute stream."""
+        if cached is None or not np.array_equal(cached[0], lens):
+            cached = (lens.copy(), ops.h2d(lens.astype(np.int32), dev))
+        return cached
+
+    def _between_layers(self, l, h, res_outputs):
+        """What lies between layer l's output h and the next layer's input:
+        projection + tanh (rnn.py:409-411), then either subsampling (rnn.py:413-
+        439) or the residual / dense-residual sums (rnn.py:454-462).  Returns (h,
+        res_outputs, (t_mul, t_add, concat)): the row map by which the next
+        layer's input GEMM reads h in place -- 'drop' reads frame 2t+1, 'concat'
+        frames 2t and 2t+1 as one row of twice the width; t_mul == 2 tells the
+        caller to halve its lengths, by its own rule."""
+        rows = (1, 0, False)
+        if l == self.num_layers - 1 or not (self.residual or self.dense_residual or
+                                            self.num_proj > 0 or self.subsample_list[l]):
+            return h, res_outputs, rows
+        if self.num_proj > 0:
+            h = ops.tanh(getattr(self, 'proj_l%d' % l)(h))
+        if self.subsample_list[l]:
+            rows = (2, 1, False) if self.subsample_type == 'drop' else (2, 0, True)
+        elif (self.residual or self.dense_residual) and l >= self.residual_start_layer - 1:
+            for lower in res_outputs:
+                h = ops.add(h, lower)
+            res_outputs = [h] if self.residual else res_outputs + [h]
+        return h, res_outputs, rows
 
     # ------------------------------------------------------------- streaming
     @property
@@ -409,38 +425,22 @@ class RNNEncoder(nn.Module):
         h = xs[:, :T].contiguous()
         t_mul, t_add, concat = 1, 0, False
         res_outputs = []
-        lens_d = lens_key = None
+        lens_c = None
         for l in range(self.num_layers):
             (w_ih, w_hh, b_ih, b_hh), _ = self._layer_tensors(l)
-            if lens_key is None or not np.array_equal(lens_key, lens):
-                lens_key = lens.copy()
-                lens_d = ops.h2d(lens.astype(np.int32), dev)
+            lens_c = self._lens_h2d(lens, lens_c, dev)
             whh = state.whh_bf16(l, w_hh, owner._flat_param) if bf16 else w_hh
             h, (state.h[l], state.c[l]) = ops.lstm_stream_layer(
-                h, lens_d, T, w_ih, whh, b_ih, b_hh, (state.h[l], state.c[l]), t_mul=t_mul,
+                h, lens_c[1], T, w_ih, whh, b_ih, b_hh, (state.h[l], state.c[l]), t_mul=t_mul,
                 t_add=t_add, concat=concat)
-            t_mul, t_add, concat = 1, 0, False
-            if l == self.num_layers - 1 or not (self.residual or self.dense_residual or
-                                                self.num_proj > 0 or self.subsample_list[l]):
-                continue
-            if self.num_proj > 0:
-                h = ops.tanh(getattr(self, 'proj_l%d' % l)(h))
-            if self.subsample_list[l]:
-                # as forward(): read in place by the next layer's input GEMM
+            h, res_outputs, (t_mul, t_add, concat) = self._between_layers(l, h, res_outputs)
+            if t_mul == 2:         # lengths halve per row
                 T, lens = T // 2, lens // 2
                 if T == 0:
                     # a final chunk shorter than the stride: one padded frame,
                     # read from a source wide enough for the row map
                     T = 1
                     h = torch.cat([h, torch.zeros_like(h)], dim=1)
-                if self.subsample_type == 'drop':
-                    t_mul, t_add = 2, 1
-                else:
-                    t_mul, t_add, concat = 2, 0, True
-            elif (self.residual or self.dense_residual) and l >= self.residual_start_layer - 1:
-                for lower in res_outputs:
-                    h = ops.add(h, lower)
-                res_outputs = [h] if self.residual else res_outputs + [h]
         state.final = state.final | final
         state.last_lens_np = lens.astype(np.int32)
         return h, ops.h2d(state.last_lens_np, dev)

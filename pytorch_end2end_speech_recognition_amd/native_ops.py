@@ -39,6 +39,15 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
+def _grown_ws(cache, nbytes, device):
+    """cache's (device -> tensor) workspace of at least nbytes: kept from the
+    largest call so far, replaced only by a larger one."""
+    ws = cache.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = cache[device] = _ws(nbytes, device)
+    return ws
+
+
 def h2d(a, device):
     """Host array -> device tensor without blocking the host: staged through
     pinned memory (torch's caching host allocator keeps the block until the
@@ -1159,9 +1168,7 @@ def att_decode_beam(enc, enc_a, lens, h0, emb_dim, sharpen, sigmoid, w_ih, w_hh,
                  max_len, ctypes.byref(ex))
     if nb == 0:
         return None
-    ws = _att_beam['ws'].get(dev)
-    if ws is None or ws.numel() < nb:
-        ws = _att_beam['ws'][dev] = _ws(nb, dev)
+    ws = _grown_ws(_att_beam['ws'], nb, dev)
     keep = [t.contiguous() for t in (w_ih, w_hh, gen['b_ih'], gen['b_hh'], w_dec, w_conv, conv_w,
                                      v, gen['w_d'], gen['w_c'], gen['w_fc'], gen['emb_w'])]
     kb = [None if gen[k] is None else gen[k].contiguous() for k in ('b_d', 'b_c', 'b_fc')]
@@ -2208,6 +2215,21 @@ def bgru_layer(x_src, lens, T, w_ih, w_hh, b_ih, b_hh, perm=None, t_mul=1, t_add
                              w_ih, w_hh, b_ih, b_hh, *graph_params)
 
 
+def _lstm_uni_gx(x_src, T, perm, t_mul, t_add, concat, w_ih, w_hh, b_ih, b_hh):
+    """A unidirectional LSTM layer's input side, for training and streaming
+    alike: (the row map of its T input frames into x_src [B, T_src, Dsrc], gx
+    [B, T, 4H] = x W_ih^T + b_ih + b_hh from one GEMM)."""
+    B, T_src, Dsrc = x_src.shape
+    Din = 2 * Dsrc if concat else Dsrc
+    assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
+    H = w_hh.shape[1]
+    in_map = _InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Din)
+    gx = torch.empty(B, T, 4 * H, dtype=torch.float32, device=x_src.device)
+    run_gemm([gemm_problem(operand(x_src, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
+                           rowmap(4 * H), B * T, 4 * H, Din, bias=b_ih, bias2=b_hh)], x_src.device)
+    return in_map, gx
+
+
 class LSTMLayerFn(torch.autograd.Function):
     """Unidirectional LSTM layer (nn.LSTM(bidirectional=False), rnn.py:166-172 /
     :218-224) on the per-step recurrence of csrc/lstm_uni.hip.  Same input
@@ -2228,19 +2250,13 @@ class LSTMLayerFn(torch.autograd.Function):
             N.call('asr_dropout', N.ptr(x_src), N.ptr(xd), x_src.numel(), float(drop[0]),
                    int(drop[1]), N.stream_handle(dev))
             x_src = xd
-        B, T_src, Dsrc = x_src.shape
-        Din = 2 * Dsrc if concat else Dsrc
-        assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
-        H = w_hh.shape[1]
+        B, H = x_src.shape[0], w_hh.shape[1]
         cd = compute_dtype()
         nb = int(N.query('asr_lstm_uni_workspace_bytes', B, H, cd, 0))
         ws = _ws(nb, dev)
-        in_map = _InputMap(perm, t_mul, t_add, T, T_src, Dsrc, Din)
-        gx = torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev)
+        in_map, gx = _lstm_uni_gx(x_src, T, perm, t_mul, t_add, concat, w_ih, w_hh, b_ih, b_hh)
         y = torch.empty(B, T, H, dtype=torch.float32, device=dev)
         cst = torch.empty(B, T, H, dtype=torch.float32, device=dev)
-        run_gemm([gemm_problem(operand(x_src, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
-                               rowmap(4 * H), B * T, 4 * H, Din, bias=b_ih, bias2=b_hh)], dev)
         N.call('asr_lstm_uni_forward', N.ptr(gx), N.ptr(w_hh), F32, N.ptr(lens), B, T, H, cd,
                N.ptr(y), N.ptr(cst), None, N.ptr(ws), nb, N.stream_handle(dev))
         ctx.save_for_backward(x_src, w_ih, w_hh, b_ih, b_hh, lens, gx, cst, y)
@@ -2315,11 +2331,7 @@ def lstm_stream_layer(x, lens, Tc, w_ih, w_hh, b_ih, b_hh, state, t_mul=1, t_add
     N.require_device(x, lens, w_ih, w_hh, b_ih, b_hh, h_in, c_in)
     x = x.contiguous()
     dev = x.device
-    B, T_src, Dsrc = x.shape
-    Din = 2 * Dsrc if concat else Dsrc
-    H = w_hh.shape[1]
-    Tc = int(Tc)
-    assert w_ih.shape[1] == Din, (tuple(w_ih.shape), Din)
+    B, H, Tc = x.shape[0], w_hh.shape[1], int(Tc)
     assert tuple(h_in.shape) == tuple(c_in.shape) == (B, H) and lens.dtype == torch.int32
     cd = compute_dtype()
     if N.query('asr_lstm_uni_shape_ok', int(B), Tc, int(H)) != 1:
@@ -2331,12 +2343,9 @@ def lstm_stream_layer(x, lens, Tc, w_ih, w_hh, b_ih, b_hh, state, t_mul=1, t_add
     if cd == BF16 and w_dt == F32:
         nb = int(N.query('asr_lstm_stream_workspace_bytes', B, H, cd))
         ws = _ws(nb, dev)
-    in_map = _InputMap(None, t_mul, t_add, Tc, T_src, Dsrc, Din)
-    gx = torch.empty(B, Tc, 4 * H, dtype=torch.float32, device=dev)
+    _, gx = _lstm_uni_gx(x, Tc, None, t_mul, t_add, concat, w_ih, w_hh, b_ih, b_hh)
     y = torch.empty(B, Tc, H, dtype=torch.float32, device=dev)
     h_out, c_out = torch.empty_like(h_in), torch.empty_like(c_in)
-    run_gemm([gemm_problem(operand(x, 0, in_map.rows()), operand(w_ih, 0, rowmap(Din)), gx,
-                           rowmap(4 * H), B * Tc, 4 * H, Din, bias=b_ih, bias2=b_hh)], dev)
     N.call('asr_lstm_stream_forward', N.ptr(gx), N.ptr(w_hh), w_dt, N.ptr(lens), B, Tc, H, cd,
            N.ptr(h_in), N.ptr(c_in), N.ptr(h_out), N.ptr(c_out),
            N.ptr(y), N.ptr(ws), nb, N.stream_handle(dev))
@@ -3077,6 +3086,18 @@ def last_ctc_beam_path():
     return _ctc_beam['path']
 
 
+def _ctc_lm_args(who, lm, V, beta):
+    """What the CTC searches ask of lm (None: no LM) and beta before any call:
+    (the LM struct, the tensors it points into), or (None, None)."""
+    lms, keep = _lm_struct(lm, who) if lm is not None else (None, None)
+    if lm is not None and (int(lm['emb'].shape[0]) != V or int(lm['w_out'].shape[0]) != V):
+        raise ValueError('%s: the LM has %d classes, the CTC head %d (blank '
+                         'included; <eos> takes its place)' % (who, lm['w_out'].shape[0], V))
+    if not np.isfinite(beta):
+        raise ValueError('%s: beta = %r is not finite' % (who, beta))
+    return lms, keep
+
+
 def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, beta=0.0):
     """CTC prefix beam search on device: logits [B, T, V] raw (normalize=True:
     the log-softmax is fused) or log-probabilities.  Returns (hyps int32 [B, T],
@@ -3094,21 +3115,13 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, 
     B, T, V = logits.shape
     dev = logits.device
     W, beta = int(beam_width), float(beta)
-    lms, keep = _lm_struct(lm, 'ctc_beam_search') if lm is not None else (None, None)
-    if lm is not None and (int(lm['emb'].shape[0]) != V or int(lm['w_out'].shape[0]) != V):
-        raise ValueError('ctc_beam_search: the LM has %d classes, the CTC head %d (blank '
-                         'included; <eos> takes its place)' % (lm['w_out'].shape[0], V))
-    if not np.isfinite(beta):
-        raise ValueError('ctc_beam_search: beta = %r is not finite' % (beta,))
+    lms, keep = _ctc_lm_args('ctc_beam_search', lm, V, beta)
     hyps = torch.empty(B, T, dtype=torch.int32, device=dev)
     hl = torch.empty(B, dtype=torch.int32, device=dev)
     scores = torch.empty(B, dtype=torch.float32, device=dev)
     lens_d = lens.int().contiguous()
     if lm is None and beta == 0:
-        nb = N.query('asr_ctc_beam_ws_bytes', T, B, V, W)
-        ws = _beam_ws.get(dev)
-        if ws is None or ws.numel() < nb:
-            ws = _beam_ws[dev] = _ws(nb, dev)
+        ws = _grown_ws(_beam_ws, N.query('asr_ctc_beam_ws_bytes', T, B, V, W), dev)
         N.call('asr_ctc_beam_search', N.ptr(logits), V, T * V, T, B, V, N.ptr(lens_d), int(blank),
                W, int(bool(normalize)), N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl),
                N.ptr(scores), N.stream_handle(dev))
@@ -3120,9 +3133,7 @@ def ctc_beam_search(logits, lens, beam_width, blank=0, normalize=True, lm=None, 
             return None                  # the LM's shape is outside the kernels' limits
     else:
         nb = N.query('asr_ctc_beam_lm_ws_bytes', T, B, V, W, 0, 0, 0)
-    ws = _beam_ws.get(dev)
-    if ws is None or ws.numel() < nb:
-        ws = _beam_ws[dev] = _ws(nb, dev)
+    ws = _grown_ws(_beam_ws, nb, dev)
     rc = N.lib().asr_ctc_beam_search_lm(
         N.ptr(logits), V, T * V, T, B, V, N.ptr(lens_d), int(blank), W, int(bool(normalize)),
         N.ptr_struct(lms), beta, N.ptr(ws), ws.numel(), N.ptr(hyps), N.ptr(hl), N.ptr(scores),
@@ -3172,13 +3183,8 @@ def ctc_beam_stream_state(batch_size, num_classes, beam_width, max_frames, devic
     st.B, st.V, st.W, st.max_frames = int(batch_size), int(num_classes), int(beam_width), \
         int(max_frames)
     st.blank, st.normalize, st.beta, st.device = int(blank), bool(normalize), float(beta), device
-    st.lms, st.keep = _lm_struct(lm, 'ctc_beam_stream') if lm is not None else (None, None)
-    st.ws = None
-    if lm is not None and (int(lm['emb'].shape[0]) != st.V or int(lm['w_out'].shape[0]) != st.V):
-        raise ValueError('ctc_beam_stream: the LM has %d classes, the CTC head %d (blank '
-                         'included; <eos> takes its place)' % (lm['w_out'].shape[0], st.V))
-    if not np.isfinite(st.beta):
-        raise ValueError('ctc_beam_stream: beta = %r is not finite' % (beta,))
+    st.lms, st.keep = _ctc_lm_args('ctc_beam_stream', lm, st.V, st.beta)
+    st.ws = {}                   # device -> the feeds' workspace
     nb = N.query('asr_ctc_beam_stream_state_bytes', st.max_frames, st.B, st.V, st.W, *st.lm_dims)
     # (a refused shape: the reset below names it)
     st.buf = _ws(max(nb, 16), device)
@@ -3210,9 +3216,7 @@ def ctc_beam_stream_feed(st, logits, lens, final=None, stable=True):
     assert (B, V) == (st.B, st.V), 'the chunk is [%d, ., %d], the session [%d, ., %d]' % (
         B, V, st.B, st.V)
     dev = logits.device
-    nb = N.query('asr_ctc_beam_stream_ws_bytes', T, B, V, st.W)
-    if st.ws is None or st.ws.numel() < nb:
-        st.ws = _ws(nb, dev)
+    ws = _grown_ws(st.ws, N.query('asr_ctc_beam_stream_ws_bytes', T, B, V, st.W), dev)
     hyps = torch.empty(B, st.max_frames, dtype=torch.int32, device=dev)
     hl = torch.empty(B, dtype=torch.int32, device=dev)
     scores = torch.empty(B, dtype=torch.float32, device=dev)
@@ -3221,8 +3225,8 @@ def ctc_beam_stream_feed(st, logits, lens, final=None, stable=True):
         final = final.int().contiguous()
     N.call('asr_ctc_beam_stream_feed', N.ptr(logits), V, T * V, T, B, V,
            N.ptr(lens.int().contiguous()), st.blank, st.W, int(st.normalize), N.ptr_struct(st.lms),
-           st.beta, N.ptr(final), N.ptr(st.buf), st.buf.numel(), st.max_frames, N.ptr(st.ws),
-           st.ws.numel(), N.ptr(hyps), st.max_frames, N.ptr(hl), N.ptr(scores), N.ptr(sl),
+           st.beta, N.ptr(final), N.ptr(st.buf), st.buf.numel(), st.max_frames, N.ptr(ws),
+           ws.numel(), N.ptr(hyps), st.max_frames, N.ptr(hl), N.ptr(scores), N.ptr(sl),
            N.stream_handle(dev))
     _ctc_beam['path'] = 'stream' if st.lm_dims[0] == 0 and st.beta == 0 else 'stream_lm'
     return hyps, hl, scores, sl
@@ -3393,9 +3397,7 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, unit='token', eos=None, space=No
                       0 if token_map is None else token_map.numel(),
                       int(hyp.dtype == torch.int64))
     nb = N.query('asr_edit_distance_ws_bytes', B, max_r, max_h)
-    ws = _edit['ws'].get(dev)
-    if ws is None or ws.numel() < nb:
-        ws = _edit['ws'][dev] = _ws(nb, dev)
+    ws = _grown_ws(_edit['ws'], nb, dev)
     rc = getattr(N.lib(), 'asr_edit_distance')(
         N.ptr(hyp), max(hyp.stride(0), max_h), N.ptr(hl), N.ptr(ref), max(ref.stride(0), max_r),
         N.ptr(rl), B, max_r, max_h, ctypes.byref(opts), N.ptr(out), N.ptr(totals), N.ptr(ws),
@@ -3544,9 +3546,7 @@ def ctc_align(logits, lens, labels_flat, label_lens, max_label_len, blank=0, nor
     if B == 0 or T == 0:
         raise ValueError('ctc_align: empty batch or no frames')
     nb = N.query('asr_ctc_align_ws_bytes', T, B, V, M)
-    ws = _align['ws'].get(dev)
-    if ws is None or ws.numel() < nb:
-        ws = _align['ws'][dev] = _ws(nb, dev)
+    ws = _grown_ws(_align['ws'], nb, dev)
     rc = getattr(N.lib(), 'asr_ctc_align')(
         N.ptr(logits), logits.stride(1), logits.stride(0), T, B, V, N.ptr(labels_flat),
         N.ptr(label_lens), N.ptr(lens), M, int(blank), int(bool(normalize)), N.ptr(ali),

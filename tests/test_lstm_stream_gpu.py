@@ -11,7 +11,8 @@ Every case: on the same gx, each schedule's concatenated y and final (h, c)
 equal the single-chunk call's bit for bit; y is exactly 0 at padded frames;
 and per tensor max |got - f64| / max |f64| <= MARGIN x the recorded constant
 (the f32 one in fp32 mode, the larger of the f32 and the bf16 one in bf16
-mode).  err/bound is printed per tensor.  Also: two identical calls agree bit
+mode).  err/bound is printed per tensor.  Also: from a zero state a single
+chunk gives the bits of asr_lstm_uni_forward, two identical calls agree bit
 for bit, rows with lens == 0 return their state bit-identical, c_out may be
 c_in, a bf16 W_hh gives the bits of the converted f32 one, aliased h_in / h_out
 are ASR_ERR_ARG and H = 1032 is ASR_ERR_UNSUPPORTED with nothing written."""
@@ -81,6 +82,36 @@ def test_chunked_equals_whole_bitwise_and_matches_f64(case, precision, cuda_dev)
         other = _feed(cuda_dev, case, cd, sizes)
         for k, a, b in zip(S.OUT_KEYS, whole, other):
             assert torch.equal(a, b), (name, k, 'differs from the single-chunk call')
+
+
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+@pytest.mark.parametrize('case', ['h20_b3', 'h24_b33'])
+def test_zero_state_single_chunk_equals_the_offline_recurrence_bitwise(case, precision, cuda_dev):
+    """From h = c = 0 and in one chunk, asr_lstm_stream_forward gives the bits
+    asr_lstm_uni_forward writes on a copy of the same gx: y everywhere, and
+    h_out[b] is y[b, lens[b] - 1].  (The offline step skips the recurrent
+    product at t = 0; the stream's product of zeros sums to the same zeros.)"""
+    from pytorch_end2end_speech_recognition_amd import _native as N
+    dev, cd = cuda_dev, CD[precision]
+    inp = S.case_inputs(case)
+    gx, whh, lens = inp['gx'].to(dev), inp['w_hh'].to(dev), inp['totals']
+    B, T, H = gx.shape[0], gx.shape[1], whh.shape[1]
+    zero = torch.zeros(B, H, device=dev)
+    rc, y, h, c = _call(dev, gx.clone(), whh, lens, cd, zero, zero.clone())
+    assert rc == 0
+    act = gx.clone()                           # the offline forward overwrites its gx
+    y_off, cst = torch.empty(B, T, H, device=dev), torch.empty(B, T, H, device=dev)
+    nb = max(int(N.query('asr_lstm_uni_workspace_bytes', B, H, cd, 0)), 256)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    lens_d = torch.as_tensor(np.asarray(lens, np.int32)).to(dev)
+    rc = N.query('asr_lstm_uni_forward', N.ptr(act), N.ptr(whh), N.ASR_DT_F32, N.ptr(lens_d), B, T,
+                 H, cd, N.ptr(y_off), N.ptr(cst), None, N.ptr(ws), nb, N.stream_handle(dev))
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert torch.equal(y, y_off)
+    for b, n in enumerate(lens):
+        assert torch.equal(h[b], y_off[b, n - 1]), ('h_out of row', b)
+        assert torch.equal(c[b], cst[b, n - 1]), ('c_out of row', b)
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
